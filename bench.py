@@ -2,13 +2,24 @@
 """Headline benchmark: AlignNet-3D point-cloud pairs/sec at N=1024 on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode infer|train] [--batch B] [--workload pointnet|dgcnn]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if --dump-outputs is given, and
+prints the line: the headline and the roofline of its own timed region.  Everything else the benchmark measures -- the CPU
+baseline, the K steps again without the kernel timers, the sustained loop, the split-bf16 / training / PCIe-inclusive / dgcnn /
+loader / ICP legs and, at --gpus N > 1, the single-rank reference and the sync-BN latency probe -- runs with --full only.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy (float32): the eight
+output arrays of the forward (--mode infer) or every variable of the model after the step (--mode train, `/` in a name becomes `__`).
+Inputs, weights and engine seed are fixed, so two builds run with the same arguments can be compared output for output.  Above
+64 MB in all, a fixed seeded sample of rows of each array is written instead.
 
 A "step" is one pass of the hot path (models/tp8.py get_model, eval mode, i.e. the reference's timed `sess.run`,
 train.py:447-449) over one batch of synthetic pairs that is already resident in HBM.  Workload at N=1 =
 BASELINE.json configs[1]: SynthCars widths, batch 256, N=1024, fp32.  With --gpus N (launched under
 torch.distributed.run, one rank per GPU) every rank processes its own batch of 256 pairs (weak scaling; pairs are
 independent in eval mode so the inference path has no data-path collective); value = all pairs / max-over-ranks time.
-For N > 1 the training leg runs by default as well: data-parallel steps with the library's RCCL all-reduce over xGMI.
+With --full and N > 1 the training leg runs as well: data-parallel steps with the library's RCCL all-reduce over xGMI.
 
 Prints ONE JSON line (rank 0).  Every timed leg (headline, `infer_bf16x3`, `train`, `train.bf16`) carries a `roofline`
 object: dominant kernel = the timed kernel with the largest HIP-event time inside that leg's timed region (events on the
@@ -235,7 +246,7 @@ def engine_options(eng):
 
 
 def extra_legs(eng, local_rank, min_seconds):
-    """Short secondary legs appended to the default one-GPU inference run so that the driver's record carries BASELINE.json configs[4]
+    """Short secondary legs appended to the one-GPU inference run with --full so that the line carries BASELINE.json configs[4]
     (DGCNN, N = 4096) and the SURVEY 8(f) rows: dgcnn inference at one GPU's share of configs[4] (512 pairs), dgcnn training steps
     (fp32 / bf16 convs, 64 pairs), the batch loader (reference-style files vs packed cache on the host; HBM-resident dataset + device
     sampler feeding training steps) and the ICP refinement.  About 6 s in total; never part of `value`."""
@@ -363,6 +374,28 @@ def extra_legs(eng, local_rank, min_seconds):
     return out
 
 
+DUMP_CAP_BYTES = 60_000_000   # array data; the .npy headers (~128 bytes per file) stay well inside the 64 MB the files may take
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES):
+    """arrays: {name: np.ndarray} -> out_dir/<name>.npy in float32.  Over `cap` bytes of data in all, each array keeps the same fixed,
+    seeded sample of its rows (an array of one row: of its elements), so the same arguments give the same sample in every run."""
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > cap:
+        frac = cap / total
+        for k, v in arrays.items():
+            if v.ndim and v.shape[0] <= 1:
+                v = v.reshape(-1)
+            if v.ndim and v.shape[0] > 1:
+                m = max(1, int(v.shape[0] * frac))
+                rows = np.sort(np.random.default_rng(0).choice(v.shape[0], m, replace=False))
+                arrays[k] = v[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def visible_gpus():
     import torch
     return torch.cuda.device_count()
@@ -416,11 +449,17 @@ def main():
     ap.add_argument("--infer-dtype", choices=["f32", "bf16x3"], default="f32",
                     help="inference backbone arithmetic of the timed region: exact fp32 MFMA (default, BASELINE.json configs[1]) or the "
                          "opt-in split-bf16 mode (three bf16 MFMAs per fp32 product, fp32 accumulate)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement the line can carry: CPU baseline, the K steps without kernel timers, "
+                         "sustained loop, split-bf16 / training / PCIe-inclusive / dgcnn / loader / ICP legs, single-rank reference (the --no-* "
+                         "switches below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train-leg", action="store_true")
     ap.add_argument("--no-split-leg", action="store_true")
     ap.add_argument("--no-pcie-leg", action="store_true")
-    ap.add_argument("--train-leg", action="store_true", help="(kept for compatibility: the training leg now runs by default, also for --gpus > 1)")
+    ap.add_argument("--train-leg", action="store_true", help="(kept for compatibility: the training leg runs with --full, also for --gpus > 1)")
     ap.add_argument("--allreduce-overlap", type=int, default=1, help="data-parallel training: bucketed all-reduce next to the backward (1) or one call after it (0)")
     ap.add_argument("--workload", choices=["pointnet", "dgcnn"], default="pointnet",
                     help="dgcnn = BASELINE.json configs[4] shape: N=4096, edge-conv branch (--mode train: fp32 only)")
@@ -429,11 +468,11 @@ def main():
     ap.add_argument("--sync-bn", type=int, default=0, help="data-parallel training legs (--gpus > 1): 1 = BatchNorm statistics and the loss over the global batch "
                                                              "(engine options sync_bn + global_loss: the reference's single-device semantics); 0 = local BN / local loss")
     ap.add_argument("--sustained-seconds", type=float, default=5.0,
-                    help="after the K timed steps: the same step back to back for at least this long (clock-settled rate + sclk readings); 0 = off")
+                    help="--full: after the K timed steps, the same step back to back for at least this long (clock-settled rate + sclk readings); 0 = off")
     ap.add_argument("--secondary-timeout", type=float, default=240.0,
                     help="--gpus > 1 under torch.distributed.run: if the legs AFTER the headline measurement (single-rank reference, sustained loop, training legs over "
                          "RCCL) have not finished after this many seconds, rank 0 prints the line with what is complete and every rank exits (0 = no watchdog)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the short dgcnn / loader / icp legs the default --gpus 1 inference run appends")
+    ap.add_argument("--no-extra-legs", action="store_true", help="skip the short dgcnn / loader / icp legs a --full --gpus 1 inference run appends")
     ap.add_argument("--grad-communicator", type=int, default=0,
                     help="data-parallel training: 1 = the gradient buckets travel on a second RCCL communicator of their own (alignnet_comm_init_grad), so that "
                          "sync-BN's per-layer sums do not serialise behind them; 0 = one communicator for everything")
@@ -549,6 +588,9 @@ def run_rank(args, real_stdout, threads):
     import alignnet3d
     from alignnet3d.synth import synth_pairs  # synthetic input generator (SURVEY 8d recipe); the oracle is only imported by cpu_baseline()
 
+    if not args.full:   # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_train_leg = args.no_split_leg = args.no_pcie_leg = args.no_extra_legs = True
+        args.sustained_seconds = 0
     if threads is not None:
         rank, local_rank, world = threads.get_rank(), 0, threads.get_world_size()
         args.gpus = world                         # (what the line reports as ranks; devices_used says one)
@@ -784,7 +826,15 @@ def run_rank(args, real_stdout, threads):
         spinup_steps += 8
     dt, kern = time_leg(step, args.steps, args.warmup)
     head_per_rank = time_leg.last_per_rank
-    dt_off, _ = time_leg(step, args.steps, 0, timers=False)   # (reported next to `value`, never instead of it: the same K steps without the kernel timers)
+    if args.dump_outputs and rank == 0:   # before anything else steps the engine: the last timed step's results
+        if args.mode == "train":
+            res = {name.replace("/", "__"): eng.get_variable(name) for name, _, _ in eng.variables()}
+        else:
+            res = {k: v.cpu().numpy() for k, v in outs.items()}
+        dump_outputs(args.dump_outputs, res)
+    dt_off = None
+    if args.full:   # (reported next to `value`, never instead of it: the same K steps without the kernel timers)
+        dt_off, _ = time_leg(step, args.steps, 0, timers=False)
     head_bf16 = (args.mode == "train" and args.train_dtype == "bf16") or (args.mode == "infer" and args.infer_dtype == "bf16x3")
     backbone_kernel = eng.last_backbone_kernel().split("<")[0] if args.mode == "infer" else "train"
     if args.mode == "infer":
@@ -816,8 +866,6 @@ def run_rank(args, real_stdout, threads):
             # every call of the headline step in this process (spin-up, warm-up, the K timed steps, their repeat with the timers off, the
             # sustained loop): tools/summarize_prof.py divides a profiled run's dispatch counts by THIS number
             "steps_executed": executed[0],
-            "without_kernel_timers": {"value": round(world * B * args.steps / dt_off, 1), "ms_per_step": round(dt_off / args.steps * 1e3, 4),
-                                      "what": "the same K steps again with the per-kernel HIP-event timers off (`value` is the region they run in)"},
             "whole_path_tflops": round(FLOPS_PER_PAIR_TOTAL * B * args.steps / dt / 1e12 * 1.0, 2)
             if world == 1 and not dg and npts == N_POINTS and args.mode == "infer" else None,
         }
@@ -835,6 +883,9 @@ def run_rank(args, real_stdout, threads):
             if dist_on:
                 line["allreduce_exposed_ms_per_step"] = round(kern.get("allreduce", (0.0, 0))[0] / args.steps, 4)
                 line.update(head_sync_bn)
+        if dt_off is not None:
+            line["without_kernel_timers"] = {"value": round(world * B * args.steps / dt_off, 1), "ms_per_step": round(dt_off / args.steps * 1e3, 4),
+                                             "what": "the same K steps again with the per-kernel HIP-event timers off (`value` is the region they run in)"}
         if dist_on:
             line["per_rank_pairs_per_s"] = per_rank_rates(head_per_rank, args.steps)
         if single_rank is not None:
@@ -894,7 +945,7 @@ def run_rank(args, real_stdout, threads):
 
     # ---- world > 1: what ONE rank of this very run does with the node to itself -- the N = 1 value this line scales from (rank 0 steps alone, the
     #      other ranks wait at the fence), so that the scaling efficiency value / (n_gpus x this) is computable from this one line
-    if dist is not None and world > 1:
+    if dist is not None and world > 1 and args.full:
         fence()
         if rank == 0:
             e1 = eng
@@ -1026,11 +1077,11 @@ def run_rank(args, real_stdout, threads):
         pcie_info["pipelined"] = {"value": round(B * kp / qdt, 1), "unit": "pairs/s", "ms_per_step": round(qdt / kp * 1e3, 4), "steps": kp,
                                   "what": "alignnet_forward_submit / _wait: the same pageable buffers in and out, two batches in flight (pinned staging, "
                                           "H2D on a copy stream under the previous batch's forward, D2H on a third stream)"}
-    # ---- short dgcnn / loader / icp legs (default one-GPU inference run only)
+    # ---- short dgcnn / loader / icp legs (one-GPU inference run with --full only)
     if not dist_on and args.mode == "infer" and not dg and args.infer_dtype == "f32" and not args.no_extra_legs:
         extra = extra_legs(eng, local_rank, args.min_leg_seconds)
     # the headline training leg's sync-BN latency probe is a collective: EVERY rank runs it (only rank 0 writes the line)
-    head_sync_bn = sync_bn_fields() if (dist_on and args.mode == "train") else {}
+    head_sync_bn = sync_bn_fields() if (dist_on and args.mode == "train" and args.full) else {}
     if dist is not None:
         dist.barrier()
 

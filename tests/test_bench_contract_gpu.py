@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def _run(*args, **extra_env):
     return json.loads(lines[0])
 
 
-def _check_common(d, steps, warmup):
+def _check_common(d, steps, warmup, timed_regions=2):
     for k in REQUIRED:
         assert k in d, k
     assert d["unit"] == "pairs/s" and d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup
@@ -37,13 +38,13 @@ def _check_common(d, steps, warmup):
         assert k in r, k
     assert r["bound"] in ("hbm", "mfma", "valu") and r["unit"] == {"hbm": "GB/s", "mfma": "TFLOP/s", "valu": "Ginstr/s"}[r["bound"]]
     assert abs(r["frac"] - r["achieved"] / r["peak"]) <= 1e-3 and 0.0 < r["frac"] < 1.0
-    # every call of the headline step is accounted for (tools/summarize_prof.py normalises profiled runs by this number)
-    assert d["steps_executed"] >= d["spinup_steps_untimed"] + warmup + 2 * steps
+    # every call of the headline step is accounted for (tools/summarize_prof.py normalises profiled runs by this number); --full times the K steps twice
+    assert d["steps_executed"] >= d["spinup_steps_untimed"] + warmup + timed_regions * steps
 
 
 def test_default_line(gpu_required):
-    """`python bench.py` (inference headline, BASELINE.json configs[1]) with its secondary legs and the CPU baseline."""
-    d = _run("--steps", "10", "--warmup", "2", "--min-leg-seconds", "0.05", "--sustained-seconds", "1.0")
+    """`python bench.py --full` (inference headline, BASELINE.json configs[1]) with its secondary legs and the CPU baseline."""
+    d = _run("--full", "--steps", "10", "--warmup", "2", "--min-leg-seconds", "0.05", "--sustained-seconds", "1.0")
     _check_common(d, 10, 2)
     su = d["sustained"]
     assert su["seconds"] >= 1.0 and su["steps"] > 10 and 0.7 * d["value"] < su["value"] < 1.2 * d["value"], su
@@ -75,7 +76,7 @@ def test_default_line(gpu_required):
                                          (("--workload", "dgcnn", "--batch", "32", "--points", "1024"), "dgcnn_fused"),
                                          (("--workload", "dgcnn", "--mode", "train", "--train-dtype", "bf16", "--batch", "256", "--points", "512"), "dg_train_bwd_edge")])   # (a full chip: below 256 clouds the edge kernels split clouds over workgroups and another pass may lead)
 def test_other_lines(gpu_required, args, kernel):
-    d = _run(*args, "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--sustained-seconds", "0")
+    d = _run(*args, "--full", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--sustained-seconds", "0")
     _check_common(d, 5, 1)
     assert d["roofline"]["kernel"].startswith(kernel), d["roofline"]["kernel"]
     if kernel == "train_bwd_b2":
@@ -95,7 +96,7 @@ def test_force_dist_rehearsal_at_world_1(gpu_required, args):
     sustained loop's flag all-reduce, the training headline and the training legs with both --allreduce-overlap values and
     --sync-bn 1 -- rehearsed at world = 1 on this box's one GPU (--force-dist), so that the driver's 8-GPU node is not its first
     execution.  What a 1-GPU box cannot show is xGMI itself: the scaling curve stays the driver's to measure."""
-    d = _run("--force-dist", *args, "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--sustained-seconds", "0.6")
+    d = _run("--force-dist", "--full", *args, "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--sustained-seconds", "0.6")
     _check_common(d, 5, 1)
     assert "forced_dist" in d and d["n_gpus"] == 1
     assert d["per_rank_pairs_per_s"]["ranks"] == 1 and abs(d["per_rank_pairs_per_s"]["min"] - d["value"]) <= 2e-2 * d["value"]
@@ -114,7 +115,7 @@ def test_a_hung_secondary_leg_costs_the_leg_not_the_line(gpu_required):
     """Real ranks (torch.distributed.run): everything after the headline measurement -- the single-rank reference, the sustained loop, the training legs over
     RCCL -- runs under a watchdog (--secondary-timeout).  With a stand-in for a collective that never returns (BENCH_TEST_HANG_AFTER_HEADLINE) rank 0 still
     prints the one line, complete in its contract fields and marked `incomplete`, and the processes exit 0."""
-    d = _run("--force-dist", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--secondary-timeout", "3", BENCH_TEST_HANG_AFTER_HEADLINE="1")
+    d = _run("--force-dist", "--full", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--secondary-timeout", "3", BENCH_TEST_HANG_AFTER_HEADLINE="1")
     _check_common(d, 5, 1)
     assert "watchdog" in d["incomplete"] and "train" not in d and "sustained" not in d
     assert d["roofline"]["frac"] > 0.5 and d["per_rank_pairs_per_s"]["ranks"] == 1
@@ -131,7 +132,7 @@ def test_world_2_rehearsal_on_one_gpu(gpu_required, args):
     rank count, the exposed all-reduce, the single-rank reference the line scales from."""
     env = dict(os.environ, BENCH_REHEARSAL_TIMEOUT_S="120")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rehearse-world", "2", *args, "--steps", "5", "--warmup", "1", "--sustained-seconds", "0.3"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rehearse-world", "2", "--full", *args, "--steps", "5", "--warmup", "1", "--sustained-seconds", "0.3"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -150,3 +151,46 @@ def test_world_2_rehearsal_on_one_gpu(gpu_required, args):
     else:
         for leg in (d["train"], d["train"]["bf16"]):
             assert leg["rccl_ranks"] == 2 and leg["per_rank_pairs_per_s"]["ranks"] == 2, leg
+
+
+@pytest.mark.parametrize("mode", ["infer", "train"])
+def test_plain_line_and_dumped_outputs(gpu_required, mode, tmp_path):
+    """A plain run (no --full) times the K steps once and measures nothing besides the headline; --dump-outputs writes what the last timed
+    step computed: the forward's eight outputs (infer), every variable of the model after the step (train)."""
+    out = tmp_path / "outputs"
+    d = _run("--mode", mode, "--steps", "7", "--warmup", "2", "--dump-outputs", str(out))
+    _check_common(d, 7, 2, timed_regions=1)
+    assert d["steps_executed"] == d["spinup_steps_untimed"] + 2 + 7
+    for k in ("cpu_baseline", "without_kernel_timers", "sustained", "infer_bf16x3", "train", "pcie_inclusive", "dgcnn", "loader", "icp"):
+        assert k not in d, k
+    files = sorted(p.name for p in out.iterdir())
+    assert sum((out / f).stat().st_size for f in files) <= 64 << 20
+    arrays = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    import alignnet3d
+    from alignnet3d.synth import synth_pairs
+    cfg = alignnet3d.default_model_config()
+    cfg["model"]["num_points"], cfg["training"]["batch_size"] = 1024, 256
+    eng = alignnet3d.Engine(cfg, device=0, seed=0)
+    if mode == "train":
+        assert files == sorted(name.replace("/", "__") + ".npy" for name, _, _ in eng.variables())
+        # the dump holds the variables after the training steps, not the initial ones (same seed and config as the bench's engine)
+        weights = [name for name, _, trainable in eng.variables() if trainable and name.endswith("weights")]
+        assert len(weights) > 10
+        for name in weights:
+            init = eng.get_variable(name)
+            got = arrays[name.replace("/", "__")]
+            assert got.shape == init.shape and not np.array_equal(got, init), name
+        eng.close()
+        return
+    assert files == sorted(k + ".npy" for k in alignnet3d.OUTPUT_NAMES)
+    # the same forward on the bench's inputs and weights, through the host path of a fresh engine
+    for name, shp, _ in eng.variables():
+        if name.endswith("moving_var"):
+            eng.set_variable(name, np.ones(shp[0] * shp[1], np.float32))
+    src = synth_pairs(256, 1024, seed=1234, dtype=np.float32)
+    ref = eng.forward(src["pcs1"], src["pcs2"])
+    eng.close()
+    for k in alignnet3d.OUTPUT_NAMES:
+        assert arrays[k].shape == ref[k].shape, k
+        np.testing.assert_allclose(arrays[k], ref[k], rtol=0, atol=1e-5, err_msg=k)

@@ -232,21 +232,35 @@ def test_evaluate_numbers_match_the_reference(tiny, tmp_path, kind):
         vars(cfg.data)["basepath"] = old
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs"), reason="the reference only exists in the build container")
-def test_every_shipped_reference_config_marshals(tiny, monkeypatch):
-    """Each configs/*.json of the reference (read in place, build container only) through the drop-in's config.py merge and the
+REFERENCE_SCHEMA_CONFIGS = {   # user files in the reference's schema, merged over config.py's defaults (the reference's default.json values)
+    "Defaults": {},
+    "Points512": {"model": {"num_points": 512}},
+    "Points512Half": {"model": {"num_points": 512, "options": {"angle_factor": 0.5}}},
+    "Dgcnn512": {"model": {"backbone": "dgcnn", "num_points": 512, "options": {"angle_factor": 0.5}}},
+    "Bins50Inverted": {"model": {"angles": {"num_bins": 50, "accept_inverted_angle": True}}},
+    "Batch128": {"model": {"num_points": 512}, "training": {"batch_size": 128, "learning_rate": 0.001}},
+    "NarrowStage1": {"model": {"options": {"s1transformer": [[64, 64, 128], [[256, 128], 0.5]]}}},
+    "ShallowEmbedding": {"model": {"options": {"embedding": [64, 128, 1024], "remaining_transform_prediction": [[256, 128], 0.6]}}},
+}
+
+
+def test_reference_schema_configs_marshal(tiny, monkeypatch):
+    """Configs in the reference's schema -- its defaults (five-deep s2 and embedding, s1 [128, 128, 256], N = 1024) and the overrides its
+    dataset configs make (N = 512, angle_factor 0.5, dgcnn, bins, batch, narrower stages) -- through the drop-in's config.py merge and the
     engine's config marshalling (make_c_config): num_points / bins / widths / keep probabilities / schedules arrive as written,
     and nothing that the engine does not build (loss variants, backbones) slips through silently."""
-    import glob
     from alignnet3d.engine import make_c_config
     cfgmod = tiny["config"]
     monkeypatch.setattr(cfgmod, "_read_split", lambda path: list(range(1000)))   # the datasets are not here: ntrain / nval only
     seen = 0
-    for path in sorted(glob.glob("/root/reference/configs/*.json")):
-        user = json.load(open(path))
+    for name, user in REFERENCE_SCHEMA_CONFIGS.items():
+        user = json.loads(json.dumps(user))
+        user.setdefault("data", {})["basepath"] = os.path.join(tiny["tmp"], name)
+        path = os.path.join(tiny["tmp"], name + ".json")
+        json.dump(user, open(path, "w"))
         cfgmod.reset_config()
         cfg = cfgmod.load_config(path)
-        assert cfg.name == os.path.basename(path)[:-5] and cfg.data.ntrain == 1000
+        assert cfg.name == name and cfg.data.ntrain == 1000
         c = make_c_config(cfg)
         m = cfg.to_dict()["model"]
         assert c.num_points == m["num_points"] and c.num_bins == m["angles"]["num_bins"]
@@ -255,7 +269,7 @@ def test_every_shipped_reference_config_marshals(tiny, monkeypatch):
         assert list(c.s2_conv.w[:c.s2_conv.n]) == m["options"]["s2transformer"][0]
         assert list(c.emb_conv.w[:c.emb_conv.n]) == m["options"]["embedding"]
         assert list(c.rem_fc.w[:c.rem_fc.n]) == m["options"]["remaining_transform_prediction"][0]
-        assert abs(c.s1_keep - m["options"]["s1transformer"][1][1]) < 1e-7
+        assert abs(c.s1_keep - m["options"]["s1transformer"][1][1]) < 1e-7 and abs(c.angle_factor - m["options"]["angle_factor"]) < 1e-7
         assert c.batch_size == cfg.training.batch_size and abs(c.learning_rate - cfg.training.learning_rate) < 1e-9
         assert c.accept_inverted_angle == int(m["angles"]["accept_inverted_angle"])
         if "model" in user and "num_points" in user["model"]:
