@@ -31,6 +31,7 @@ KERNEL_IDS = {"pointnet_fused": 1, "pointnet_fused<64,128>": 2, "pointnet_fused<
               "pointnet_split": 5, "pointnet_split<64,128>": 6, "pointnet_split_persist": 7, "pointnet_fused<64,128,k16,tp64>": 8, "dgcnn_fused": 10, "dgcnn_fused<64,128>": 11,
               "dgcnn_split": 12, "dgcnn_split<64,128>": 13}
 KERNEL_NAMES = {v: k for k, v in KERNEL_IDS.items()}
+ICP_FULL_ROTATION = 1   # include/alignnet_hip.h ALIGNNET_ICP_FULL_ROTATION: flags bit of alignnet_icp_register*
 
 
 class EngineError(RuntimeError):
@@ -122,6 +123,20 @@ def make_c_config(cfg, device=None, seed=0):
 
 def _fp(a):
     return a.ctypes.data_as(_capi.FP)
+
+
+def centroid_inits(points1, points2, offsets, rows):
+    """icp.py:62-66 get_centroid_init for the examples at `rows` of packed tables (points1 / points2 [n, >=3], offsets
+    [n + 1, 2] as uploaded with Engine.upload_dataset): identity rotation, translation = mean(pc2) - mean(pc1), the means
+    taken in float64 over the float64 copy of the cloud as Open3D's points hold it.  [B, 4, 4] float64; a pair with an
+    empty cloud keeps translation 0 (the reference's mean of nothing is NaN)."""
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    out = np.tile(np.eye(4), (rows.size, 1, 1))
+    for k, i in enumerate(rows):
+        (a1, a2), (b1, b2) = offsets[i], offsets[i + 1]
+        if b1 > a1 and b2 > a2:
+            out[k, :3, 3] = np.array(points2[a2:b2, :3], np.float64).mean(axis=0) - np.array(points1[a1:b1, :3], np.float64).mean(axis=0)
+    return out
 
 
 class Engine:
@@ -334,6 +349,8 @@ class Engine:
         return arrs
 
     # ---- ICP refinement on the full clouds (icp.py:69-78 / train.py:463-484) ------
+    centroid_inits = staticmethod(centroid_inits)
+
     @staticmethod
     def _icp_bufs(inits, B):
         init = np.ascontiguousarray(inits, np.float64).reshape(B, 16)
@@ -342,24 +359,34 @@ class Engine:
         dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
         return init, out, fit, rmse, its, dp
 
-    def icp_refine(self, sources, targets, inits, radius=0.1, its=30):
-        """sources / targets: lists of [n, 3] arrays; inits: [B, 4, 4].  Returns dict(transforms, fitness, rmse, iterations)."""
+    def icp_refine(self, sources, targets, inits, radius=0.1, its=30, constrained=True):
+        """sources / targets: lists of [n, 3] arrays; inits: [B, 4, 4].  Returns dict(transforms, fitness, rmse, iterations).
+        constrained=True: rotation about z only (with_constraint=True, alignnet_icp_refine); False: full 3-D rotation
+        (with_constraint=False, alignnet_icp_register with ALIGNNET_ICP_FULL_ROTATION)."""
         B = len(sources)
         off = np.zeros((B + 1, 2), np.int64)
         off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
         cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
         p1, p2 = cat(sources), cat(targets)
         init, out, fit, rmse, it, dp = self._icp_bufs(inits, B)
-        self._check(self._lib.alignnet_icp_refine(self._h, _fp(p1), _fp(p2), off.ctypes.data_as(C.POINTER(C.c_int64)), B, dp(init),
-                                                  float(radius), int(its), dp(out), dp(fit), dp(rmse), it.ctypes.data_as(C.POINTER(C.c_int32))))
+        offp, itp = off.ctypes.data_as(C.POINTER(C.c_int64)), it.ctypes.data_as(C.POINTER(C.c_int32))
+        if constrained:
+            self._check(self._lib.alignnet_icp_refine(self._h, _fp(p1), _fp(p2), offp, B, dp(init), float(radius), int(its), dp(out), dp(fit), dp(rmse), itp))
+        else:
+            self._check(self._lib.alignnet_icp_register(self._h, _fp(p1), _fp(p2), offp, B, dp(init), float(radius), int(its), ICP_FULL_ROTATION,
+                                                        dp(out), dp(fit), dp(rmse), itp))
         return dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, iterations=it)
 
-    def icp_refine_rows(self, rows, inits, radius=0.1, its=30):
+    def icp_refine_rows(self, rows, inits, radius=0.1, its=30, constrained=True):
         """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows."""
         r, rp = self._rows(rows)
         init, out, fit, rmse, it, dp = self._icp_bufs(inits, r.size)
-        self._check(self._lib.alignnet_icp_refine_dataset(self._h, rp, r.size, dp(init), float(radius), int(its), dp(out), dp(fit), dp(rmse),
-                                                          it.ctypes.data_as(C.POINTER(C.c_int32))))
+        itp = it.ctypes.data_as(C.POINTER(C.c_int32))
+        if constrained:
+            self._check(self._lib.alignnet_icp_refine_dataset(self._h, rp, r.size, dp(init), float(radius), int(its), dp(out), dp(fit), dp(rmse), itp))
+        else:
+            self._check(self._lib.alignnet_icp_register_dataset(self._h, rp, r.size, dp(init), float(radius), int(its), ICP_FULL_ROTATION,
+                                                                dp(out), dp(fit), dp(rmse), itp))
         return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
 
     @staticmethod

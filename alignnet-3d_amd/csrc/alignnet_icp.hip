@@ -22,6 +22,10 @@
 // lane whose smallest is under it and whose second smallest is not evaluates that ONE target in fp64 (the old arithmetic); a lane with two or more under
 // it (a near-tie inside its slice: rare) walks its slice in fp64 as before; the quad's (distance, index) minima meet as before.  Same decisions as the
 // all-fp64 scan at a third of its vector-issue time (a first form with the fp64 evaluation inside the scan loop spilled around the branch: 7.7 ms).
+// icp_kernel<kFull>: the estimate kind.  kFull = false is the z-constrained estimate above (with_constraint=True).  kFull = true is Open3D's
+// unconstrained point-to-point estimate (with_constraint=False: Eigen::umeyama(src, dst, false) over the inlier correspondences), used by the
+// ICP baseline evaluation mode (icp.py:150-213): the same scan, 17 sums instead of 10 (count, sum a, sum b, the nine entries of sum b a^T, sum of
+// distances, all about the same pivot), then the 3x3 Umeyama rotation in fp64 on one lane (icp_umeyama_rotation: one-sided Jacobi SVD).
 #include "engine.h"
 #include <cmath>
 #include <vector>
@@ -36,7 +40,8 @@ int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1;
     if (e_ != hipSuccess) return fail(h, std::string(#expr) + ": " + hipGetErrorString(e_));     \
   } while (0)
 
-constexpr int kIcpThreads = 1024, kIcpSums = 12, kIcpSplit = 4;   // threads per pair; lanes per source point
+constexpr int kIcpThreads = 1024, kIcpSums = 12, kIcpSplit = 4;   // threads per pair; sums of the z-constrained estimate; lanes per source point
+constexpr int kIcpSumsFull = 17;     // sums of the full-rotation estimate: count, a (3), b (3), b a^T (9), distance
 constexpr float kIcpFar = 1e18f;      // padding of the fp32 slices: a distance of 3e36, under no threshold
 typedef float icp_f32x2 __attribute__((ext_vector_type(2)));
 
@@ -65,29 +70,107 @@ struct IcpArgs {
   double* fitness; double* rmse; int* iters;   // [B] each, may be null
 };
 
-__device__ __forceinline__ void block_reduce(double (&v)[kIcpSums], double* red /*[waves][kIcpSums]*/, double* tot /*[kIcpSums]*/)
+template <int N>
+__device__ __forceinline__ void block_reduce(double (&v)[N], double* red /*[waves][N]*/, double* tot /*[N]*/)
 {
 #pragma unroll
-  for (int k = 0; k < kIcpSums; ++k)
+  for (int k = 0; k < N; ++k)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
   __syncthreads();
   if ((threadIdx.x & 63) == 0)
-    for (int k = 0; k < kIcpSums; ++k) red[(threadIdx.x >> 6) * kIcpSums + k] = v[k];
+    for (int k = 0; k < N; ++k) red[(threadIdx.x >> 6) * N + k] = v[k];
   __syncthreads();
-  if (threadIdx.x < kIcpSums) {
+  if (threadIdx.x < N) {
     double s = 0.0;
-    for (int w = 0; w < kIcpThreads / 64; ++w) s += red[w * kIcpSums + threadIdx.x];   // fixed order: deterministic
+    for (int w = 0; w < kIcpThreads / 64; ++w) s += red[w * N + threadIdx.x];   // fixed order: deterministic
     tot[threadIdx.x] = s;
   }
   __syncthreads();
 }
 
+// R = U diag(1, 1, sign(det U det V)) V^T for A = U S V^T (singular values descending): Eigen::umeyama's rotation without scaling, A = the
+// centred cross-covariance sum (q - mean q)(p - mean p)^T (its 1 / n does not change U, V).  One-sided Jacobi on the columns of A (A V -> U S),
+// fp64, one lane.  U is completed to a right-handed frame (u2 = u0 x u1; the sign fix then reads det V alone -- the same R, and no division by
+// the smallest singular value), and u1 is Gram-Schmidt'ed against u0 (or chosen orthogonal to it when A has rank <= 1: collinear or coincident
+// correspondences), so R is a finite proper rotation for every A.  The 3x3 matrices live in LDS (`work`, 27 doubles): held in registers
+// they made this one-lane step spill 6 VGPRs instead of 4 (the scan with 17 sums alone compiles spill-free).
+// In: work[0..8] = A (row-major).  Out: work[18..26] = R (row-major).
+__device__ __forceinline__ void icp_umeyama_rotation(double* work)
+{
+  double* a = work;       // columns -> U S
+  double* v = work + 9;   // columns -> V
+  double* R = work + 18;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) v[i] = i % 4 == 0 ? 1.0 : 0.0;
+#pragma unroll 1
+  for (int sweep = 0; sweep < 24; ++sweep) {
+    bool rotated = false;
+#pragma unroll
+    for (int pr = 0; pr < 3; ++pr) {
+      const int p = pr == 2 ? 1 : 0, q = pr == 0 ? 1 : 2;
+      double al = 0.0, be = 0.0, ga = 0.0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { al += a[i * 3 + p] * a[i * 3 + p]; be += a[i * 3 + q] * a[i * 3 + q]; ga += a[i * 3 + p] * a[i * 3 + q]; }
+      if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;   // columns orthogonal to working precision (or one of them zero)
+      const double ze = (be - al) / (2.0 * ga);
+      const double t = (ze >= 0.0 ? 1.0 : -1.0) / (fabs(ze) + sqrt(1.0 + ze * ze));
+      const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double ap = a[i * 3 + p], aq = a[i * 3 + q], vp = v[i * 3 + p], vq = v[i * 3 + q];
+        a[i * 3 + p] = c * ap - s * aq; a[i * 3 + q] = s * ap + c * aq;
+        v[i * 3 + p] = c * vp - s * vq; v[i * 3 + q] = s * vp + c * vq;
+      }
+      rotated = true;
+    }
+    if (!rotated) break;
+  }
+  double sv[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) sv[k] = a[k] * a[k] + a[3 + k] * a[3 + k] + a[6 + k] * a[6 + k];
+  // singular values descending (the sign fix acts on the smallest): compare-exchange of the column pairs (0,1), (1,2), (0,1)
+#pragma unroll
+  for (int pr = 0; pr < 3; ++pr) {
+    const int p = pr == 1 ? 1 : 0, q = p + 1;
+    if (sv[q] > sv[p]) {
+      const double w = sv[p]; sv[p] = sv[q]; sv[q] = w;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double x = a[i * 3 + p]; a[i * 3 + p] = a[i * 3 + q]; a[i * 3 + q] = x;
+        const double y = v[i * 3 + p]; v[i * 3 + p] = v[i * 3 + q]; v[i * 3 + q] = y;
+      }
+    }
+  }
+  double u0[3] = {1.0, 0.0, 0.0}, u1[3];
+  const double s0 = sqrt(sv[0]);
+  if (s0 > 1e-250)
+    for (int i = 0; i < 3; ++i) u0[i] = a[i * 3] / s0;
+  const double d01 = u0[0] * a[1] + u0[1] * a[4] + u0[2] * a[7];
+  for (int i = 0; i < 3; ++i) u1[i] = a[i * 3 + 1] - d01 * u0[i];
+  double n1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+  if (!(n1 > 1e-250 + 1e-300 * s0)) {   // rank <= 1: any unit vector orthogonal to u0 (the axis u0 is least aligned with, minus its u0 part)
+    const int k = fabs(u0[0]) <= fabs(u0[1]) ? (fabs(u0[0]) <= fabs(u0[2]) ? 0 : 2) : (fabs(u0[1]) <= fabs(u0[2]) ? 1 : 2);
+    for (int i = 0; i < 3; ++i) u1[i] = (i == k ? 1.0 : 0.0) - u0[k] * u0[i];
+    n1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+  }
+  for (int i = 0; i < 3; ++i) u1[i] /= n1;
+  const double u2[3] = {u0[1] * u1[2] - u0[2] * u1[1], u0[2] * u1[0] - u0[0] * u1[2], u0[0] * u1[1] - u0[1] * u1[0]};
+  const double detv = v[0] * (v[4] * v[8] - v[5] * v[7]) - v[1] * (v[3] * v[8] - v[5] * v[6]) + v[2] * (v[3] * v[7] - v[4] * v[6]);
+  const double d = detv < 0.0 ? -1.0 : 1.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) R[i * 3 + j] = u0[i] * v[j * 3] + u1[i] * v[j * 3 + 1] + d * u2[i] * v[j * 3 + 2];
+}
+
+template <bool kFull>
 __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
 {
+  constexpr int kSums = kFull ? kIcpSumsFull : kIcpSums;
   extern __shared__ __attribute__((aligned(16))) double tgt[];   // [3][lds_points] doubles | [3][4 slices][S4] floats
   __shared__ double T[12];            // rows 0..2 of the 4x4
-  __shared__ double red[(kIcpThreads / 64) * kIcpSums], tot[kIcpSums];
+  __shared__ double red[(kIcpThreads / 64) * kSums], tot[kSums];
   const int b = blockIdx.x, tid = threadIdx.x, sub = tid & (kIcpSplit - 1);
   const long long row = a.rows ? a.rows[b] : b;
   const long long s_lo = a.off[row * 2], n1 = a.off[(row + 1) * 2] - s_lo;
@@ -120,9 +203,9 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
   if (n1 > 0 && n2 > 0)
     for (k = 0;; ++k) {
       // ---- evaluate(T): nearest target point of every transformed source point, sums over the inliers ----
-      double v[kIcpSums];
+      double v[kSums];
 #pragma unroll
-      for (int q = 0; q < kIcpSums; ++q) v[q] = 0.0;
+      for (int q = 0; q < kSums; ++q) v[q] = 0.0;
       for (long long i0 = 0; i0 < n1; i0 += kIcpThreads / kIcpSplit) {
         const long long i = i0 + (tid / kIcpSplit);
         const bool active = i < n1;                      // (inactive quads run along on the last point: the shuffles below want every lane)
@@ -192,16 +275,43 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
           const double qz = bj < nl ? tz[bj] : (double)dst[(long long)bj * 3 + 2];
           const double ax = px - cx, ay = py - cy, az = pz - cz, bx = qx - cx, by = qy - cy, bz = qz - cz;
           v[0] += 1.0; v[1] += ax; v[2] += ay; v[3] += az; v[4] += bx; v[5] += by; v[6] += bz;
-          v[7] += ax * bx + ay * by; v[8] += ax * by - ay * bx; v[9] += best;
+          if constexpr (kFull) {   // sum b a^T, row-major
+            v[7] += bx * ax; v[8] += bx * ay; v[9] += bx * az;
+            v[10] += by * ax; v[11] += by * ay; v[12] += by * az;
+            v[13] += bz * ax; v[14] += bz * ay; v[15] += bz * az; v[16] += best;
+          } else {
+            v[7] += ax * bx + ay * by; v[8] += ax * by - ay * bx; v[9] += best;
+          }
         }
       }
       block_reduce(v, red, tot);
       const double cnt = tot[0];
       fit = cnt / (double)n1;
-      rmse = cnt > 0.0 ? sqrt(tot[9] / cnt) : 0.0;
+      rmse = cnt > 0.0 ? sqrt(tot[kFull ? 16 : 9] / cnt) : 0.0;
       if (k > 0 && fabs(fit - fit_prev) < 1e-6 && fabs(rmse - rmse_prev) < 1e-6) break;
       if (k == a.its) break;
       fit_prev = fit; rmse_prev = rmse;
+      if constexpr (kFull) {
+        // ---- estimate: rotation + translation minimising sum |R p + t - q|^2 over the correspondences (Umeyama, no scaling) ----
+        if (tid == 0 && cnt > 0.0) {
+          const double am[3] = {tot[1] / cnt, tot[2] / cnt, tot[3] / cnt}, bm[3] = {tot[4] / cnt, tot[5] / cnt, tot[6] / cnt};   // about the pivot
+          double* const Rm = red + 18;   // (red is free until the next block_reduce: A, the SVD's work, R)
+#pragma unroll
+          for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) red[i * 3 + j] = tot[7 + i * 3 + j] - cnt * (bm[i] * am[j]);
+          icp_umeyama_rotation(red);
+          const double mp[3] = {cx + am[0], cy + am[1], cz + am[2]}, mq[3] = {cx + bm[0], cy + bm[1], cz + bm[2]};
+          // T <- U T,  U = [R | mean q - R mean p]
+          double n[12];
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+            for (int col = 0; col < 4; ++col) n[r * 4 + col] = Rm[r * 3] * T[col] + Rm[r * 3 + 1] * T[4 + col] + Rm[r * 3 + 2] * T[8 + col];
+            n[r * 4 + 3] += mq[r] - (Rm[r * 3] * mp[0] + Rm[r * 3 + 1] * mp[1] + Rm[r * 3 + 2] * mp[2]);
+          }
+          for (int q = 0; q < 12; ++q) T[q] = n[q];
+        }
+      } else
       // ---- estimate: rotation about z + translation minimising sum |Rz p + t - q|^2 over the correspondences ----
       if (tid == 0 && cnt > 0.0) {
         const double apx = tot[1] / cnt, apy = tot[2] / cnt, apz = tot[3] / cnt;   // means about the pivot
@@ -235,7 +345,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
 
 // shared driver: tables already on the device
 int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long long* d_off, const int* d_rows, long long max_n2,
-            int B, const double* init, double radius, int its, double* out, double* fitness, double* rmse, int* iters)
+            int B, const double* init, double radius, int its, bool full, double* out, double* fitness, double* rmse, int* iters)
 {
   if (!init || !out) return fail(h, "icp: null init / out");
   if (!(radius > 0.0) || its < 0) return fail(h, "icp: radius must be > 0 and its >= 0");
@@ -250,12 +360,16 @@ int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long
   const long long budget = (150 * 1024) / 36;   // doubles x 3 + floats x 3 per point within one CU's LDS
   a.lds_points = (int)std::max<long long>(1, std::min(budget, max_n2));
   a.out = d_out; a.fitness = d_fr; a.rmse = d_fr + B; a.iters = d_it;
-  static alignnet::PerDeviceOnce attr;
-  if (attr.need(h->cfg.device)) {
-    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(icp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
-    attr.mark(h->cfg.device);
+  static alignnet::PerDeviceOnce attr[2];
+  const void* kernel = full ? reinterpret_cast<const void*>(icp_kernel<true>) : reinterpret_cast<const void*>(icp_kernel<false>);
+  if (attr[full].need(h->cfg.device)) {
+    HIP_TRY(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+    attr[full].mark(h->cfg.device);
   }
-  hipLaunchKernelGGL(icp_kernel, dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
+  if (full)
+    hipLaunchKernelGGL(icp_kernel<true>, dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
+  else
+    hipLaunchKernelGGL(icp_kernel<false>, dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(out, d_out, (size_t)B * 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (fitness) HIP_TRY(h, hipMemcpyAsync(fitness, d_fr, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -266,22 +380,21 @@ int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long
   return 0;
 }
 
-}  // namespace
-
-extern "C" int alignnet_icp_refine(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
-                                   const double* init, double radius, int32_t its, double* out, double* fitness, double* rmse,
-                                   int32_t* iterations)
+// clouds passed from the host (alignnet_icp_refine / alignnet_icp_register); `fn` names the entry point in the messages
+int icp_host(alignnet_handle* h, const char* fn, const float* points1, const float* points2, const int64_t* offsets, int32_t B, const double* init,
+             double radius, int32_t its, bool full, double* out, double* fitness, double* rmse, int32_t* iterations)
 {
   if (!h) return 1;
-  if (!offsets || B < 1) return fail(h, "alignnet_icp_refine: null offsets or B < 1");
+  const std::string name(fn);
+  if (!offsets || B < 1) return fail(h, name + ": null offsets or B < 1");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   long long max_n2 = 0;
   for (int i = 0; i < B; ++i) {
-    if (offsets[(i + 1) * 2] < offsets[i * 2] || offsets[(i + 1) * 2 + 1] < offsets[i * 2 + 1]) return fail(h, "alignnet_icp_refine: offsets must be non-decreasing");
+    if (offsets[(i + 1) * 2] < offsets[i * 2] || offsets[(i + 1) * 2 + 1] < offsets[i * 2 + 1]) return fail(h, name + ": offsets must be non-decreasing");
     max_n2 = std::max<long long>(max_n2, offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1]);
   }
   const size_t n0 = (size_t)offsets[B * 2], n1 = (size_t)offsets[B * 2 + 1];
-  if ((n0 && !points1) || (n1 && !points2)) return fail(h, "alignnet_icp_refine: null point blob");
+  if ((n0 && !points1) || (n1 && !points2)) return fail(h, name + ": null point blob");
   float *d0 = nullptr, *d1 = nullptr; long long* doff = nullptr;
   HIP_TRY(h, hipMalloc(&d0, std::max<size_t>(n0, 1) * 3 * sizeof(float)));
   HIP_TRY(h, hipMalloc(&d1, std::max<size_t>(n1, 1) * 3 * sizeof(float)));
@@ -289,26 +402,70 @@ extern "C" int alignnet_icp_refine(alignnet_handle* h, const float* points1, con
   if (n0) HIP_TRY(h, hipMemcpyAsync(d0, points1, n0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   if (n1) HIP_TRY(h, hipMemcpyAsync(d1, points2, n1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(doff, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  const int rc = run_icp(h, d0, d1, doff, nullptr, max_n2, B, init, radius, its, out, fitness, rmse, iterations);
+  const int rc = run_icp(h, d0, d1, doff, nullptr, max_n2, B, init, radius, its, full, out, fitness, rmse, iterations);
   hipFree(d0); hipFree(d1); hipFree(doff);
   return rc;
 }
 
-extern "C" int alignnet_icp_refine_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
-                                           int32_t its, double* out, double* fitness, double* rmse, int32_t* iterations)
+// clouds of the uploaded dataset addressed by rows (alignnet_icp_refine_dataset / alignnet_icp_register_dataset)
+int icp_rows(alignnet_handle* h, const char* fn, const int32_t* rows, int32_t B, const double* init, double radius, int32_t its, bool full,
+             double* out, double* fitness, double* rmse, int32_t* iterations)
 {
   if (!h) return 1;
+  const std::string name(fn);
   alignnet::DatasetTables t;
-  if (!alignnet_dataset_tables(h, &t)) return fail(h, "alignnet_icp_refine_dataset: no dataset uploaded");
-  if (!rows || B < 1) return fail(h, "alignnet_icp_refine_dataset: null rows or B < 1");
+  if (!alignnet_dataset_tables(h, &t)) return fail(h, name + ": no dataset uploaded");
+  if (!rows || B < 1) return fail(h, name + ": null rows or B < 1");
   for (int i = 0; i < B; ++i)
-    if (rows[i] < 0 || rows[i] >= t.n) return fail(h, "alignnet_icp_refine_dataset: row " + std::to_string(rows[i]) + " out of range");
+    if (rows[i] < 0 || rows[i] >= t.n) return fail(h, name + ": row " + std::to_string(rows[i]) + " out of range");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   int* d_rows = nullptr;
   HIP_TRY(h, hipMalloc(&d_rows, (size_t)B * sizeof(int)));
   HIP_TRY(h, hipMemcpyAsync(d_rows, rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   // the largest target cloud is not known on the host: size the LDS stage for the budget, the kernel clamps per pair
-  const int rc = run_icp(h, t.pts[0], t.pts[1], t.off, d_rows, (150 * 1024) / 36, B, init, radius, its, out, fitness, rmse, iterations);
+  const int rc = run_icp(h, t.pts[0], t.pts[1], t.off, d_rows, (150 * 1024) / 36, B, init, radius, its, full, out, fitness, rmse, iterations);
   hipFree(d_rows);
   return rc;
+}
+
+// flags of alignnet_icp_register*: bit 0 = full rotation; no other bit is defined
+int icp_flags(alignnet_handle* h, const char* fn, int32_t flags, bool* full)
+{
+  if (flags & ~1) return fail(h, std::string(fn) + ": unknown flags " + std::to_string(flags) + " (bit 0 = full rotation is the only one)");
+  *full = (flags & 1) != 0;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int alignnet_icp_refine(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
+                                   const double* init, double radius, int32_t its, double* out, double* fitness, double* rmse,
+                                   int32_t* iterations)
+{
+  return icp_host(h, "alignnet_icp_refine", points1, points2, offsets, B, init, radius, its, false, out, fitness, rmse, iterations);
+}
+
+extern "C" int alignnet_icp_refine_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
+                                           int32_t its, double* out, double* fitness, double* rmse, int32_t* iterations)
+{
+  return icp_rows(h, "alignnet_icp_refine_dataset", rows, B, init, radius, its, false, out, fitness, rmse, iterations);
+}
+
+extern "C" int alignnet_icp_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
+                                     const double* init, double radius, int32_t its, int32_t flags, double* out, double* fitness, double* rmse,
+                                     int32_t* iterations)
+{
+  if (!h) return 1;
+  bool full = false;
+  if (icp_flags(h, "alignnet_icp_register", flags, &full)) return 1;
+  return icp_host(h, "alignnet_icp_register", points1, points2, offsets, B, init, radius, its, full, out, fitness, rmse, iterations);
+}
+
+extern "C" int alignnet_icp_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
+                                             int32_t its, int32_t flags, double* out, double* fitness, double* rmse, int32_t* iterations)
+{
+  if (!h) return 1;
+  bool full = false;
+  if (icp_flags(h, "alignnet_icp_register_dataset", flags, &full)) return 1;
+  return icp_rows(h, "alignnet_icp_register_dataset", rows, B, init, radius, its, full, out, fitness, rmse, iterations);
 }

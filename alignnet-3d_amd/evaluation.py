@@ -57,6 +57,40 @@ def get_mat_angle(translation=None, rotation=None, rotation_center=(0.0, 0.0, 0.
     return m3 @ m2 @ m1
 
 
+def rotvec_z(R):
+    """z component of the rotation vector of each rotation matrix in R [..., 3, 3]: what the ICP baseline stores as the predicted
+    angle (icp.py:197-199, Rotation.from_dcm(R).as_rotvec()[2]) -- not atan2(R10, R00), which agrees only for a rotation about z.
+    Same steps as SciPy's: the quaternion by the largest of (trace, R00, R11, R22) (well conditioned at every angle), w >= 0, then
+    angle = 2 atan2(|v|, w) and v scaled by angle / sin(angle / 2), by its Taylor series below angle 1e-3."""
+    R = np.asarray(R, np.float64)
+    shape = R.shape[:-2]
+    m = R.reshape(-1, 3, 3)
+    q = np.empty((m.shape[0], 4))   # x, y, z, w
+    d = np.stack([m[:, 0, 0], m[:, 1, 1], m[:, 2, 2], m[:, 0, 0] + m[:, 1, 1] + m[:, 2, 2]], 1)
+    choice = d.argmax(1)
+    w = choice == 3
+    q[w, 0] = m[w, 2, 1] - m[w, 1, 2]
+    q[w, 1] = m[w, 0, 2] - m[w, 2, 0]
+    q[w, 2] = m[w, 1, 0] - m[w, 0, 1]
+    q[w, 3] = 1.0 + d[w, 3]
+    for i in range(3):
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = choice == i
+        q[s, i] = 1.0 - d[s, 3] + 2.0 * m[s, i, i]
+        q[s, j] = m[s, j, i] + m[s, i, j]
+        q[s, k] = m[s, k, i] + m[s, i, k]
+        q[s, 3] = m[s, k, j] - m[s, j, k]
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    q[q[:, 3] < 0] *= -1.0
+    angle = 2.0 * np.arctan2(np.linalg.norm(q[:, :3], axis=1), q[:, 3])
+    small = np.abs(angle) <= 1e-3
+    scale = np.empty_like(angle)
+    a2 = angle[small] ** 2
+    scale[small] = 2.0 + a2 / 12.0 + 7.0 * a2 * a2 / 2880.0
+    scale[~small] = angle[~small] / np.sin(angle[~small] / 2.0)
+    return (scale * q[:, 2]).reshape(shape)
+
+
 def translate_transform_to_new_center_of_rotation(pred_translations, pred_angles, pred_centers, gt_pc1centers):
     """Same map as tp_utils/pointcloud.py:309-318: t' = -d + Rz(angle) d + t with d = new_centre - old_centre."""
     out = np.zeros_like(pred_translations)

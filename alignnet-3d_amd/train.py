@@ -10,6 +10,7 @@ evaluation (one process per GPU; gradient all-reduce on RCCL inside the engine).
 import argparse
 import copy
 import datetime
+import json
 import logging
 import os
 import sys
@@ -321,6 +322,98 @@ class Run:
             logger.info("Interrupted")
 
 
+# ---- ICP baseline evaluation mode (evaluation.special.mode = "icp", icp.py:150-213) ---------------------------------------
+ICP_CHUNK = 4096   # pairs per registration call
+
+
+def icp_plan(icp):
+    """What evaluation.special.icp asks for: "centroid" (p2point: icp.py:69-78 from get_centroid_init) or "precomputed" (o3_gicp /
+    o3_gicp_fast with refine p2p: point-to-point ICP from the stored global-registration results, icp.py:157-169).  Anything else
+    raises NotImplementedError naming the variant and what is missing -- before an engine is created."""
+    variant = icp.variant
+    refine = icp.refine if icp.has("refine") else None
+    if variant == "p2point":
+        return "centroid"
+    if variant in ("o3_gicp", "o3_gicp_fast"):
+        if refine == "p2p":
+            return "precomputed"
+        if refine is None:
+            what = "RANSAC" if variant == "o3_gicp" else "fast global registration (FGR)"
+            raise NotImplementedError("evaluation.special.icp.variant=%s: its global registration (%s on FPFH features of 0.05 m voxel-downsampled "
+                                      "clouds, icp.py:85-143) is not built; only its 'refine': 'p2p' form runs, from the results of a global "
+                                      "registration stored in <logdir[:-4]>/val/eval000000" % (variant, what))
+        raise NotImplementedError("evaluation.special.icp.variant=%s with refine=%r: only refine 'p2p' is built (icp.py:112-116)" % (variant, refine))
+    if variant in ("p2plane", "goicp"):
+        raise NotImplementedError("evaluation.special.icp.variant=%s is not built: the reference's icp_%s is `assert False` too (icp.py:81-82, 146-147)"
+                                  % (variant, variant))
+    raise NotImplementedError("evaluation.special.icp.variant=%r is not an ICP baseline of the reference (icp.py:180-191)" % (variant,))
+
+
+def run_icp_mode(flags):
+    """icp.py:150-213 evaluate: register the FULL source cloud of every val pair onto its full target cloud (radius 0.10, 30 iterations,
+    point-to-point, with_constraint from the config), store T[:3, 3], the z component of T's rotation vector and zero centres, and evaluate
+    for accept_inverted_angle False / True with mean_time = registration time / nval.  The clouds are uploaded to HBM once and registered in
+    chunks on the GPU (alignnet_icp_register_dataset)."""
+    icp = cfg.evaluation.special.icp
+    plan = icp_plan(icp)
+    rank, local_rank, world = parallel.world_info()
+    if rank != 0:   # the reference's evaluate is one process: only rank 0 registers and writes
+        return
+    val = provider.getDataFiles("%s/split/val.txt" % cfg.data.basepath)
+    nval = len(val)
+    constrained = bool(icp.with_constraint)
+    total_time = 0.0
+    if plan == "precomputed":   # icp.py:157-169
+        gdir = "%s/val/eval%s" % (cfg.logging.logdir[:-4], str(0).zfill(6))
+        if not os.path.isdir(gdir):
+            raise FileNotFoundError("ICP refine of variant %s needs the precomputed global-registration results in %s (missing)" % (icp.variant, gdir))
+        gjson = "%s/eval_180.json" % gdir
+        if not os.path.isfile(gjson):
+            raise FileNotFoundError("ICP refine of variant %s needs %s (missing)" % (icp.variant, gjson))
+        with open(gjson) as fh:
+            total_time += json.load(fh)["mean_time"] * float(nval)
+        pre = {k: np.load("%s/%s.npy" % (gdir, k)) for k in ("pred_translations", "pred_angles", "pred_s1_pc1centers")}
+        logger.info("Precomputed results loaded from %s" % gdir)
+    packed = provider.use_packed_cache()
+    labels = provider.load_batch(val, override_batch_size=nval, dont_load_pointclouds=True)
+    gt_t, gt_a, gt_c1 = labels[2], labels[3], labels[4]
+    eval_dir = "%s/val/eval%s" % (cfg.logging.logdir, str(0).zfill(6))
+    if flags.use_old_results and os.path.isfile("%s/pred_translations.npy" % eval_dir):
+        pred_t = np.load("%s/pred_translations.npy" % eval_dir)
+        pred_a = np.load("%s/pred_angles.npy" % eval_dir)
+        pred_c = np.load("%s/pred_s1_pc1centers.npy" % eval_dir)
+        logger.info("ICP results of %s re-evaluated" % eval_dir)
+    else:
+        import alignnet3d
+        engine = alignnet3d.Engine(cfg, device=local_rank if world > 1 else None)
+        packed.upload(engine)
+        rows = packed.rows_of(val)
+        pred_t, pred_a = np.empty((nval, 3), np.float32), np.empty((nval, 1), np.float32)
+        pred_c = np.zeros((nval, 3), np.float32)   # the transforms are about the origin (icp.py:193-194)
+        for s in range(0, nval, ICP_CHUNK):
+            e = min(s + ICP_CHUNK, nval)
+            if plan == "centroid":
+                inits = alignnet3d.engine.centroid_inits(packed.p[0], packed.p[1], packed.off, rows[s:e])
+            else:
+                inits = [evaluation.get_mat_angle(pre["pred_translations"][i], pre["pred_angles"][i], rotation_center=pre["pred_s1_pc1centers"][i])
+                         for i in range(s, e)]
+            t0 = time.time()
+            T = engine.icp_refine_rows(rows[s:e], inits, radius=0.10, its=30, constrained=constrained)["transforms"]
+            total_time += time.time() - t0
+            pred_t[s:e] = T[:, :3, 3]
+            pred_a[s:e, 0] = evaluation.rotvec_z(T[:, :3, :3])
+        engine.close()
+        os.makedirs(eval_dir, exist_ok=True)
+        np.save("%s/pred_translations.npy" % eval_dir, pred_t)
+        np.save("%s/pred_angles.npy" % eval_dir, pred_a)
+        np.save("%s/pred_s1_pc1centers.npy" % eval_dir, pred_c)
+        logger.info("ICP (%s, %s estimate) on %d pairs: %.3f s" % (icp.variant, "z-constrained" if constrained else "full-rotation", nval, total_time))
+    mean_time = total_time / nval
+    for inv in (False, True):
+        ev = evaluation.evaluate(cfg, val, pred_t, pred_a, gt_t, gt_a, pred_c, gt_c1, eval_dir=eval_dir, accept_inverted_angle=inv, mean_time=mean_time)
+        logger.info(evaluation.ns_to_dict(ev))
+
+
 def main(argv=None):
     flags = parse_args(argv)
     load_config(flags.config)
@@ -342,9 +435,8 @@ def main(argv=None):
                 Run(flags).train(eval_only=True, eval_epoch=flags.eval_epoch, do_timings=True, override_batch_size=bs)
         elif mode == "held":         # train.py:553-554: eval_only with the checkpoint of another run's logdir
             Run(flags).train(eval_only=True, eval_epoch=flags.eval_epoch, eval_only_model_to_load=cfg.evaluation.special.held.model)
-        elif mode == "icp":
-            raise NotImplementedError("evaluation.special.mode=icp runs the reference's CPU ICP baselines (icp.py:80-330: global registration, "
-                                      "Go-ICP): out of scope (SURVEY 2); --refineICP is the supported ICP path")
+        elif mode == "icp":          # icp.py:150-213 (the reference's README: "Running ICP evaluations")
+            run_icp_mode(flags)
         else:
             assert False
     elif flags.operation == "train":

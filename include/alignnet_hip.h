@@ -314,6 +314,17 @@ int alignnet_icp_refine(alignnet_handle* h, const float* points1, const float* p
 int alignnet_icp_refine_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
                                 int32_t its, double* out, double* fitness, double* rmse, int32_t* iterations);
 
+/* ---- ICP registration with a choice of estimate (the ICP baseline evaluation mode, icp.py:150-213) ------------
+ * Same arguments and results as alignnet_icp_refine / _dataset, plus `flags`: bit 0 set = full 3-D rotation (Open3D's
+ * TransformationEstimationPointToPoint with with_constraint=False: Eigen::umeyama over the inlier correspondences,
+ * no scaling); clear = the z-constrained estimate, bit-identical to alignnet_icp_refine*.  Other bits are an error. */
+#define ALIGNNET_ICP_FULL_ROTATION 1
+int alignnet_icp_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
+                          const double* init, double radius, int32_t its, int32_t flags, double* out, double* fitness,
+                          double* rmse, int32_t* iterations);
+int alignnet_icp_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
+                                  int32_t its, int32_t flags, double* out, double* fitness, double* rmse, int32_t* iterations);
+
 /* ---- run-time options with no counterpart in the reference's config surface --------
  * "train_matmul_bf16" (0/1, default 0): training only -- the two MFMA convs of every backbone (the hidden 1x1 conv
  *   and the -> C3 feature lift, 96 % of the step's FLOPs, models/tp8.py:55-57), in the forward and in the backward's
