@@ -389,6 +389,66 @@ class Engine:
                                                                 dp(out), dp(fit), dp(rmse), itp))
         return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
 
+    # ---- global registration: RANSAC on FPFH feature matches (csrc/alignnet_globalreg.hip) ----
+    @staticmethod
+    def _global_bufs(B, streams, default_streams):
+        st = np.ascontiguousarray(default_streams if streams is None else streams, np.int32).ravel()
+        if st.size != B:
+            raise ValueError("streams: one id per pair (%d given for %d pairs)" % (st.size, B))
+        out = np.empty((B, 16), np.float64)
+        fit, rmse = np.empty(B, np.float64), np.empty(B, np.float64)
+        it, val = np.empty(B, np.int64), np.empty(B, np.int32)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        tail = (dp(out), dp(fit), dp(rmse), it.ctypes.data_as(C.POINTER(C.c_int64)), val.ctypes.data_as(C.POINTER(C.c_int32)))
+        return st, tail, lambda: dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, iterations=it, validations=val)
+
+    def global_register(self, sources, targets, constrained=True, seed=0, streams=None, max_iteration=4000000, max_validation=500):
+        """RANSAC on FPFH feature matches of the 5 cm voxel-downsampled clouds (the reference's o3_gicp, no ICP after it).
+        sources / targets: lists of [n, 3] arrays.  constrained=True: rotation about z only; False: full 3-D rotation.
+        streams: one non-negative id per pair selecting its random draws under `seed` (default 0 .. B - 1); a pair's result
+        depends on (seed, stream, clouds, arguments) only.  Returns dict(transforms, fitness, rmse, iterations, validations)."""
+        B = len(sources)
+        off = np.zeros((B + 1, 2), np.int64)
+        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
+        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
+        p1, p2 = cat(sources), cat(targets)
+        st, tail, result = self._global_bufs(B, streams, np.arange(B))
+        self._check(self._lib.alignnet_global_register(self._h, _fp(p1), _fp(p2), off.ctypes.data_as(C.POINTER(C.c_int64)), B,
+                                                       0 if constrained else ICP_FULL_ROTATION, int(seed), st.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                       int(max_iteration), int(max_validation), *tail))
+        return result()
+
+    def global_register_rows(self, rows, constrained=True, seed=0, streams=None, max_iteration=4000000, max_validation=500):
+        """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows; streams default to the rows."""
+        r, rp = self._rows(rows)
+        st, tail, result = self._global_bufs(r.size, streams, r)
+        self._check(self._lib.alignnet_global_register_dataset(self._h, rp, r.size, 0 if constrained else ICP_FULL_ROTATION, int(seed),
+                                                               st.ctypes.data_as(C.POINTER(C.c_int32)), int(max_iteration), int(max_validation), *tail))
+        return result()
+
+    def debug_global_stages(self, source, target, constrained=True, seed=0, stream=0, max_iteration=4000000, max_validation=500):
+        """Test hook: global_register of one pair, with the stage outputs.  Returns the result dict (scalars, transform [4, 4]) plus
+        per cloud (index 0 = source, 1 = target) lists points / voxels / voxel_points / normals / spfh / fpfh, `matches` (target index
+        of every downsampled source point) and `winning_iteration` (-1: no hypothesis was validated)."""
+        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+        cap = max(len(p1), len(p2), 1)
+        counts = np.zeros(2, np.int32)
+        pts, vox, npt = np.zeros((2, cap, 3), np.float64), np.zeros((2, cap, 3), np.int32), np.zeros((2, cap), np.int32)
+        nrm, spfh, fpfh = np.zeros((2, cap, 3), np.float64), np.zeros((2, cap, 33), np.float64), np.zeros((2, cap, 33), np.float64)
+        match, win = np.zeros(cap, np.int32), np.zeros(1, np.int64)
+        st, tail, result = self._global_bufs(1, [stream], None)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.alignnet_debug_global_stages(self._h, _fp(p1), len(p1), _fp(p2), len(p2), 0 if constrained else ICP_FULL_ROTATION, int(seed),
+                                                           int(stream), int(max_iteration), int(max_validation), cap, ip(counts), dp(pts), ip(vox), ip(npt),
+                                                           dp(nrm), dp(spfh), dp(fpfh), ip(match), win.ctypes.data_as(C.POINTER(C.c_int64)), *tail))
+        res = result()
+        out = dict(transform=res["transforms"][0], fitness=float(res["fitness"][0]), rmse=float(res["rmse"][0]), iterations=int(res["iterations"][0]),
+                   validations=int(res["validations"][0]), winning_iteration=int(win[0]), counts=counts.copy(), matches=match[: counts[0]].copy())
+        for name, arr in (("points", pts), ("voxels", vox), ("voxel_points", npt), ("normals", nrm), ("spfh", spfh), ("fpfh", fpfh)):
+            out[name] = [arr[k, : counts[k]].copy() for k in range(2)]
+        return out
+
     @staticmethod
     def read_device(ptr, count, dtype=np.float32):
         """Debug / test helper: copy `count` elements from a device pointer (synchronous hipMemcpy)."""

@@ -325,6 +325,37 @@ int alignnet_icp_register(alignnet_handle* h, const float* points1, const float*
 int alignnet_icp_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
                                   int32_t its, int32_t flags, double* out, double* fitness, double* rmse, int32_t* iterations);
 
+/* ---- global registration: RANSAC on FPFH feature matches (the `o3_gicp` baseline, icp.py:85-143) --------------
+ * Per pair: voxel downsample (0.05 m) of both clouds, normals (radius 0.10, 30 nearest), FPFH (radius 0.25, 100
+ * nearest), nearest-feature matches, then RANSAC (4 correspondences, edge-length 0.9 and distance checks, threshold
+ * 0.075, validated hypotheses scored by fitness then inlier rmse); no ICP follows.  Open3D is not available: the
+ * computation is DEFINED by tests/global_reg_ref.py (unpinned; the downsample's output order and the random
+ * generator are this project's own).  Clouds and offsets as in alignnet_icp_register; `flags` bit 0 =
+ * ALIGNNET_ICP_FULL_ROTATION (Umeyama estimate), clear = rotation about z only.  `seed` and the per-pair `streams`
+ * ([B] ids in [0, 2^24), NULL = all zero) select the draws: a pair's result depends on (seed, stream, clouds,
+ * arguments) only, never on the batch.  max_iteration <= 2^38 and max_validation are Open3D's
+ * RANSACConvergenceCriteria (4000000, 500).  out_T: [B][16] row-major 4x4 float64 (identity when nothing was
+ * validated: an empty cloud, fewer than 4 downsampled points, no draw passing the checks); out_fitness / out_rmse /
+ * out_iterations (iterations run) / out_validations: [B] each, may be NULL.
+ * _dataset: the clouds of the uploaded dataset (alignnet_dataset_upload) addressed by example rows. */
+int alignnet_global_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
+                             int32_t flags, uint64_t seed, const int32_t* streams, int64_t max_iteration, int32_t max_validation,
+                             double* out_T, double* out_fitness, double* out_rmse, int64_t* out_iterations,
+                             int32_t* out_validations);
+int alignnet_global_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, int32_t flags, uint64_t seed,
+                                     const int32_t* streams, int64_t max_iteration, int32_t max_validation, double* out_T,
+                                     double* out_fitness, double* out_rmse, int64_t* out_iterations, int32_t* out_validations);
+/* Test hook: one pair, with the stage outputs the tests pin on.  cap >= max(n1, n2) is the row stride of the per-cloud
+ * arrays (index 0 = source, 1 = target): counts [2] downsampled sizes; points [2][cap][3]; voxels [2][cap][3] voxel
+ * indices; voxel_points [2][cap] points per voxel; normals [2][cap][3]; spfh, fpfh [2][cap][33]; matches [cap] target
+ * index of every downsampled source point; winning_iteration [1] (-1: none). */
+int alignnet_debug_global_stages(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2,
+                                 int32_t flags, uint64_t seed, int32_t stream, int64_t max_iteration, int32_t max_validation,
+                                 int64_t cap, int32_t* counts, double* points, int32_t* voxels, int32_t* voxel_points,
+                                 double* normals, double* spfh, double* fpfh, int32_t* matches, int64_t* winning_iteration,
+                                 double* out_T, double* out_fitness, double* out_rmse, int64_t* out_iterations,
+                                 int32_t* out_validations);
+
 /* ---- run-time options with no counterpart in the reference's config surface --------
  * "train_matmul_bf16" (0/1, default 0): training only -- the two MFMA convs of every backbone (the hidden 1x1 conv
  *   and the -> C3 feature lift, 96 % of the step's FLOPs, models/tp8.py:55-57), in the forward and in the backward's
