@@ -120,6 +120,17 @@ SYMBOLS = {
                                                C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "alignnet_fgr_register": (C.c_int, [H, FP, FP, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.c_double, C.c_double,
+                                        C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "alignnet_fgr_register_dataset": (C.c_int, [H, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.c_double, C.c_double,
+                                                C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "alignnet_debug_fgr_stages": (C.c_int, [H, FP, C.c_int64, FP, C.c_int64, C.c_int32, C.c_uint64, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double,
+                                            C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "alignnet_set_option": (C.c_int, [H, C.c_char_p, C.c_int64]),
     "alignnet_get_option": (C.c_int, [H, C.c_char_p, C.POINTER(C.c_int64)]),
     "alignnet_profile_read_kernel": (C.c_int, [H, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -32,6 +32,7 @@ KERNEL_IDS = {"pointnet_fused": 1, "pointnet_fused<64,128>": 2, "pointnet_fused<
               "dgcnn_split": 12, "dgcnn_split<64,128>": 13}
 KERNEL_NAMES = {v: k for k, v in KERNEL_IDS.items()}
 ICP_FULL_ROTATION = 1   # include/alignnet_hip.h ALIGNNET_ICP_FULL_ROTATION: flags bit of alignnet_icp_register*
+FGR_DECREASE_MU = 2     # include/alignnet_hip.h ALIGNNET_FGR_DECREASE_MU: flags bit of alignnet_fgr_register*
 
 
 class EngineError(RuntimeError):
@@ -446,6 +447,85 @@ class Engine:
         out = dict(transform=res["transforms"][0], fitness=float(res["fitness"][0]), rmse=float(res["rmse"][0]), iterations=int(res["iterations"][0]),
                    validations=int(res["validations"][0]), winning_iteration=int(win[0]), counts=counts.copy(), matches=match[: counts[0]].copy())
         for name, arr in (("points", pts), ("voxels", vox), ("voxel_points", npt), ("normals", nrm), ("spfh", spfh), ("fpfh", fpfh)):
+            out[name] = [arr[k, : counts[k]].copy() for k in range(2)]
+        return out
+
+    # ---- fast global registration on FPFH feature matches (csrc/alignnet_globalreg.hip, the fgr_* kernels) ----
+    @staticmethod
+    def _fgr_bufs(B, streams, default_streams, constrained, decrease_mu, division_factor, maximum_correspondence_distance, iteration_number,
+                  tuple_scale, maximum_tuple_count):
+        st = np.ascontiguousarray(default_streams if streams is None else streams, np.int32).ravel()
+        if st.size != B:
+            raise ValueError("streams: one id per pair (%d given for %d pairs)" % (st.size, B))
+        out = np.empty((B, 16), np.float64)
+        fit, rmse = np.empty(B, np.float64), np.empty(B, np.float64)
+        corr, trials = np.empty(B, np.int32), np.empty(B, np.int64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        flags = (0 if constrained else ICP_FULL_ROTATION) | (FGR_DECREASE_MU if decrease_mu else 0)
+        options = (float(division_factor), float(maximum_correspondence_distance), int(iteration_number), float(tuple_scale), int(maximum_tuple_count))
+        tail = (dp(out), dp(fit), dp(rmse), corr.ctypes.data_as(C.POINTER(C.c_int32)), trials.ctypes.data_as(C.POINTER(C.c_int64)))
+        return st, flags, options, tail, lambda: dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, correspondences=corr, trials=trials)
+
+    def fgr_register(self, sources, targets, constrained=True, decrease_mu=False, seed=0, streams=None, division_factor=1.4,
+                     maximum_correspondence_distance=0.025, iteration_number=64, tuple_scale=0.95, maximum_tuple_count=1000):
+        """Fast global registration on FPFH feature matches of the 5 cm voxel-downsampled clouds (the reference's o3_gicp_fast, no ICP
+        after it; defined by tests/fgr_ref.py).  sources / targets: lists of [n, 3] arrays.  constrained=True: rotation about z only; False:
+        full 3-D rotation.  decrease_mu: Open3D's FastGlobalRegistrationOption.decrease_mu.  streams: one non-negative id per pair selecting
+        its tuple draws under `seed` (default 0 .. B - 1); a pair's result depends on (seed, stream, clouds, arguments) only.
+        Returns dict(transforms, fitness, rmse, correspondences, trials)."""
+        B = len(sources)
+        off = np.zeros((B + 1, 2), np.int64)
+        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
+        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
+        p1, p2 = cat(sources), cat(targets)
+        st, flags, options, tail, result = self._fgr_bufs(B, streams, np.arange(B), constrained, decrease_mu, division_factor,
+                                                          maximum_correspondence_distance, iteration_number, tuple_scale, maximum_tuple_count)
+        self._check(self._lib.alignnet_fgr_register(self._h, _fp(p1), _fp(p2), off.ctypes.data_as(C.POINTER(C.c_int64)), B, flags, int(seed),
+                                                    st.ctypes.data_as(C.POINTER(C.c_int32)), *options, *tail))
+        return result()
+
+    def fgr_register_rows(self, rows, constrained=True, decrease_mu=False, seed=0, streams=None, division_factor=1.4,
+                          maximum_correspondence_distance=0.025, iteration_number=64, tuple_scale=0.95, maximum_tuple_count=1000):
+        """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows; streams default to the rows."""
+        r, rp = self._rows(rows)
+        st, flags, options, tail, result = self._fgr_bufs(r.size, streams, r, constrained, decrease_mu, division_factor,
+                                                          maximum_correspondence_distance, iteration_number, tuple_scale, maximum_tuple_count)
+        self._check(self._lib.alignnet_fgr_register_dataset(self._h, rp, r.size, flags, int(seed), st.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                            *options, *tail))
+        return result()
+
+    def debug_fgr_stages(self, source, target, constrained=True, decrease_mu=False, seed=0, stream=0, division_factor=1.4,
+                         maximum_correspondence_distance=0.025, iteration_number=64, tuple_scale=0.95, maximum_tuple_count=1000):
+        """Test hook: fgr_register of one pair, with the stage outputs.  Returns the result dict (scalars, transform [4, 4]) plus per cloud
+        (index 0 = source, 1 = target) lists points / fpfh, `matches` (target index of every downsampled source point), `reverse_matches`
+        (source index of every downsampled target point), `cross` (source indices of the mutual matches, ascending), `tuple_source` /
+        `tuple_target` (the correspondences the tuple test kept, 3 per accepted trial, in trial order), `tuple_trials` (the trial of every
+        accepted tuple), `means` [2, 3], `scale`, and `trace` [iteration_number, 4, 4]: the transform after every iteration, in the normalised
+        frame, moving the target onto the source."""
+        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+        cap = max(len(p1), len(p2), 1)
+        mtc, its = max(int(maximum_tuple_count), 0), max(int(iteration_number), 0)
+        counts = np.zeros(4, np.int32)
+        pts, fpfh = np.zeros((2, cap, 3), np.float64), np.zeros((2, cap, 33), np.float64)
+        match, rmatch, cross = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        ts, tt, ttr = np.zeros(3 * mtc + 1, np.int32), np.zeros(3 * mtc + 1, np.int32), np.zeros(mtc + 1, np.int64)
+        norm, trace = np.zeros(7, np.float64), np.zeros((its + 1, 16), np.float64)
+        st, flags, options, tail, result = self._fgr_bufs(1, [stream], None, constrained, decrease_mu, division_factor,
+                                                          maximum_correspondence_distance, iteration_number, tuple_scale, maximum_tuple_count)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.alignnet_debug_fgr_stages(self._h, _fp(p1), len(p1), _fp(p2), len(p2), flags, int(seed), int(stream), *options, cap,
+                                                        ip(counts), dp(pts), dp(fpfh), ip(match), ip(rmatch), ip(cross), ip(ts), ip(tt),
+                                                        ttr.ctypes.data_as(C.POINTER(C.c_int64)), dp(norm), dp(trace), *tail))
+        res = result()
+        na = int(counts[3])
+        out = dict(transform=res["transforms"][0], fitness=float(res["fitness"][0]), rmse=float(res["rmse"][0]),
+                   correspondences=int(res["correspondences"][0]), trials=int(res["trials"][0]), counts=counts[:2].copy(),
+                   matches=match[: counts[0]].copy() if counts[1] else match[:0].copy(),
+                   reverse_matches=rmatch[: counts[1]].copy() if counts[0] else rmatch[:0].copy(), cross=cross[: counts[2]].copy(),
+                   tuple_source=ts[: 3 * na].copy(), tuple_target=tt[: 3 * na].copy(), tuple_trials=ttr[:na].copy(),
+                   means=norm[:6].reshape(2, 3).copy(), scale=float(norm[6]), trace=trace[:its].reshape(its, 4, 4).copy())
+        for name, arr in (("points", pts), ("fpfh", fpfh)):
             out[name] = [arr[k, : counts[k]].copy() for k in range(2)]
         return out
 

@@ -21,6 +21,8 @@
 //                         validated in iteration order by the whole workgroup against the grid (LDS-resident when it fits, else from HBM)
 //                         until max_validation have been -- so "the first max_validation that pass, in iteration order" is what is
 //                         validated, whatever the launch shape.
+// Fast global registration (FGR, the reference's `o3_gicp_fast`, icp.py:121-143; DEFINED by tests/fgr_ref.py) shares stages 1-5 and the grid:
+// section 8 below (gr_match_kernel<true>, fgr_tuple_kernel, fgr_optimise_kernel, fgr_score_kernel) and alignnet_fgr_register*.
 #include "engine.h"
 #include "icp_estimate.h"
 #include <cmath>
@@ -62,6 +64,7 @@ struct GrArgs {
   double* spfh; double* fpfh;
   // per pair
   int* match; int* cell; int* cellfill; double* gpts; double* gpar; int* gdim;
+  int* rmatch;                  // FGR only: [pairs][cap] nearest source feature of every target feature
   int* err;
   // RANSAC
   unsigned long long seed; long long max_iteration; int max_validation;
@@ -447,14 +450,16 @@ __global__ __launch_bounds__(kThreads) void gr_fpfh_kernel(const GrArgs a)
 }
 
 // ---- 5. feature matches: for every source feature the nearest target feature (lowest index wins a tie) --------------------------------
+// kReverse (FGR): the roles swapped -- for every target feature the nearest source feature, into a.rmatch
+template <bool kReverse>
 __global__ __launch_bounds__(kThreads) void gr_match_kernel(const GrArgs a)
 {
   __shared__ double tile[kMatchTile][kBins];
   const int bl = blockIdx.x, tid = threadIdx.x;
-  const int ms = a.m[2 * bl], mt = a.m[2 * bl + 1];
-  const double* fs = a.fpfh + (size_t)(2 * bl) * a.cap * kBins;
-  const double* ft = a.fpfh + (size_t)(2 * bl + 1) * a.cap * kBins;
-  int* match = a.match + (size_t)bl * a.cap;
+  const int ms = a.m[2 * bl + (kReverse ? 1 : 0)], mt = a.m[2 * bl + (kReverse ? 0 : 1)];
+  const double* fs = a.fpfh + (size_t)(2 * bl + (kReverse ? 1 : 0)) * a.cap * kBins;
+  const double* ft = a.fpfh + (size_t)(2 * bl + (kReverse ? 0 : 1)) * a.cap * kBins;
+  int* match = (kReverse ? a.rmatch : a.match) + (size_t)bl * a.cap;
   for (int i0 = 0; i0 < ms; i0 += kThreads) {
     const int i = i0 + tid;
     const bool active = i < ms;
@@ -760,6 +765,391 @@ __global__ __launch_bounds__(kThreads) void gr_ransac_kernel(const GrArgs a, con
   }
 }
 
+// ---- 8. fast global registration (FGR, the reference's `o3_gicp_fast`; DEFINED by tests/fgr_ref.py) --------------------------------------
+// On top of stages 1-5: the reverse matches (gr_match_kernel<true>), then per pair
+//   fgr_tuple_kernel      one workgroup: the clouds' means and the normalising scale, the normalised points, the cross check (mutual matches
+//                         compacted in ascending source index by block scans), then rounds of one tuple trial per lane; the lanes that pass
+//                         are taken in trial order by ballot until max_tuples have been or ncorr * 100 trials are drawn
+//   fgr_optimise_kernel   one workgroup: all Gauss-Newton iterations in one launch.  Per iteration each lane accumulates its correspondences'
+//                         contributions to the 16 (full) / 8 (z-constrained) distinct sums of J^T J and J^T r, reduced in a fixed order
+//                         (wave butterfly, then the waves in index order); every lane then solves the 6x6 / 4x4 system itself (Cholesky, fp64):
+//                         the same instruction stream on the same sums, so no broadcast and one barrier per iteration.  The correspondences'
+//                         points are gathered once into LDS (structure of arrays) when 3 max_tuples of them fit (up to 1024 tuples: Open3D's
+//                         1000 does), else read through the index lists from HBM every iteration: the same arithmetic either way
+//   gr_grid_kernel + fgr_score_kernel   fitness and inlier rmse of the result, threshold maximum_correspondence_distance
+constexpr int kOptThreads = 512, kOptWaves = kOptThreads / 64;
+constexpr int kOptLdsCorr = 3072;          // correspondences whose points fgr_optimise_kernel<., true> holds in LDS (48 bytes each)
+constexpr int kFgrMinCorr = 10;
+constexpr double kFgrPivotEps = 1e-12;
+
+struct FgrArgs {
+  double* npts;                 // [2 pairs][cap][3] normalised points
+  double* norm;                 // [pairs][8]: mean of the source (3), of the target (3), scale
+  int* cross; int* counts;      // [pairs][cap] cross-checked source indices; [pairs][2] their number, accepted tuples
+  int* ci; int* cj;             // [pairs][3 max_tuples] tuple correspondences (source, target index)
+  long long* ctrial;            // [pairs][max_tuples] trial index of every accepted tuple
+  long long* trials;            // [pairs] trials drawn
+  double* trace;                // [pairs][iterations][16] transform after every iteration (normalised frame), or null
+  unsigned long long seed;
+  double division_factor, max_corr_dist, tuple_scale;
+  int iterations, max_tuples, decrease_mu;
+};
+
+__global__ __launch_bounds__(kThreads) void fgr_tuple_kernel(const GrArgs a, const FgrArgs f)
+{
+  __shared__ double red[kWaves][3];
+  __shared__ double mean[2][3];
+  __shared__ double s_scale;
+  __shared__ int sh[kWaves + 1];
+  __shared__ unsigned long long wmask[kWaves];
+  __shared__ long long s_trials;
+  const int bl = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int ms = a.m[2 * bl], mt = a.m[2 * bl + 1];
+  double* norm = f.norm + (size_t)bl * 8;
+  int* counts = f.counts + (size_t)bl * 2;
+  if (ms == 0 || mt == 0) {   // an empty cloud: nothing to normalise or to match
+    if (tid < 8) norm[tid] = 0.0;
+    if (tid == 0) { counts[0] = 0; counts[1] = 0; f.trials[bl] = 0; }
+    return;
+  }
+  // ---- means, scale, normalised points ----
+  double d2max = 0.0;
+  for (int side = 0; side < 2; ++side) {
+    const int m = side ? mt : ms;
+    const double* dp = a.dpts + (size_t)(2 * bl + side) * a.cap * 3;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int i = tid; i < m; i += kThreads)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) s[k] += dp[(size_t)i * 3 + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o);
+      if (lane == 0) red[w][k] = s[k];
+    }
+    __syncthreads();
+    if (tid < 3) { double t = 0.0; for (int q = 0; q < kWaves; ++q) t += red[q][tid]; mean[side][tid] = t / (double)m; }
+    __syncthreads();
+    for (int i = tid; i < m; i += kThreads) {
+      const double x = dp[(size_t)i * 3] - mean[side][0], y = dp[(size_t)i * 3 + 1] - mean[side][1], z = dp[(size_t)i * 3 + 2] - mean[side][2];
+      d2max = fmax(d2max, x * x + y * y + z * z);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) d2max = fmax(d2max, __shfl_xor(d2max, o));
+  if (lane == 0) red[w][0] = d2max;
+  __syncthreads();
+  if (tid == 0) { double t = 0.0; for (int q = 0; q < kWaves; ++q) t = fmax(t, red[q][0]); s_scale = sqrt(t); }
+  __syncthreads();
+  const double scale = s_scale;
+  if (tid < 6) norm[tid] = mean[tid / 3][tid % 3];
+  if (tid == 6) norm[6] = scale;
+  if (tid == 7) norm[7] = 0.0;
+  for (int side = 0; side < 2; ++side) {
+    const int m = side ? mt : ms;
+    const double* dp = a.dpts + (size_t)(2 * bl + side) * a.cap * 3;
+    double* np = f.npts + (size_t)(2 * bl + side) * a.cap * 3;
+    for (size_t q = tid; q < (size_t)m * 3; q += kThreads) np[q] = (dp[q] - mean[side][q % 3]) / scale;
+  }
+  // ---- cross check: the source indices whose match points back, ascending ----
+  const int* match = a.match + (size_t)bl * a.cap;
+  const int* rmatch = a.rmatch + (size_t)bl * a.cap;
+  int* cross = f.cross + (size_t)bl * a.cap;
+  int ncorr = 0;
+  for (int i0 = 0; i0 < ms; i0 += kThreads) {
+    const int i = i0 + tid;
+    const int keep = (i < ms && rmatch[match[i]] == i) ? 1 : 0;
+    int total;
+    const int pos = gr_block_scan(keep, sh, &total);
+    if (keep) cross[ncorr + pos] = i;
+    ncorr += total;
+  }
+  if (tid == 0) { counts[0] = ncorr; s_trials = f.max_tuples > 0 ? (long long)ncorr * 100 : 0; }
+  __syncthreads();   // the list and the normalised points are read back below
+  // ---- tuple test ----
+  const double* sp = f.npts + (size_t)(2 * bl) * a.cap * 3;
+  const double* tp = f.npts + (size_t)(2 * bl + 1) * a.cap * 3;
+  int* ci = f.ci + (size_t)bl * 3 * f.max_tuples;
+  int* cj = f.cj + (size_t)bl * 3 * f.max_tuples;
+  long long* ctrial = f.ctrial + (size_t)bl * f.max_tuples;
+  const unsigned long long stream = a.streams ? (unsigned long long)a.streams[bl] : 0ull;
+  const long long total = f.max_tuples > 0 ? (long long)ncorr * 100 : 0;
+  const double ts = f.tuple_scale;
+  int accepted = 0;
+  for (long long t0 = 0; t0 < total && accepted < f.max_tuples; t0 += kThreads) {
+    const long long t = t0 + tid;
+    bool pass = false;
+    int ii[3] = {0, 0, 0}, jj[3] = {0, 0, 0};
+    if (t < total) {
+      double p[3][3], q[3][3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        ii[k] = cross[gr_draw(f.seed, stream, (unsigned long long)t, k, ncorr)];
+        jj[k] = match[ii[k]];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { p[k][c] = sp[(size_t)ii[k] * 3 + c]; q[k][c] = tp[(size_t)jj[k] * 3 + c]; }
+      }
+      pass = true;
+#pragma unroll
+      for (int e = 0; e < 3; ++e) {
+        const int u = e, v = e == 2 ? 0 : e + 1;
+        const double ax = p[v][0] - p[u][0], ay = p[v][1] - p[u][1], az = p[v][2] - p[u][2];
+        const double bx = q[v][0] - q[u][0], by = q[v][1] - q[u][1], bz = q[v][2] - q[u][2];
+        const double li = sqrt(ax * ax + ay * ay + az * az), lj = sqrt(bx * bx + by * by + bz * bz);
+        if (!(li * ts < lj && lj < li / ts)) pass = false;
+      }
+    }
+    const unsigned long long bal = __ballot(pass);
+    if (lane == 0) wmask[w] = bal;
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int q = 0; q < kWaves; ++q) { const int c = __popcll(wmask[q]); before += q < w ? c : 0; all += c; }
+    if (pass) {   // trial order = lane order
+      const int pos = accepted + before + __popcll(bal & ((1ull << lane) - 1ull));
+      if (pos < f.max_tuples) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { ci[(size_t)pos * 3 + k] = ii[k]; cj[(size_t)pos * 3 + k] = jj[k]; }
+        ctrial[pos] = t;
+        if (pos == f.max_tuples - 1) s_trials = t + 1;
+      }
+    }
+    accepted = min(accepted + all, f.max_tuples);
+    __syncthreads();
+  }
+  if (tid == 0) { counts[1] = accepted; f.trials[bl] = s_trials; }
+}
+
+// x with A x = b for the symmetric positive definite A (lower triangle used), Cholesky in index order.  false: a pivot is not greater than
+// kFgrPivotEps times its diagonal entry.  One reciprocal per column (kept on the diagonal) instead of a division per entry: the solve is on
+// the critical path of every iteration
+template <int N>
+__device__ __forceinline__ bool fgr_cholesky_solve(double (&A)[N][N], const double (&b)[N], double (&x)[N])
+{
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    double d = A[k][k];
+#pragma unroll
+    for (int j = 0; j < k; ++j) d -= A[k][j] * A[k][j];
+    if (!(d > kFgrPivotEps * A[k][k])) { ok = false; d = 1.0; }
+    const double il = 1.0 / sqrt(d);
+    A[k][k] = il;
+#pragma unroll
+    for (int i = k + 1; i < N; ++i) {
+      double v = A[i][k];
+#pragma unroll
+      for (int j = 0; j < k; ++j) v -= A[i][j] * A[k][j];
+      A[i][k] = v * il;
+    }
+  }
+  double y[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double v = b[i];
+#pragma unroll
+    for (int j = 0; j < i; ++j) v -= A[i][j] * y[j];
+    y[i] = v * A[i][i];
+  }
+#pragma unroll
+  for (int i = N - 1; i >= 0; --i) {
+    double v = y[i];
+#pragma unroll
+    for (int j = i + 1; j < N; ++j) v -= A[j][i] * x[j];
+    x[i] = v * A[i][i];
+  }
+  return ok;
+}
+
+template <bool kFull, bool kLds>
+__global__ __launch_bounds__(kOptThreads) void fgr_optimise_kernel(const GrArgs a, const FgrArgs f)
+{
+  extern __shared__ __attribute__((aligned(16))) double lds[];   // kLds: p_x p_y p_z q0_x q0_y q0_z, [n] each
+  // the distinct sums: full  0..5 A00 A01 A02 A11 A12 A22 (rotation block), 6..8 sum s q, 9 sum s, 10..12 rotation part of J^T r, 13..15 sum s r
+  //                    z-constrained  0 A22, 1..2 sum s q_x, s q_y, 3 sum s, 4 the z-rotation entry of J^T r, 5..7 sum s r
+  constexpr int kSums = kFull ? 16 : 8;
+  __shared__ double red[2][kOptWaves][kSums];
+  const int bl = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int ms = a.m[2 * bl], mt = a.m[2 * bl + 1];
+  const int n = (ms == 0 || mt == 0) ? 0 : 3 * f.counts[(size_t)bl * 2 + 1];
+  const double* sp = f.npts + (size_t)(2 * bl) * a.cap * 3;
+  const double* tp = f.npts + (size_t)(2 * bl + 1) * a.cap * 3;
+  const int* ci = f.ci + (size_t)bl * 3 * f.max_tuples;
+  const int* cj = f.cj + (size_t)bl * 3 * f.max_tuples;
+  double T[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+  bool stopped = n < kFgrMinCorr;
+  double mu = 1.0;
+  if constexpr (kLds) {
+    for (int c = tid; c < n; c += kOptThreads) {
+      const size_t i = (size_t)ci[c] * 3, j = (size_t)cj[c] * 3;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { lds[k * n + c] = sp[i + k]; lds[(3 + k) * n + c] = tp[j + k]; }
+    }
+    __syncthreads();
+  }
+  for (int it = 0; it < f.iterations; ++it) {
+    if (!stopped) {   // uniform over the workgroup: every lane solves the same system
+      double acc[kSums];
+#pragma unroll
+      for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
+      for (int c = tid; c < n; c += kOptThreads) {
+        double px, py, pz, q0x, q0y, q0z;
+        if constexpr (kLds) {
+          px = lds[c]; py = lds[n + c]; pz = lds[2 * n + c]; q0x = lds[3 * n + c]; q0y = lds[4 * n + c]; q0z = lds[5 * n + c];
+        } else {
+          const size_t i = (size_t)ci[c] * 3, j = (size_t)cj[c] * 3;
+          px = sp[i]; py = sp[i + 1]; pz = sp[i + 2]; q0x = tp[j]; q0y = tp[j + 1]; q0z = tp[j + 2];
+        }
+        const double qx = T[0] * q0x + T[1] * q0y + T[2] * q0z + T[3];
+        const double qy = T[4] * q0x + T[5] * q0y + T[6] * q0z + T[7];
+        const double qz = T[8] * q0x + T[9] * q0y + T[10] * q0z + T[11];
+        const double rx = px - qx, ry = py - qy, rz = pz - qz;
+        const double tmp = mu / (rx * rx + ry * ry + rz * rz + mu);
+        const double s = tmp * tmp;
+        if constexpr (kFull) {
+          acc[0] += s * (qy * qy + qz * qz); acc[1] -= s * (qx * qy); acc[2] -= s * (qx * qz);
+          acc[3] += s * (qx * qx + qz * qz); acc[4] -= s * (qy * qz); acc[5] += s * (qx * qx + qy * qy);
+          acc[6] += s * qx; acc[7] += s * qy; acc[8] += s * qz; acc[9] += s;
+          acc[10] += s * (qz * ry - qy * rz); acc[11] += s * (qx * rz - qz * rx); acc[12] += s * (qy * rx - qx * ry);
+          acc[13] += s * rx; acc[14] += s * ry; acc[15] += s * rz;
+        } else {
+          acc[0] += s * (qx * qx + qy * qy); acc[1] += s * qx; acc[2] += s * qy; acc[3] += s;
+          acc[4] += s * (qy * rx - qx * ry); acc[5] += s * rx; acc[6] += s * ry; acc[7] += s * rz;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kSums; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+        if (lane == 0) red[it & 1][w][k] = acc[k];
+      }
+      __syncthreads();   // one barrier per iteration: the buffer written two iterations on is only reached through the next one
+      double S[kSums];
+#pragma unroll
+      for (int k = 0; k < kSums; ++k) {
+        double t = 0.0;
+#pragma unroll
+        for (int q = 0; q < kOptWaves; ++q) t += red[it & 1][q][k];
+        S[k] = t;
+      }
+      double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      bool ok;
+      if constexpr (kFull) {
+        // J rows [0, -qz, qy, -1, 0, 0], [qz, 0, -qx, 0, -1, 0], [-qy, qx, 0, 0, 0, -1]
+        double A[6][6] = {{S[0], 0.0, 0.0, 0.0, 0.0, 0.0}, {S[1], S[3], 0.0, 0.0, 0.0, 0.0}, {S[2], S[4], S[5], 0.0, 0.0, 0.0},
+                          {0.0, S[8], -S[7], S[9], 0.0, 0.0}, {-S[8], 0.0, S[6], 0.0, S[9], 0.0}, {S[7], -S[6], 0.0, 0.0, 0.0, S[9]}};
+        const double b[6] = {-S[10], -S[11], -S[12], S[13], S[14], S[15]};   // -J^T r
+        ok = fgr_cholesky_solve<6>(A, b, x);
+      } else {
+        double A[4][4] = {{S[0], 0.0, 0.0, 0.0}, {-S[2], S[3], 0.0, 0.0}, {S[1], 0.0, S[3], 0.0}, {0.0, 0.0, 0.0, S[3]}};
+        const double b[4] = {-S[4], S[5], S[6], S[7]};
+        double y[4];
+        ok = fgr_cholesky_solve<4>(A, b, y);
+        x[2] = y[0]; x[3] = y[1]; x[4] = y[2]; x[5] = y[3];
+      }
+      if (!ok) stopped = true;
+      else {   // T <- Delta T, Delta = R_z(x2) R_y(x1) R_x(x0), t = x3..5
+        double D[9];
+        const double cz = cos(x[2]), sz = sin(x[2]);
+        if constexpr (kFull) {
+          const double cx = cos(x[0]), sx = sin(x[0]), cy = cos(x[1]), sy = sin(x[1]);
+          D[0] = cz * cy; D[1] = cz * sy * sx - sz * cx; D[2] = cz * sy * cx + sz * sx;
+          D[3] = sz * cy; D[4] = sz * sy * sx + cz * cx; D[5] = sz * sy * cx - cz * sx;
+          D[6] = -sy; D[7] = cy * sx; D[8] = cy * cx;
+        } else {
+          D[0] = cz; D[1] = -sz; D[2] = 0.0; D[3] = sz; D[4] = cz; D[5] = 0.0; D[6] = 0.0; D[7] = 0.0; D[8] = 1.0;
+        }
+        double Tn[12];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) Tn[r * 4 + c] = D[r * 3] * T[c] + D[r * 3 + 1] * T[4 + c] + D[r * 3 + 2] * T[8 + c];
+          Tn[r * 4 + 3] += x[3 + r];
+        }
+#pragma unroll
+        for (int q = 0; q < 12; ++q) T[q] = Tn[q];
+      }
+    }
+    if (f.trace && tid == 0) {
+      double* tr = f.trace + ((size_t)bl * f.iterations + it) * 16;
+      for (int q = 0; q < 12; ++q) tr[q] = T[q];
+      tr[12] = 0.0; tr[13] = 0.0; tr[14] = 0.0; tr[15] = 1.0;
+    }
+    if (f.decrease_mu && (it & 3) == 0 && mu > f.max_corr_dist) mu /= f.division_factor;
+  }
+  if (tid == 0) {   // back to the original frame, inverted: the result maps the source onto the target
+    double* out = a.out_T + (size_t)bl * 16;
+    double R[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    if (ms != 0 && mt != 0) {
+      const double* norm = f.norm + (size_t)bl * 8;
+      const double scale = norm[6];
+      double u[3];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) u[r] = norm[r] + scale * T[r * 4 + 3] - (T[r * 4] * norm[3] + T[r * 4 + 1] * norm[4] + T[r * 4 + 2] * norm[5]);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        R[r * 4] = T[r]; R[r * 4 + 1] = T[4 + r]; R[r * 4 + 2] = T[8 + r];
+        R[r * 4 + 3] = -(T[r] * u[0] + T[4 + r] * u[1] + T[8 + r] * u[2]);
+      }
+    }
+    for (int q = 0; q < 12; ++q) out[q] = R[q];
+    out[12] = 0.0; out[13] = 0.0; out[14] = 0.0; out[15] = 1.0;
+  }
+}
+
+// fitness and inlier rmse of a.out_T on the downsampled clouds against the grid of gr_grid_kernel (threshold tau), as the RANSAC validation
+__global__ __launch_bounds__(kThreads) void fgr_score_kernel(const GrArgs a, const double tau)
+{
+  __shared__ double red[kWaves * 2];
+  const int bl = blockIdx.x, tid = threadIdx.x;
+  const int ms = a.m[2 * bl];
+  const double* sp = a.dpts + (size_t)(2 * bl) * a.cap * 3;
+  const int* gdim = a.gdim + (size_t)bl * 4;
+  const int nx = gdim[0], ny = gdim[1], nz = gdim[2];
+  const double mnx = a.gpar[(size_t)bl * 4], mny = a.gpar[(size_t)bl * 4 + 1], mnz = a.gpar[(size_t)bl * 4 + 2], cs = a.gpar[(size_t)bl * 4 + 3];
+  const double* gx = a.gpts + (size_t)bl * a.cap * 3; const double* gy = gx + a.cap; const double* gz = gy + a.cap;
+  const int* cell = a.cell + (size_t)bl * (kMaxCells + 1);
+  const double tau2 = tau * tau;
+  double Tl[12];
+#pragma unroll
+  for (int q = 0; q < 12; ++q) Tl[q] = a.out_T[(size_t)bl * 16 + q];
+  double v[2] = {0.0, 0.0};
+  for (int i = tid; i < ms; i += kThreads) {
+    const double sx = sp[(size_t)i * 3], sy = sp[(size_t)i * 3 + 1], sz = sp[(size_t)i * 3 + 2];
+    const double qx = Tl[0] * sx + Tl[1] * sy + Tl[2] * sz + Tl[3];
+    const double qy = Tl[4] * sx + Tl[5] * sy + Tl[6] * sz + Tl[7];
+    const double qz = Tl[8] * sx + Tl[9] * sy + Tl[10] * sz + Tl[11];
+    const double fx = floor((qx - mnx) / cs), fy = floor((qy - mny) / cs), fz = floor((qz - mnz) / cs);
+    if (!(fx >= -1.0 && fx <= (double)nx && fy >= -1.0 && fy <= (double)ny && fz >= -1.0 && fz <= (double)nz)) continue;
+    const int x0 = max(0, (int)fx - 1), x1 = min(nx - 1, (int)fx + 1);
+    const int y0 = max(0, (int)fy - 1), y1 = min(ny - 1, (int)fy + 1);
+    const int z0 = max(0, (int)fz - 1), z1 = min(nz - 1, (int)fz + 1);
+    if (x0 > x1) continue;
+    double best = INFINITY;
+    for (int z = z0; z <= z1; ++z)
+      for (int y = y0; y <= y1; ++y) {
+        const int rowc = (z * ny + y) * nx;
+        const int b = cell[rowc + x0], e = cell[rowc + x1 + 1];
+        for (int j = b; j < e; ++j) {
+          const double dx = qx - gx[j], dy = qy - gy[j], dz = qz - gz[j];
+          best = fmin(best, dx * dx + dy * dy + dz * dz);
+        }
+      }
+    if (best <= tau2) { v[0] += 1.0; v[1] += best; }
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+  if ((tid & 63) == 0) { red[(tid >> 6) * 2] = v[0]; red[(tid >> 6) * 2 + 1] = v[1]; }
+  __syncthreads();
+  if (tid == 0) {
+    double cnt = 0.0, sum = 0.0;
+    for (int q = 0; q < kWaves; ++q) { cnt += red[q * 2]; sum += red[q * 2 + 1]; }
+    a.out_fit[bl] = ms > 0 ? cnt / (double)ms : 0.0;
+    a.out_rmse[bl] = cnt > 0.0 ? sqrt(sum / cnt) : 0.0;
+  }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -793,6 +1183,19 @@ struct GrDebugOut {   // alignnet_debug_global_stages: host arrays for the stage
 };
 
 constexpr size_t kWsBudget = (size_t)3 << 29;   // 1.5 GiB of stage arrays per chunk
+
+// stages 1-5 of a chunk of bc pairs: downsample, normals, SPFH / FPFH, the matches source -> target
+void launch_front_end(alignnet_handle* h, const GrArgs& a, int bc)
+{
+  const int parts = bc >= 128 ? 1 : (bc >= 32 ? 4 : 16);   // workgroups per cloud of the per-point stages at small batches
+  hipLaunchKernelGGL(gr_voxel_kernel, dim3(2 * bc), dim3(kThreads), 0, h->stream, a);
+  hipLaunchKernelGGL(gr_neighbours_kernel<30>, dim3(2 * bc), dim3(kThreads), 0, h->stream, a, 2.0 * kVoxel, 3);
+  hipLaunchKernelGGL(gr_normals_kernel, dim3(2 * bc, parts), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(gr_neighbours_kernel<100>, dim3(2 * bc), dim3(kThreads), 0, h->stream, a, 5.0 * kVoxel, 6);
+  hipLaunchKernelGGL(gr_spfh_kernel, dim3(2 * bc, parts), dim3(kThreads), 0, h->stream, a);
+  hipLaunchKernelGGL(gr_fpfh_kernel, dim3(2 * bc, parts), dim3(kThreads), 0, h->stream, a);
+  hipLaunchKernelGGL(gr_match_kernel<false>, dim3(bc), dim3(kThreads), 0, h->stream, a);
+}
 
 // shared driver: blobs and offsets already on the device; n1 / n2 = the cloud sizes of the B pairs (host)
 int run_global(alignnet_handle* h, const std::string& name, const float* d_p0, const float* d_p1, const long long* d_off, const int* rows,
@@ -842,14 +1245,7 @@ int run_global(alignnet_handle* h, const std::string& name, const float* d_p0, c
     if (streams) { HIP_TRY(h, hipMemcpyAsync(d_ids + chunk, streams + s, (size_t)bc * sizeof(int), hipMemcpyHostToDevice, h->stream)); a.streams = d_ids + chunk; }
     bool hbm_path = false;
     for (int i = s; i < s + bc; ++i) hbm_path = hbm_path || n2[i] > lds_sure;
-    const int parts = bc >= 128 ? 1 : (bc >= 32 ? 4 : 16);   // workgroups per cloud of the per-point stages at small batches
-    hipLaunchKernelGGL(gr_voxel_kernel, dim3(2 * bc), dim3(kThreads), 0, h->stream, a);
-    hipLaunchKernelGGL(gr_neighbours_kernel<30>, dim3(2 * bc), dim3(kThreads), 0, h->stream, a, 2.0 * kVoxel, 3);
-    hipLaunchKernelGGL(gr_normals_kernel, dim3(2 * bc, parts), dim3(256), 0, h->stream, a);
-    hipLaunchKernelGGL(gr_neighbours_kernel<100>, dim3(2 * bc), dim3(kThreads), 0, h->stream, a, 5.0 * kVoxel, 6);
-    hipLaunchKernelGGL(gr_spfh_kernel, dim3(2 * bc, parts), dim3(kThreads), 0, h->stream, a);
-    hipLaunchKernelGGL(gr_fpfh_kernel, dim3(2 * bc, parts), dim3(kThreads), 0, h->stream, a);
-    hipLaunchKernelGGL(gr_match_kernel, dim3(bc), dim3(kThreads), 0, h->stream, a);
+    launch_front_end(h, a, bc);
     hipLaunchKernelGGL(gr_grid_kernel, dim3(bc), dim3(kThreads), 0, h->stream, a, tau);
     if (full) {
       hipLaunchKernelGGL((gr_ransac_kernel<true, true>), dim3(bc), dim3(kThreads), kLdsBytes, h->stream, a, tau);
@@ -928,6 +1324,177 @@ int global_host(alignnet_handle* h, const char* fn, const float* points1, const 
   return rc;
 }
 
+// ---- FGR host ------------------------------------------------------------------------------------------------------------------------
+struct FgrParams {
+  bool full, decrease_mu;
+  uint64_t seed; const int32_t* streams;
+  double division_factor, max_corr_dist; int32_t iterations; double tuple_scale; int32_t max_tuples;
+};
+
+struct FgrDebugOut {   // alignnet_debug_fgr_stages: host arrays for the stage outputs of pair 0 (stride `cap` per cloud)
+  long long cap;
+  int32_t* counts; double* points; double* fpfh; int32_t* matches; int32_t* rmatches; int32_t* cross; int32_t* tuple_source; int32_t* tuple_target;
+  int64_t* tuple_trials; double* normalisation; double* trace;
+};
+
+// the FGR arrays of a chunk, behind the shared stage arrays
+size_t carve_fgr(GrArgs& a, FgrArgs& f, char* base, long long pairs, long long cap, int max_tuples, int trace_iterations)
+{
+  Carve cv{base};
+  const size_t p = (size_t)pairs, c = (size_t)cap, mtc = (size_t)max_tuples;
+  a.rmatch = cv.take<int>(p * c);
+  f.npts = cv.take<double>(p * 2 * c * 3); f.norm = cv.take<double>(p * 8);
+  f.cross = cv.take<int>(p * c); f.counts = cv.take<int>(p * 2);
+  f.ci = cv.take<int>(p * 3 * mtc + 1); f.cj = cv.take<int>(p * 3 * mtc + 1); f.ctrial = cv.take<long long>(p * mtc + 1);
+  f.trials = cv.take<long long>(p);
+  f.trace = trace_iterations > 0 ? cv.take<double>(p * (size_t)trace_iterations * 16) : nullptr;
+  return cv.at;
+}
+
+int fgr_params(alignnet_handle* h, const std::string& name, int32_t flags, uint64_t seed, const int32_t* streams, double division_factor,
+               double max_corr_dist, int32_t iterations, double tuple_scale, int32_t max_tuples, FgrParams* p)
+{
+  if (flags & ~(ALIGNNET_ICP_FULL_ROTATION | ALIGNNET_FGR_DECREASE_MU))
+    return fail(h, name + ": unknown flags " + std::to_string(flags) + " (bit 0 = full rotation, bit 1 = decrease mu)");
+  if (!(division_factor >= 1.0) || !std::isfinite(division_factor)) return fail(h, name + ": division_factor must be finite and >= 1");
+  if (!(max_corr_dist > 0.0) || !std::isfinite(max_corr_dist)) return fail(h, name + ": maximum_correspondence_distance must be finite and > 0");
+  if (iterations < 0 || iterations > (1 << 20)) return fail(h, name + ": iteration_number must be in [0, 2^20]");
+  if (!(tuple_scale > 0.0 && tuple_scale <= 1.0)) return fail(h, name + ": tuple_scale must be in (0, 1]");
+  if (max_tuples < 0 || max_tuples > (1 << 20)) return fail(h, name + ": maximum_tuple_count must be in [0, 2^20]");
+  *p = FgrParams{(flags & ALIGNNET_ICP_FULL_ROTATION) != 0, (flags & ALIGNNET_FGR_DECREASE_MU) != 0, seed, streams, division_factor, max_corr_dist,
+                 iterations, tuple_scale, max_tuples};
+  return 0;
+}
+
+// shared driver, as run_global: blobs and offsets already on the device; n1 / n2 = the cloud sizes of the B pairs (host)
+int run_fgr(alignnet_handle* h, const std::string& name, const float* d_p0, const float* d_p1, const long long* d_off, const int* rows,
+            const std::vector<long long>& n1, const std::vector<long long>& n2, int B, const FgrParams& p, double* out_T, double* out_fit,
+            double* out_rmse, int32_t* out_corr, int64_t* out_trials, const FgrDebugOut* dbg)
+{
+  if (!out_T) return fail(h, name + ": null out_T");
+  if (p.streams)
+    for (int i = 0; i < B; ++i)
+      if (p.streams[i] < 0 || p.streams[i] >= (1 << 24)) return fail(h, name + ": stream id " + std::to_string(p.streams[i]) + " outside [0, 2^24)");
+  long long cap = 1;
+  for (int i = 0; i < B; ++i) {
+    if (n1[i] > 0x3fffffff || n2[i] > 0x3fffffff) return fail(h, name + ": a cloud of more than 2^30 points");
+    cap = std::max(cap, std::max(n1[i], n2[i]));
+  }
+  long long P2 = 1;
+  while (P2 < cap) P2 <<= 1;
+  const int trace_its = dbg ? p.iterations : 0;
+  GrArgs a{}; FgrArgs f{};
+  const size_t per_pair = carve(a, nullptr, 1, cap, P2) + carve_fgr(a, f, nullptr, 1, cap, p.max_tuples, trace_its);
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, kWsBudget / per_pair));
+  const size_t shared_bytes = carve(a, nullptr, chunk, cap, P2);
+  const size_t need = shared_bytes + carve_fgr(a, f, nullptr, chunk, cap, p.max_tuples, trace_its) + align_up((size_t)chunk * 8);
+  if (h->globalreg_ws_bytes < need) {
+    if (h->globalreg_ws) { HIP_TRY(h, hipStreamSynchronize(h->stream)); hipFree(h->globalreg_ws); h->globalreg_ws = nullptr; h->globalreg_ws_bytes = 0; }
+    HIP_TRY(h, hipMalloc(&h->globalreg_ws, need));
+    h->globalreg_ws_bytes = need;
+  }
+  char* ws = static_cast<char*>(h->globalreg_ws);
+  carve(a, ws, chunk, cap, P2);
+  const size_t used = shared_bytes + carve_fgr(a, f, ws + shared_bytes, chunk, cap, p.max_tuples, trace_its);
+  int* d_ids = reinterpret_cast<int*>(ws + used);   // [chunk] rows | [chunk] streams
+  a.pts[0] = d_p0; a.pts[1] = d_p1; a.off = d_off;
+  f.seed = p.seed; f.division_factor = p.division_factor; f.max_corr_dist = p.max_corr_dist; f.tuple_scale = p.tuple_scale;
+  f.iterations = p.iterations; f.max_tuples = p.max_tuples; f.decrease_mu = p.decrease_mu ? 1 : 0;
+  HIP_TRY(h, hipMemsetAsync(a.err, 0, sizeof(int), h->stream));
+  const bool opt_lds = 3 * (long long)p.max_tuples <= kOptLdsCorr;
+  const size_t opt_lds_bytes = (size_t)3 * p.max_tuples * 48;
+  static alignnet::PerDeviceOnce attr;
+  if (attr.need(h->cfg.device)) {
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(fgr_optimise_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kOptLdsCorr * 48));
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(fgr_optimise_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kOptLdsCorr * 48));
+    attr.mark(h->cfg.device);
+  }
+  std::vector<int> counts((size_t)chunk * 2);
+  for (int s = 0; s < B; s += chunk) {
+    const int bc = std::min(chunk, B - s);
+    a.pair0 = s;
+    a.rows = nullptr; a.streams = nullptr;
+    if (rows) { HIP_TRY(h, hipMemcpyAsync(d_ids, rows + s, (size_t)bc * sizeof(int), hipMemcpyHostToDevice, h->stream)); a.rows = d_ids; }
+    if (p.streams) { HIP_TRY(h, hipMemcpyAsync(d_ids + chunk, p.streams + s, (size_t)bc * sizeof(int), hipMemcpyHostToDevice, h->stream)); a.streams = d_ids + chunk; }
+    launch_front_end(h, a, bc);
+    hipLaunchKernelGGL(gr_match_kernel<true>, dim3(bc), dim3(kThreads), 0, h->stream, a);
+    hipLaunchKernelGGL(fgr_tuple_kernel, dim3(bc), dim3(kThreads), 0, h->stream, a, f);
+    if (opt_lds) {
+      if (p.full) hipLaunchKernelGGL((fgr_optimise_kernel<true, true>), dim3(bc), dim3(kOptThreads), opt_lds_bytes, h->stream, a, f);
+      else hipLaunchKernelGGL((fgr_optimise_kernel<false, true>), dim3(bc), dim3(kOptThreads), opt_lds_bytes, h->stream, a, f);
+    } else {
+      if (p.full) hipLaunchKernelGGL((fgr_optimise_kernel<true, false>), dim3(bc), dim3(kOptThreads), 0, h->stream, a, f);
+      else hipLaunchKernelGGL((fgr_optimise_kernel<false, false>), dim3(bc), dim3(kOptThreads), 0, h->stream, a, f);
+    }
+    hipLaunchKernelGGL(gr_grid_kernel, dim3(bc), dim3(kThreads), 0, h->stream, a, p.max_corr_dist);
+    hipLaunchKernelGGL(fgr_score_kernel, dim3(bc), dim3(kThreads), 0, h->stream, a, p.max_corr_dist);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out_T + (size_t)s * 16, a.out_T, (size_t)bc * 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (out_fit) HIP_TRY(h, hipMemcpyAsync(out_fit + s, a.out_fit, (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (out_rmse) HIP_TRY(h, hipMemcpyAsync(out_rmse + s, a.out_rmse, (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (out_corr) HIP_TRY(h, hipMemcpyAsync(counts.data(), f.counts, (size_t)bc * 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (out_trials) HIP_TRY(h, hipMemcpyAsync(out_trials + s, f.trials, (size_t)bc * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // the next chunk reuses the stage arrays
+    if (out_corr)
+      for (int i = 0; i < bc; ++i) out_corr[s + i] = 3 * counts[(size_t)i * 2 + 1];
+  }
+  int err = 0;
+  HIP_TRY(h, hipMemcpy(&err, a.err, sizeof(int), hipMemcpyDeviceToHost));
+  if (err) return fail(h, name + ": a coordinate is not finite, or a cloud spans more than 2^21 voxels of 0.05 m");
+  if (dbg) {   // B == 1: the stage arrays of clouds 0 (source) and 1 (target) are still in place
+    const size_t c = (size_t)cap, dc = (size_t)dbg->cap;
+    HIP_TRY(h, hipMemcpy(dbg->counts, a.m, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(dbg->counts + 2, f.counts, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    for (int side = 0; side < 2; ++side) {
+      const size_t m = (size_t)dbg->counts[side];
+      if (m > dc) return fail(h, name + ": cap smaller than a cloud");
+      if (!m) continue;
+      HIP_TRY(h, hipMemcpy(dbg->points + side * dc * 3, a.dpts + side * c * 3, m * 3 * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_TRY(h, hipMemcpy(dbg->fpfh + side * dc * kBins, a.fpfh + side * c * kBins, m * kBins * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    const size_t ms = (size_t)dbg->counts[0], mt = (size_t)dbg->counts[1], nc = (size_t)dbg->counts[2], na = (size_t)dbg->counts[3];
+    if (ms && mt) {
+      HIP_TRY(h, hipMemcpy(dbg->matches, a.match, ms * sizeof(int), hipMemcpyDeviceToHost));
+      HIP_TRY(h, hipMemcpy(dbg->rmatches, a.rmatch, mt * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    if (nc) HIP_TRY(h, hipMemcpy(dbg->cross, f.cross, nc * sizeof(int), hipMemcpyDeviceToHost));
+    if (na) {
+      HIP_TRY(h, hipMemcpy(dbg->tuple_source, f.ci, na * 3 * sizeof(int), hipMemcpyDeviceToHost));
+      HIP_TRY(h, hipMemcpy(dbg->tuple_target, f.cj, na * 3 * sizeof(int), hipMemcpyDeviceToHost));
+      HIP_TRY(h, hipMemcpy(dbg->tuple_trials, f.ctrial, na * sizeof(long long), hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(h, hipMemcpy(dbg->normalisation, f.norm, 7 * sizeof(double), hipMemcpyDeviceToHost));
+    if (p.iterations) HIP_TRY(h, hipMemcpy(dbg->trace, f.trace, (size_t)p.iterations * 16 * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+// clouds passed from the host
+int fgr_host(alignnet_handle* h, const std::string& name, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
+             const FgrParams& p, double* out_T, double* out_fit, double* out_rmse, int32_t* out_corr, int64_t* out_trials, const FgrDebugOut* dbg)
+{
+  if (!offsets || B < 1) return fail(h, name + ": null offsets or B < 1");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  std::vector<long long> n1(B), n2(B);
+  for (int i = 0; i < B; ++i) {
+    n1[i] = offsets[(i + 1) * 2] - offsets[i * 2]; n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1];
+    if (n1[i] < 0 || n2[i] < 0) return fail(h, name + ": offsets must be non-decreasing");
+  }
+  const size_t t0 = (size_t)offsets[B * 2], t1 = (size_t)offsets[B * 2 + 1];
+  if ((t0 && !points1) || (t1 && !points2)) return fail(h, name + ": null point blob");
+  float *d0 = nullptr, *d1 = nullptr; long long* doff = nullptr;
+  HIP_TRY(h, hipMalloc(&d0, std::max<size_t>(t0, 1) * 3 * sizeof(float)));
+  HIP_TRY(h, hipMalloc(&d1, std::max<size_t>(t1, 1) * 3 * sizeof(float)));
+  HIP_TRY(h, hipMalloc(&doff, (size_t)(B + 1) * 2 * sizeof(long long)));
+  if (t0) HIP_TRY(h, hipMemcpyAsync(d0, points1, t0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (t1) HIP_TRY(h, hipMemcpyAsync(d1, points2, t1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(doff, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  const int rc = run_fgr(h, name, d0, d1, doff, nullptr, n1, n2, B, p, out_T, out_fit, out_rmse, out_corr, out_trials, dbg);
+  hipStreamSynchronize(h->stream);
+  hipFree(d0); hipFree(d1); hipFree(doff);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" void alignnet_globalreg_free(alignnet_handle* h)
@@ -983,4 +1550,62 @@ extern "C" int alignnet_debug_global_stages(alignnet_handle* h, const float* poi
   const GrDebugOut dbg{cap, counts, points, voxels, voxel_points, normals, spfh, fpfh, matches, winning_iteration};
   return global_host(h, "alignnet_debug_global_stages", points1, points2, offsets, 1, flags, seed, &stream, max_iteration, max_validation, out_T,
                      out_fitness, out_rmse, out_iterations, out_validations, &dbg);
+}
+
+extern "C" int alignnet_fgr_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B, int32_t flags,
+                                     uint64_t seed, const int32_t* streams, double division_factor, double maximum_correspondence_distance,
+                                     int32_t iteration_number, double tuple_scale, int32_t maximum_tuple_count, double* out_T, double* out_fitness,
+                                     double* out_rmse, int32_t* out_correspondences, int64_t* out_trials)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_fgr_register");
+  FgrParams p;
+  if (fgr_params(h, name, flags, seed, streams, division_factor, maximum_correspondence_distance, iteration_number, tuple_scale, maximum_tuple_count, &p))
+    return 1;
+  return fgr_host(h, name, points1, points2, offsets, B, p, out_T, out_fitness, out_rmse, out_correspondences, out_trials, nullptr);
+}
+
+extern "C" int alignnet_fgr_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, int32_t flags, uint64_t seed, const int32_t* streams,
+                                             double division_factor, double maximum_correspondence_distance, int32_t iteration_number,
+                                             double tuple_scale, int32_t maximum_tuple_count, double* out_T, double* out_fitness, double* out_rmse,
+                                             int32_t* out_correspondences, int64_t* out_trials)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_fgr_register_dataset");
+  FgrParams p;
+  if (fgr_params(h, name, flags, seed, streams, division_factor, maximum_correspondence_distance, iteration_number, tuple_scale, maximum_tuple_count, &p))
+    return 1;
+  alignnet::DatasetTables t;
+  if (!alignnet_dataset_tables(h, &t)) return fail(h, name + ": no dataset uploaded");
+  if (!rows || B < 1) return fail(h, name + ": null rows or B < 1");
+  for (int i = 0; i < B; ++i)
+    if (rows[i] < 0 || rows[i] >= t.n) return fail(h, name + ": row " + std::to_string(rows[i]) + " out of range");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  std::vector<long long> off((size_t)(t.n + 1) * 2), n1(B), n2(B);   // the cloud sizes size the stage arrays
+  HIP_TRY(h, hipMemcpy(off.data(), t.off, off.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  for (int i = 0; i < B; ++i) {
+    n1[i] = off[((size_t)rows[i] + 1) * 2] - off[(size_t)rows[i] * 2];
+    n2[i] = off[((size_t)rows[i] + 1) * 2 + 1] - off[(size_t)rows[i] * 2 + 1];
+  }
+  return run_fgr(h, name, t.pts[0], t.pts[1], t.off, rows, n1, n2, B, p, out_T, out_fitness, out_rmse, out_correspondences, out_trials, nullptr);
+}
+
+extern "C" int alignnet_debug_fgr_stages(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2, int32_t flags,
+                                         uint64_t seed, int32_t stream, double division_factor, double maximum_correspondence_distance,
+                                         int32_t iteration_number, double tuple_scale, int32_t maximum_tuple_count, int64_t cap, int32_t* counts,
+                                         double* points, double* fpfh, int32_t* matches, int32_t* reverse_matches, int32_t* cross,
+                                         int32_t* tuple_source, int32_t* tuple_target, int64_t* tuple_trials, double* normalisation, double* trace,
+                                         double* out_T, double* out_fitness, double* out_rmse, int32_t* out_correspondences, int64_t* out_trials)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_debug_fgr_stages");
+  if (n1 < 0 || n2 < 0 || cap < n1 || cap < n2) return fail(h, name + ": cap must hold both clouds");
+  if (!counts || !points || !fpfh || !matches || !reverse_matches || !cross || !tuple_source || !tuple_target || !tuple_trials || !normalisation || !trace)
+    return fail(h, name + ": null output");
+  FgrParams p;
+  if (fgr_params(h, name, flags, seed, &stream, division_factor, maximum_correspondence_distance, iteration_number, tuple_scale, maximum_tuple_count, &p))
+    return 1;
+  const int64_t offsets[4] = {0, 0, n1, n2};
+  const FgrDebugOut dbg{cap, counts, points, fpfh, matches, reverse_matches, cross, tuple_source, tuple_target, tuple_trials, normalisation, trace};
+  return fgr_host(h, name, points1, points2, offsets, 1, p, out_T, out_fitness, out_rmse, out_correspondences, out_trials, &dbg);
 }

@@ -356,6 +356,51 @@ int alignnet_debug_global_stages(alignnet_handle* h, const float* points1, int64
                                  double* out_T, double* out_fitness, double* out_rmse, int64_t* out_iterations,
                                  int32_t* out_validations);
 
+/* ---- fast global registration (FGR) on FPFH feature matches (the `o3_gicp_fast` baseline, icp.py:121-143) ------
+ * Per pair: the same downsample, normals, FPFH and nearest-feature matches as alignnet_global_register, then Open3D
+ * 0.7's FastGlobalRegistration (Zhou, Park, Koltun, ECCV 2016): both clouds centred and divided by the largest
+ * centred norm; matches both ways and the cross check; the tuple test (ncorr * 100 trials of three correspondences,
+ * edge lengths within tuple_scale of each other, the first maximum_tuple_count passing trials kept); iteration_number
+ * Gauss-Newton steps with the line-process weight (mu / (r.r + mu))^2, mu starting at 1; no ICP follows.  Open3D is
+ * not available: the computation is DEFINED by tests/fgr_ref.py (unpinned; the trial draws, the order of the
+ * cross-checked list, the singularity test of the solve and the z-constrained form are this project's own).
+ * `flags`: bit 0 = ALIGNNET_ICP_FULL_ROTATION (six unknowns), clear = rotation about z only (x_2, t: a 4 x 4 system);
+ * ALIGNNET_FGR_DECREASE_MU: after every 4th iteration (0, 4, ...), while mu > maximum_correspondence_distance,
+ * mu /= division_factor.  Other bits are an error.  seed / streams as for alignnet_global_register.  Open3D's
+ * option values: division_factor 1.4, maximum_correspondence_distance 0.025, iteration_number 64, tuple_scale 0.95,
+ * maximum_tuple_count 1000.  Arguments outside their ranges (division_factor < 1, a distance <= 0, iteration_number or
+ * maximum_tuple_count outside [0, 2^20], tuple_scale outside (0, 1]) fail; nothing is clamped.
+ * out_T: [B][16] row-major 4x4 float64 mapping the source onto the target (identity for an empty cloud; the
+ * translation between the downsampled means when fewer than 10 correspondences pass the tuple test); out_fitness /
+ * out_rmse: inlier share and rmse of out_T on the downsampled clouds within maximum_correspondence_distance;
+ * out_correspondences: correspondences the tuple test kept (3 per passing trial); out_trials: trials drawn.  [B]
+ * each, may be NULL. */
+#define ALIGNNET_FGR_DECREASE_MU 2
+int alignnet_fgr_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
+                          int32_t flags, uint64_t seed, const int32_t* streams, double division_factor,
+                          double maximum_correspondence_distance, int32_t iteration_number, double tuple_scale,
+                          int32_t maximum_tuple_count, double* out_T, double* out_fitness, double* out_rmse,
+                          int32_t* out_correspondences, int64_t* out_trials);
+int alignnet_fgr_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, int32_t flags, uint64_t seed,
+                                  const int32_t* streams, double division_factor, double maximum_correspondence_distance,
+                                  int32_t iteration_number, double tuple_scale, int32_t maximum_tuple_count, double* out_T,
+                                  double* out_fitness, double* out_rmse, int32_t* out_correspondences, int64_t* out_trials);
+/* Test hook: one pair, with the stage outputs the tests pin on.  cap >= max(n1, n2) is the row stride of the per-cloud
+ * arrays (index 0 = source, 1 = target): counts [4] = downsampled sizes, cross-checked pairs, accepted tuples; points
+ * [2][cap][3]; fpfh [2][cap][33]; matches [cap] target index of every downsampled source point; reverse_matches [cap]
+ * source index of every downsampled target point; cross [cap] source indices of the mutual matches, ascending;
+ * tuple_source / tuple_target [3 maximum_tuple_count] the correspondences in trial order; tuple_trials
+ * [maximum_tuple_count] the trial of every accepted tuple; normalisation [7] the two means and the scale; trace
+ * [iteration_number][16] the transform after every iteration (normalised frame, target onto source). */
+int alignnet_debug_fgr_stages(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2,
+                              int32_t flags, uint64_t seed, int32_t stream, double division_factor,
+                              double maximum_correspondence_distance, int32_t iteration_number, double tuple_scale,
+                              int32_t maximum_tuple_count, int64_t cap, int32_t* counts, double* points, double* fpfh,
+                              int32_t* matches, int32_t* reverse_matches, int32_t* cross, int32_t* tuple_source,
+                              int32_t* tuple_target, int64_t* tuple_trials, double* normalisation, double* trace,
+                              double* out_T, double* out_fitness, double* out_rmse, int32_t* out_correspondences,
+                              int64_t* out_trials);
+
 /* ---- run-time options with no counterpart in the reference's config surface --------
  * "train_matmul_bf16" (0/1, default 0): training only -- the two MFMA convs of every backbone (the hidden 1x1 conv
  *   and the -> C3 feature lift, 96 % of the step's FLOPs, models/tp8.py:55-57), in the forward and in the backward's
