@@ -390,6 +390,27 @@ class Engine:
                                                                 dp(out), dp(fit), dp(rmse), itp))
         return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
 
+    def debug_icp_scan(self, source, target, T, radius=0.1, constrained=True, lds_points=0):
+        """Test hook: ONE evaluation (correspondence step at the 4x4 `T`) of one pair by the ICP kernel's own scan, with what it decided per
+        source point.  Returns dict(index [n1] chosen target, dist2 [n1] its fp64 squared distance, inlier [n1] bool, lanes [n1, 4] what each
+        lane of the point's quad did with its slice of the LDS-resident targets (0 none / 1 single / 2 walk; lane s holds targets s, s + 4, ...),
+        tail_won [n1] bool: the winner came from the fp64 tail, lds_points as used, fitness, rmse).  lds_points > 0 overrides the LDS stage's
+        size (<= 4266) so that small clouds reach the tail."""
+        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+        Tm = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+        n = max(len(p1), 1)
+        idx, d2, inl, paths = np.full(n, -1, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        used, fit, rmse = np.zeros(1, np.int32), np.zeros(1, np.float64), np.zeros(1, np.float64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.alignnet_debug_icp_scan(self._h, _fp(p1), len(p1), _fp(p2), len(p2), dp(Tm), float(radius),
+                                                      0 if constrained else ICP_FULL_ROTATION, int(lds_points), ip(idx), dp(d2), ip(inl), ip(paths),
+                                                      ip(used), dp(fit), dp(rmse)))
+        n1 = len(p1)
+        paths = paths[:n1]
+        return dict(index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1, lanes=np.stack([(paths >> (2 * s)) & 3 for s in range(4)], -1),
+                    tail_won=(paths & 256) != 0, lds_points=int(used[0]), fitness=float(fit[0]), rmse=float(rmse[0]))
+
     # ---- global registration: RANSAC on FPFH feature matches (csrc/alignnet_globalreg.hip) ----
     @staticmethod
     def _global_bufs(B, streams, default_streams):

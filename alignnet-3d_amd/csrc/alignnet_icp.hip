@@ -42,7 +42,12 @@ int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1;
   } while (0)
 
 constexpr int kIcpThreads = 1024, kIcpSums = 12, kIcpSplit = 4;   // threads per pair; sums of the z-constrained estimate; lanes per source point
-constexpr int kIcpSumsFull = 17;     // sums of the full-rotation estimate: count, a (3), b (3), b a^T (9), distance
+constexpr int kIcpSumsFull = 19;     // sums of the full-rotation estimate: count, a (3), b (3), b a^T (9), distance, |a|^2, |b|^2
+// A cross-covariance that is zero up to the rounding of its one-pass sums (one correspondence; every source point on the same target point) determines no
+// rotation: the estimate then keeps the rotation (Eigen's SVD of a zero matrix and the oracle's atan2(0, 0) both give the identity) instead of reading an
+// angle out of the residue (two source points on one target came out turned by pi).  Each entry is a sum of n products
+// bounded, with its centring term, by (n + 4) u sqrt(sum |a|^2 sum |b|^2) of rounding (Cauchy-Schwarz on the products' magnitudes), u = 2^-53.
+constexpr double kIcpNoise = 8.0 * 1.1102230246251565e-16;
 constexpr float kIcpFar = 1e18f;      // padding of the fp32 slices: a distance of 3e36, under no threshold
 typedef float icp_f32x2 __attribute__((ext_vector_type(2)));
 
@@ -69,7 +74,12 @@ struct IcpArgs {
   int lds_points;               // target points that fit in LDS
   double* out;                  // [B][16]
   double* fitness; double* rmse; int* iters;   // [B] each, may be null
+  // read only by the traced instantiations (icp_kernel<kFull, true>, alignnet_debug_icp_scan: one pair): per source point of the FIRST evaluation
+  int* tr_index; double* tr_dist; int* tr_inlier; int* tr_paths;
 };
+
+// path record of a quad (tr_paths): bits 2 s, 2 s + 1 = what lane s did with its slice of the LDS-resident targets, bit 8 = the winner came from the tail
+constexpr int kIcpPathNone = 0, kIcpPathSingle = 1, kIcpPathWalk = 2, kIcpPathTailWon = 256;
 
 template <int N>
 __device__ __forceinline__ void block_reduce(double (&v)[N], double* red /*[waves][N]*/, double* tot /*[N]*/)
@@ -90,7 +100,9 @@ __device__ __forceinline__ void block_reduce(double (&v)[N], double* red /*[wave
   __syncthreads();
 }
 
-template <bool kFull>
+// kTrace: the SAME scan, and behind the quad's merge one record per source point (IcpArgs::tr_*) -- the test hook's instantiations; the
+// shipped ones (kTrace = false) compile to what they were without it (per-kernel resource remarks unchanged)
+template <bool kFull, bool kTrace = false>
 __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
 {
   constexpr int kSums = kFull ? kIcpSumsFull : kIcpSums;
@@ -141,6 +153,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
         const double py = T[4] * sx + T[5] * sy + T[6] * sz + T[7];
         const double pz = T[8] * sx + T[9] * sy + T[10] * sz + T[11];
         double best = 1e300; int bj = 0x7fffffff;
+        int path = kIcpPathNone;
         {
           // one fp32 pass over the slice: its smallest distance m1 with the position it sits at, and its second smallest m2 (v_med3 of the
           // ordered pair and the newcomer) -- four vector instructions per target next to the packed arithmetic, no branch
@@ -168,6 +181,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
           // every target whose fp64 distance is the minimum has an fp32 distance <= thr.  A lane with ONE such target decides it in fp64; a lane
           // with two or more (a near-tie inside its slice: rare) walks its slice in fp64 as the all-fp64 kernel did
           if (m2 <= thr) {
+            if constexpr (kTrace) path = kIcpPathWalk;
 #pragma unroll 1
             for (int j = sub; j < nl; j += kIcpSplit) {
               const double ddx = px - tx[j], ddy = py - ty[j], ddz = pz - tz[j];
@@ -175,6 +189,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
               if (d < best) { best = d; bj = j; }   // strict: the first index of this lane's slice wins ties
             }
           } else if (m1 <= thr) {
+            if constexpr (kTrace) path = kIcpPathSingle;
             const int j = sub + kIcpSplit * im;
             if (j < nl) {
               const double ddx = px - tx[j], ddy = py - ty[j], ddz = pz - tz[j];
@@ -195,6 +210,15 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
           const int oj = __shfl_xor(bj, o);
           if (ob < best || (ob == best && oj < bj)) { best = ob; bj = oj; }
         }
+        if constexpr (kTrace) {
+          path <<= 2 * sub;
+          path |= __shfl_xor(path, 1);
+          path |= __shfl_xor(path, 2);
+          if (active && sub == 0 && k == 0) {
+            a.tr_index[i] = bj; a.tr_dist[i] = best; a.tr_inlier[i] = best <= r2;
+            a.tr_paths[i] = path | (bj >= nl ? kIcpPathTailWon : 0);
+          }
+        }
         if (active && sub == 0 && best <= r2) {
           const double qx = bj < nl ? tx[bj] : (double)dst[(long long)bj * 3];
           const double qy = bj < nl ? ty[bj] : (double)dst[(long long)bj * 3 + 1];
@@ -205,8 +229,10 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
             v[7] += bx * ax; v[8] += bx * ay; v[9] += bx * az;
             v[10] += by * ax; v[11] += by * ay; v[12] += by * az;
             v[13] += bz * ax; v[14] += bz * ay; v[15] += bz * az; v[16] += best;
+            v[17] += ax * ax + ay * ay + az * az; v[18] += bx * bx + by * by + bz * bz;
           } else {
             v[7] += ax * bx + ay * by; v[8] += ax * by - ay * bx; v[9] += best;
+            v[10] += ax * ax + ay * ay; v[11] += bx * bx + by * by;
           }
         }
       }
@@ -226,7 +252,14 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
           for (int i = 0; i < 3; ++i)
 #pragma unroll
             for (int j = 0; j < 3; ++j) red[i * 3 + j] = tot[7 + i * 3 + j] - cnt * (bm[i] * am[j]);
-          icp_umeyama_rotation(red);
+          double fro = 0.0;
+#pragma unroll
+          for (int i = 0; i < 9; ++i) fro += red[i] * red[i];
+          const double noise = kIcpNoise * cnt * sqrt(tot[17] * tot[18]);
+          if (fro > noise * noise)
+            icp_umeyama_rotation(red);
+          else
+            for (int i = 0; i < 9; ++i) Rm[i] = i % 4 == 0 ? 1.0 : 0.0;   // no rotation is determined: keep it
           const double mp[3] = {cx + am[0], cy + am[1], cz + am[2]}, mq[3] = {cx + bm[0], cy + bm[1], cz + bm[2]};
           // T <- U T,  U = [R | mean q - R mean p]
           double n[12];
@@ -244,7 +277,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
         const double aqx = tot[4] / cnt, aqy = tot[5] / cnt, aqz = tot[6] / cnt;
         const double sxx = tot[7] - cnt * (apx * aqx + apy * aqy);
         const double sxy = tot[8] - cnt * (apx * aqy - apy * aqx);
-        const double th = atan2(sxy, sxx), c = cos(th), s = sin(th);
+        const double noise = kIcpNoise * cnt * sqrt(tot[10] * tot[11]);
+        const double th = sxx * sxx + sxy * sxy > noise * noise ? atan2(sxy, sxx) : 0.0, c = cos(th), s = sin(th);   // (no rotation determined: keep it)
         const double mpx = cx + apx, mpy = cy + apy, mqx = cx + aqx, mqy = cy + aqy;
         const double tx = mqx - (c * mpx - s * mpy), ty = mqy - (s * mpx + c * mpy), tz = aqz - apz;
         // T <- U T,  U = [[c,-s,0,tx],[s,c,0,ty],[0,0,1,tz]]
@@ -270,8 +304,14 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
 }
 
 // shared driver: tables already on the device
+// alignnet_debug_icp_scan: host arrays [n1] for the records of pair 0's first evaluation; lds_points > 0 overrides the LDS stage's size (<= the budget)
+struct IcpTraceOut { long long n1; int lds_points; int* index; double* dist; int* inlier; int* paths; int* lds_points_used; };
+
+constexpr long long kIcpLdsBudget = (150 * 1024) / 36;   // doubles x 3 + floats x 3 per point within one CU's LDS
+
 int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long long* d_off, const int* d_rows, long long max_n2,
-            int B, const double* init, double radius, int its, bool full, double* out, double* fitness, double* rmse, int* iters)
+            int B, const double* init, double radius, int its, bool full, double* out, double* fitness, double* rmse, int* iters,
+            const IcpTraceOut* trace = nullptr)
 {
   if (!init || !out) return fail(h, "icp: null init / out");
   if (!(radius > 0.0) || its < 0) return fail(h, "icp: radius must be > 0 and its >= 0");
@@ -283,32 +323,57 @@ int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long
   HIP_TRY(h, hipMemcpyAsync(d_init, init, (size_t)B * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   IcpArgs a;
   a.pts[0] = d_p0; a.pts[1] = d_p1; a.off = d_off; a.rows = d_rows; a.init = d_init; a.radius = radius; a.its = its;
-  const long long budget = (150 * 1024) / 36;   // doubles x 3 + floats x 3 per point within one CU's LDS
-  a.lds_points = (int)std::max<long long>(1, std::min(budget, max_n2));
+  a.lds_points = (int)std::max<long long>(1, std::min(kIcpLdsBudget, max_n2));
   a.out = d_out; a.fitness = d_fr; a.rmse = d_fr + B; a.iters = d_it;
-  static alignnet::PerDeviceOnce attr[2];
-  const void* kernel = full ? reinterpret_cast<const void*>(icp_kernel<true>) : reinterpret_cast<const void*>(icp_kernel<false>);
-  if (attr[full].need(h->cfg.device)) {
-    HIP_TRY(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
-    attr[full].mark(h->cfg.device);
+  a.tr_index = a.tr_inlier = a.tr_paths = nullptr; a.tr_dist = nullptr;
+  char* d_tr = nullptr;   // [n1] doubles | 3 x [n1] ints
+  if (trace) {
+    if (trace->lds_points > 0) a.lds_points = trace->lds_points;
+    const size_t n = (size_t)std::max<long long>(trace->n1, 1);
+    HIP_TRY(h, hipMalloc(&d_tr, n * 20));
+    HIP_TRY(h, hipMemsetAsync(d_tr, 0xff, n * 20, h->stream));   // (index -1 where the kernel wrote nothing: an empty target)
+    a.tr_dist = reinterpret_cast<double*>(d_tr);
+    a.tr_index = reinterpret_cast<int*>(d_tr + n * 8); a.tr_inlier = a.tr_index + n; a.tr_paths = a.tr_inlier + n;
   }
-  if (full)
+  static alignnet::PerDeviceOnce attr[4];
+  const int which = (full ? 1 : 0) + (trace ? 2 : 0);
+  const void* const kernels[4] = {reinterpret_cast<const void*>(icp_kernel<false>), reinterpret_cast<const void*>(icp_kernel<true>),
+                                  reinterpret_cast<const void*>(icp_kernel<false, true>), reinterpret_cast<const void*>(icp_kernel<true, true>)};
+  if (attr[which].need(h->cfg.device)) {
+    HIP_TRY(h, hipFuncSetAttribute(kernels[which], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+    attr[which].mark(h->cfg.device);
+  }
+  if (which == 3)
+    hipLaunchKernelGGL((icp_kernel<true, true>), dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
+  else if (which == 2)
+    hipLaunchKernelGGL((icp_kernel<false, true>), dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
+  else if (full)
     hipLaunchKernelGGL(icp_kernel<true>, dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
   else
     hipLaunchKernelGGL(icp_kernel<false>, dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
   HIP_TRY(h, hipGetLastError());
+  if (trace) {
+    const size_t n = (size_t)std::max<long long>(trace->n1, 1), m = (size_t)trace->n1;
+    if (m) {
+      HIP_TRY(h, hipMemcpyAsync(trace->dist, d_tr, m * 8, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->index, d_tr + n * 8, m * 4, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->inlier, d_tr + n * 12, m * 4, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->paths, d_tr + n * 16, m * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    *trace->lds_points_used = a.lds_points;
+  }
   HIP_TRY(h, hipMemcpyAsync(out, d_out, (size_t)B * 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (fitness) HIP_TRY(h, hipMemcpyAsync(fitness, d_fr, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (rmse) HIP_TRY(h, hipMemcpyAsync(rmse, d_fr + B, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (iters) HIP_TRY(h, hipMemcpyAsync(iters, d_it, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  hipFree(d_init); hipFree(d_out); hipFree(d_fr); hipFree(d_it);
+  hipFree(d_init); hipFree(d_out); hipFree(d_fr); hipFree(d_it); hipFree(d_tr);
   return 0;
 }
 
 // clouds passed from the host (alignnet_icp_refine / alignnet_icp_register); `fn` names the entry point in the messages
 int icp_host(alignnet_handle* h, const char* fn, const float* points1, const float* points2, const int64_t* offsets, int32_t B, const double* init,
-             double radius, int32_t its, bool full, double* out, double* fitness, double* rmse, int32_t* iterations)
+             double radius, int32_t its, bool full, double* out, double* fitness, double* rmse, int32_t* iterations, const IcpTraceOut* trace = nullptr)
 {
   if (!h) return 1;
   const std::string name(fn);
@@ -328,7 +393,7 @@ int icp_host(alignnet_handle* h, const char* fn, const float* points1, const flo
   if (n0) HIP_TRY(h, hipMemcpyAsync(d0, points1, n0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   if (n1) HIP_TRY(h, hipMemcpyAsync(d1, points2, n1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(doff, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  const int rc = run_icp(h, d0, d1, doff, nullptr, max_n2, B, init, radius, its, full, out, fitness, rmse, iterations);
+  const int rc = run_icp(h, d0, d1, doff, nullptr, max_n2, B, init, radius, its, full, out, fitness, rmse, iterations, trace);
   hipFree(d0); hipFree(d1); hipFree(doff);
   return rc;
 }
@@ -349,7 +414,7 @@ int icp_rows(alignnet_handle* h, const char* fn, const int32_t* rows, int32_t B,
   HIP_TRY(h, hipMalloc(&d_rows, (size_t)B * sizeof(int)));
   HIP_TRY(h, hipMemcpyAsync(d_rows, rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   // the largest target cloud is not known on the host: size the LDS stage for the budget, the kernel clamps per pair
-  const int rc = run_icp(h, t.pts[0], t.pts[1], t.off, d_rows, (150 * 1024) / 36, B, init, radius, its, full, out, fitness, rmse, iterations);
+  const int rc = run_icp(h, t.pts[0], t.pts[1], t.off, d_rows, kIcpLdsBudget, B, init, radius, its, full, out, fitness, rmse, iterations);
   hipFree(d_rows);
   return rc;
 }
@@ -394,4 +459,21 @@ extern "C" int alignnet_icp_register_dataset(alignnet_handle* h, const int32_t* 
   bool full = false;
   if (icp_flags(h, "alignnet_icp_register_dataset", flags, &full)) return 1;
   return icp_rows(h, "alignnet_icp_register_dataset", rows, B, init, radius, its, full, out, fitness, rmse, iterations);
+}
+
+extern "C" int alignnet_debug_icp_scan(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2, const double* T,
+                                       double radius, int32_t flags, int32_t lds_points, int32_t* index, double* dist2, int32_t* inlier,
+                                       int32_t* paths, int32_t* lds_points_used, double* fitness, double* rmse)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_debug_icp_scan");
+  bool full = false;
+  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
+  if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(h, name + ": n1 / n2 out of range");
+  if (lds_points < 0 || lds_points > kIcpLdsBudget) return fail(h, name + ": lds_points must be in [0, " + std::to_string(kIcpLdsBudget) + "] (0 = as shipped)");
+  if (!index || !dist2 || !inlier || !paths || !lds_points_used) return fail(h, name + ": null output");
+  const int64_t off[4] = {0, 0, n1, n2};
+  const IcpTraceOut tr = {n1, lds_points, index, dist2, inlier, paths, lds_points_used};
+  double out[16];
+  return icp_host(h, name.c_str(), points1, points2, off, 1, T, radius, 0, full, out, fitness, rmse, nullptr, &tr);
 }

@@ -324,6 +324,20 @@ int alignnet_icp_register(alignnet_handle* h, const float* points1, const float*
                           double* rmse, int32_t* iterations);
 int alignnet_icp_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
                                   int32_t its, int32_t flags, double* out, double* fitness, double* rmse, int32_t* iterations);
+/* Test hook: ONE evaluation (the correspondence step at the transform T [16], no estimate) of one pair by the kernel of
+ * alignnet_icp_register* itself (the same scan source, compiled with a record behind it), and what it decided for
+ * every source point: index [n1] the chosen target (-1: empty target cloud); dist2 [n1] its squared distance, fp64;
+ * inlier [n1] 1 when dist2 <= radius^2; paths [n1] what the four lanes of the point's quad did with their slices of the
+ * LDS-resident targets -- bits 2 s, 2 s + 1 for lane s (targets s, s + 4, ...): 0 = none (nothing under the fp32
+ * certificate's threshold), 1 = single (one target decided in fp64), 2 = walk (the slice walked in fp64) -- and bit 8 set
+ * when the winner came from the fp64 tail behind the LDS stage.  lds_points: 0 = as shipped (min(4266, n2)), else the
+ * number of targets staged in LDS (1 .. 4266: reaches the tail with small clouds); lds_points_used [1] what was used.
+ * flags as for alignnet_icp_register; fitness / rmse [1] of this evaluation, may be NULL.
+ * Like every alignnet_debug_* entry this is outside the stable surface: ALIGNNET_ABI_VERSION does not move for it. */
+int alignnet_debug_icp_scan(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2,
+                            const double* T, double radius, int32_t flags, int32_t lds_points, int32_t* index,
+                            double* dist2, int32_t* inlier, int32_t* paths, int32_t* lds_points_used, double* fitness,
+                            double* rmse);
 
 /* ---- global registration: RANSAC on FPFH feature matches (the `o3_gicp` baseline, icp.py:85-143) --------------
  * Per pair: voxel downsample (0.05 m) of both clouds, normals (radius 0.10, 30 nearest), FPFH (radius 0.25, 100
