@@ -134,6 +134,15 @@ SYMBOLS = {
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "alignnet_scene_set_sensor": (C.c_int, [H, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "alignnet_scene_upload_meshes": (C.c_int, [H, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32]),
+    "alignnet_scene_free_meshes": (C.c_int, [H]),
+    "alignnet_scene_generate": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32, C.c_uint64,
+                                          C.c_double, C.c_double, C.POINTER(C.c_int64)]),
+    "alignnet_scene_read": (C.c_int, [H, FP, FP]),
+    "alignnet_scene_install_dataset": (C.c_int, [H, FP]),
+    "alignnet_debug_scene_cast": (C.c_int, [H, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "alignnet_set_option": (C.c_int, [H, C.c_char_p, C.c_int64]),
     "alignnet_get_option": (C.c_int, [H, C.c_char_p, C.POINTER(C.c_int64)]),
     "alignnet_profile_read_kernel": (C.c_int, [H, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

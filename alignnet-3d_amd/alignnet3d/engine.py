@@ -550,6 +550,72 @@ class Engine:
             out[name] = [arr[k, : counts[k]].copy() for k in range(2)]
         return out
 
+    # ---- spinning-LiDAR scene generator (csrc/alignnet_scene.hip; alignnet3d/scenes.py builds the arguments) ----
+    def scene_upload_meshes(self, meshes, sensor=None):
+        """meshes: list of (vertices [nv, 3] float64 normalised as scenes.normalise_mesh does, faces [nf, 3] int, centroid [3]); sensor: (dir_x [4500],
+        dir_y [4500], dir_z [64]) direction tables, None = scenes.sensor_tables().  Copied to the device once."""
+        from . import scenes
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        sx, sy, sz = (np.ascontiguousarray(a, np.float64) for a in (scenes.sensor_tables() if sensor is None else sensor))
+        assert sx.shape == (scenes.HRES,) and sy.shape == (scenes.HRES,) and sz.shape == (scenes.VRES,)
+        self._check(self._lib.alignnet_scene_set_sensor(self._h, dp(sx), dp(sy), dp(sz)))
+        M = len(meshes)
+        off = np.zeros((M + 1, 2), np.int64)
+        for m, (v, f, _) in enumerate(meshes):
+            off[m + 1] = off[m] + (len(v), len(f))
+        cat = lambda L, dt: np.ascontiguousarray(np.concatenate([np.asarray(x, dt).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), dt)
+        verts, faces = cat([m[0] for m in meshes], np.float64), cat([m[1] for m in meshes], np.int32)
+        cen = np.ascontiguousarray(np.asarray([m[2] for m in meshes], np.float64).reshape(M, 3))
+        self._check(self._lib.alignnet_scene_upload_meshes(self._h, dp(verts), faces.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           off.ctypes.data_as(C.POINTER(C.c_int64)), dp(cen), M))
+
+    def scene_free_meshes(self):
+        self._check(self._lib.alignnet_scene_free_meshes(self._h))
+
+    def scene_generate(self, mesh, scale, poses, scene_ids=None, seed=0, sigma=0.05, clip=0.05):
+        """mesh [B] library indices, scale [B], poses [B, 2, 4] = x y z angle of the two clouds, scene_ids [B] (None = 0 .. B - 1).  sigma <= 0: no
+        noise.  The clouds stay on the device (scene_read / scene_install_dataset); returns the offsets table [B + 1, 2]."""
+        mesh = np.ascontiguousarray(mesh, np.int32).ravel()
+        B = mesh.size
+        scale = np.ascontiguousarray(scale, np.float64).ravel()
+        poses = np.ascontiguousarray(poses, np.float64).reshape(B, 2, 4)
+        assert scale.size == B
+        ids = None if scene_ids is None else np.ascontiguousarray(scene_ids, np.int64).ravel()
+        assert ids is None or ids.size == B
+        off = np.zeros((B + 1, 2), np.int64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(self._lib.alignnet_scene_generate(self._h, mesh.ctypes.data_as(C.POINTER(C.c_int32)), dp(scale), dp(poses),
+                                                      None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_int64)), B, int(seed) & (2 ** 64 - 1),
+                                                      float(sigma), float(clip), off.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._scene_offsets = off
+        return off
+
+    def scene_read(self, offsets=None):
+        """(points1, points2) float32 [n, 3] blobs of the last scene_generate (offsets: its return value, None = remembered)."""
+        off = self._scene_offsets if offsets is None and hasattr(self, "_scene_offsets") else offsets
+        n1, n2 = (0, 0) if off is None else (int(off[-1, 0]), int(off[-1, 1]))
+        p1, p2 = np.empty((n1, 3), np.float32), np.empty((n2, 3), np.float32)
+        self._check(self._lib.alignnet_scene_read(self._h, _fp(p1), _fp(p2)))
+        return p1, p2
+
+    def scene_install_dataset(self, labels):
+        """The last scene_generate becomes the HBM-resident dataset (device to device); labels [B, 12] as for upload_dataset."""
+        lab = np.ascontiguousarray(labels, np.float32).reshape(-1, 12)
+        assert hasattr(self, "_scene_offsets") and lab.shape[0] == self._scene_offsets.shape[0] - 1, "one label row per generated scene"
+        self._check(self._lib.alignnet_scene_install_dataset(self._h, _fp(lab)))
+
+    def debug_scene_cast(self, mesh, scale, pose, lds_triangles=0):
+        """Test hook: ONE cloud by the shipped cast kernel, no noise.  Returns dict(t [64, 4500] float64 (inf = miss), triangle [64, 4500] (-1), window =
+        (first column, columns), lds_triangles as used).  lds_triangles in 1 .. 512 forces several LDS chunks on small meshes."""
+        pose = np.ascontiguousarray(pose, np.float64).reshape(4)
+        t, tri = np.empty(64 * 4500, np.float64), np.empty(64 * 4500, np.int32)
+        win, used = np.zeros(2, np.int32), np.zeros(1, np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.alignnet_debug_scene_cast(self._h, int(mesh), float(scale), pose.ctypes.data_as(C.POINTER(C.c_double)), int(lds_triangles),
+                                                        t.ctypes.data_as(C.POINTER(C.c_double)), ip(tri), ip(win), ip(used)))
+        self.__dict__.pop("_scene_offsets", None)
+        return dict(t=t.reshape(64, 4500), triangle=tri.reshape(64, 4500), window=(int(win[0]), int(win[1])), lds_triangles=int(used[0]))
+
     @staticmethod
     def read_device(ptr, count, dtype=np.float32):
         """Debug / test helper: copy `count` elements from a device pointer (synchronous hipMemcpy)."""
@@ -735,7 +801,7 @@ class Engine:
         self._check(self._lib.alignnet_profile_enable(self._h, int(on)))
 
     PROFILED_KERNELS = ("backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1",
-                        "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer")
+                        "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact")
 
     def profile_kernels(self):
         """{kernel: (ms, launches)} accumulated since the last profile_read(reset=True); call BEFORE that reset."""

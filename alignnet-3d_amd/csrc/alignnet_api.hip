@@ -196,6 +196,7 @@ extern "C" void alignnet_train_ws_free(alignnet_handle* h);
 extern "C" int alignnet_dataset_free(alignnet_handle* h);
 extern "C" void alignnet_comm_free(alignnet_handle* h);
 extern "C" void alignnet_globalreg_free(alignnet_handle* h);
+extern "C" void alignnet_scene_free(alignnet_handle* h);
 
 namespace { void pipe_free(alignnet_handle* h); hipStream_t pipe_stream(alignnet_handle* h, int which); }   // pipelined host path, defined with alignnet_forward_submit below
 
@@ -208,6 +209,7 @@ extern "C" void alignnet_destroy(alignnet_handle* h)
   alignnet_train_ws_free(h);
   alignnet_dataset_free(h);
   alignnet_globalreg_free(h);
+  alignnet_scene_free(h);
   pipe_free(h);
   free_ws(h);
   for (auto& pr : h->prof_pending) { hipEventDestroy(pr.a); hipEventDestroy(pr.b); }

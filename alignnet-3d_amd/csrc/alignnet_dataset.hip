@@ -141,25 +141,26 @@ extern "C" int alignnet_dataset_free(alignnet_handle* h)
   return 0;
 }
 
-extern "C" int alignnet_dataset_upload(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets,
-                                       const float* labels, int64_t n_examples)
+int alignnet_dataset_install(alignnet_handle* h, const float* points1, const float* points2, bool device_points, const int64_t* offsets, const float* labels,
+                             int64_t n_examples, const char* fn)
 {
   if (!h) return 1;
-  if (!offsets || !labels || n_examples < 1) return fail(h, "alignnet_dataset_upload: null table or no examples");
+  const std::string name(fn);
+  if (!offsets || !labels || n_examples < 1) return fail(h, name + ": null table or no examples");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   for (int64_t i = 0; i < n_examples; ++i)
     for (int t = 0; t < 2; ++t)
-      if (offsets[(i + 1) * 2 + t] < offsets[i * 2 + t]) return fail(h, "alignnet_dataset_upload: offsets must be non-decreasing");
-  if (offsets[0] != 0 || offsets[1] != 0) return fail(h, "alignnet_dataset_upload: offsets must start at 0");
+      if (offsets[(i + 1) * 2 + t] < offsets[i * 2 + t]) return fail(h, name + ": offsets must be non-decreasing");
+  if (offsets[0] != 0 || offsets[1] != 0) return fail(h, name + ": offsets must start at 0");
   alignnet_dataset_free(h);
   DatasetWS* w = new DatasetWS();
   h->dataset_ws = w;
   const float* src[2] = {points1, points2};
   for (int t = 0; t < 2; ++t) {
     const size_t np = (size_t)offsets[n_examples * 2 + t];
-    if (np && !src[t]) return fail(h, "alignnet_dataset_upload: null point blob");
+    if (np && !src[t]) return fail(h, name + ": null point blob");
     HIP_TRY(h, hipMalloc(&w->pts[t], std::max<size_t>(np, 1) * 3 * sizeof(float)));
-    if (np) HIP_TRY(h, hipMemcpy(w->pts[t], src[t], np * 3 * sizeof(float), hipMemcpyHostToDevice));
+    if (np) HIP_TRY(h, hipMemcpy(w->pts[t], src[t], np * 3 * sizeof(float), device_points ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   }
   HIP_TRY(h, hipMalloc(&w->off, (size_t)(n_examples + 1) * 2 * sizeof(long long)));
   HIP_TRY(h, hipMemcpy(w->off, offsets, (size_t)(n_examples + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice));
@@ -167,6 +168,12 @@ extern "C" int alignnet_dataset_upload(alignnet_handle* h, const float* points1,
   HIP_TRY(h, hipMemcpy(w->labels, labels, (size_t)n_examples * 12 * sizeof(float), hipMemcpyHostToDevice));
   w->n = n_examples;
   return 0;
+}
+
+extern "C" int alignnet_dataset_upload(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets,
+                                       const float* labels, int64_t n_examples)
+{
+  return alignnet_dataset_install(h, points1, points2, false, offsets, labels, n_examples, "alignnet_dataset_upload");
 }
 
 extern "C" int alignnet_dataset_sample(alignnet_handle* h, const int32_t* rows, int32_t B, uint64_t seed, float jitter_sigma,

@@ -1,0 +1,707 @@
+// Spinning-LiDAR scene generator (the SynthCars-style datasets of tp_utils/pointcloud.py:945-971,1055-1186), gfx950 only.
+//
+// Replaces trimesh + embree in SyntheticScene.generate_pointcloud_embree: the 64 x 4500-ray sensor (vfov 26.9 deg, 360 deg) is cast against
+// a posed triangle mesh, the first hit per ray is kept in ascending ray index (the reference's 20 ray parts, concatenated), and the clipped
+// range-dependent noise (:1133-1136) is added.  The semantics are DEFINED by tests/scene_ref.py (fp64, NumPy); what is this project's own:
+//  - the intersection is the scalar-triple-product form of Moeller-Trumbore with the origin at 0.  Per triangle (posed vertices v0, v1, v2, e1 = v1 - v0,
+//    e2 = v2 - v0):  N = e1 x e2,  A = e2 x v0,  Bv = v0 x e1,  c = v0 . N;  per ray d:  den = d . N,  u = d . A / den,  v = d . Bv / den,  t = c / den;
+//    hit when den != 0, u >= 0, v >= 0, u + v <= 1, t > 0 (two-sided; a zero-area triangle has N = 0 and never hits).  Everything is fp64 and every
+//    product and sum is rounded as written (no fused multiply-add: an exact zero of N or den must stay one), so the ten numbers per triangle and the three
+//    dot products per ray are bit for bit the restatement's.  The kernel tests the signs of the numerators instead of dividing (u >= 0 exactly when d . A
+//    and den agree in sign; u + v <= 1 as |d . A + d . Bv| <= |den|, which differs from the quotient form only within a few ulp of an edge, inside the
+//    restatement's undecided band of 1e-9) and divides once per hit.  Equal t: the lower triangle index wins, whatever the order of the LDS stage.
+//  - the noise stream is the dataset sampler's counter hash (alignnet_dataset.hip: mix64 + Box-Muller) keyed by (seed, scene id, cloud, ray index): a
+//    result never depends on the batch it was generated in.  It is NOT np.random.randn's stream (parity unpinned by construction, as for the sampler).
+//
+// Stages of one alignnet_scene_generate (B scenes x 2 clouds against the uploaded mesh library):
+//  1. scene_window_kernel, one workgroup per cloud: every triangle marks the columns its azimuth interval covers (+- 1e-6 column of margin) in an LDS
+//     difference array (integer atomics: order-free); a triangle whose xy projection holds the z axis covers all 4500.  The window is the complement of the
+//     largest uncovered gap of the circle of columns, so it may wrap 4499 -> 0.  The windows come back to the host (one small copy), which deals
+//     (cloud, tile of 8 window columns) work items: a batch of small far objects and one near object both become hundreds of workgroups.
+//  2. scene_cast_kernel, one workgroup (four waves) per tile; lane = elevation row, a wave takes two of the tile's columns.  The cloud's triangles go
+//     through LDS in chunks of 512: each is posed (Rz(angle) (scale v) + position, fp64), culled against the tile's azimuth sector by two exact side tests
+//     with a relative margin (all three vertices strictly before the first column's half plane, or strictly behind the last one's: conservative, so what is
+//     left is decided in fp64 as above), and the survivors' ten numbers are compacted into LDS (ballot prefix: deterministic order).  The inner loop reads
+//     one triangle as a broadcast and tests it against the wave's two columns.  Cost model: every tile poses and side-tests all T triangles of its cloud
+//     (T / 256 per thread, latency-bound on the vertex gathers) and intersects 64 x 8 rays with the few that overlap its 0.64 deg sector; a car of some
+//     hundred triangles is one chunk, a 10^5-triangle model is 200 chunks per tile -- a per-cloud binning of triangles to tiles would remove the T / 256 term
+//     and is the next step if such models matter.  t per ray goes to a [row][window column] table (inf = miss).
+//  3. scene_count_kernel (hits per (cloud, row)), scene_scan_kernel (exclusive scan in (scene, row) order per cloud index: the offsets table),
+//     scene_scatter_kernel (per (cloud, row): columns in ascending COLUMN order -- a wrapped window starts at column 0 -- ballot prefix, location = t d in
+//     fp64 rounded to float, + noise).  Counts, a scan, a scatter: no atomics that could reorder points.
+#include "engine.h"
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+namespace {
+
+int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1; }
+
+#define HIP_TRY(h, expr)                                                                         \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess) return fail(h, std::string(#expr) + ": " + hipGetErrorString(e_));     \
+  } while (0)
+
+constexpr int kRows = 64, kCols = 4500, kRays = kRows * kCols;
+constexpr int kTileCols = 8, kCastThreads = 256, kColsPerWave = kTileCols / (kCastThreads / 64);
+constexpr int kLdsTriangles = 512;        // triangles per LDS chunk as shipped (88 bytes each: three workgroups per CU)
+constexpr double kColMargin = 1e-6;       // columns of margin around a triangle's azimuth interval (fp64 atan2 is good to 1e-13 column)
+constexpr double kSideMargin = 1e-12;     // relative margin of the side tests (their rounding error is 4e-16 of the same scale)
+
+struct SceneTri { double N[3], A[3], Bv[3], c; int id, pad; };
+static_assert(sizeof(SceneTri) == 88, "LDS budget");
+
+struct SceneCloud {
+  double cs, sn, scale, px, py, pz;   // pose: Rz (scale v) + p
+  long long v0, f0;                   // first vertex / face of the mesh in the library
+  long long tbase;                    // first entry of this cloud's [64][count] table of t
+  unsigned long long scene_id;
+  int nf, first, count, which;        // faces; window (first column, columns); cloud index 0 / 1
+  float strength; int pad;
+};
+
+struct V3 { double x, y, z; };
+
+__device__ __forceinline__ V3 pose(const SceneCloud& c, const double* __restrict__ v)
+{
+#pragma clang fp contract(off)
+  const double sx = c.scale * v[0], sy = c.scale * v[1], sz = c.scale * v[2];
+  V3 r;
+  r.x = (c.cs * sx - c.sn * sy) + c.px;
+  r.y = (c.sn * sx + c.cs * sy) + c.py;
+  r.z = sz + c.pz;
+  return r;
+}
+
+__device__ __forceinline__ void tri_setup(const V3& a, const V3& b, const V3& cc, SceneTri& t)
+{
+#pragma clang fp contract(off)
+  const double e1x = b.x - a.x, e1y = b.y - a.y, e1z = b.z - a.z, e2x = cc.x - a.x, e2y = cc.y - a.y, e2z = cc.z - a.z;
+  t.N[0] = e1y * e2z - e1z * e2y; t.N[1] = e1z * e2x - e1x * e2z; t.N[2] = e1x * e2y - e1y * e2x;
+  t.A[0] = e2y * a.z - e2z * a.y; t.A[1] = e2z * a.x - e2x * a.z; t.A[2] = e2x * a.y - e2y * a.x;
+  t.Bv[0] = a.y * e1z - a.z * e1y; t.Bv[1] = a.z * e1x - a.x * e1z; t.Bv[2] = a.x * e1y - a.y * e1x;
+  t.c = (a.x * t.N[0] + a.y * t.N[1]) + a.z * t.N[2];
+}
+
+// ---- stage 1: the azimuth window of a cloud --------------------------------------------------------------------------------------------
+// column coordinate of a direction in the xy plane: h = atan2(x, y) in degrees, column = (h + 180) / 0.08
+__device__ __forceinline__ double col_coord(double x, double y) { return (atan2(x, y) * 57.29577951308232 + 180.0) * (kCols / 360.0); }
+
+__device__ int next_bit(const unsigned* w, int p, bool want_set)   // first position >= p whose bit is set / clear, -1 if none below kCols
+{
+  constexpr int kWords = (kCols + 31) / 32;
+  int i = p >> 5;
+  if (i >= kWords) return -1;
+  unsigned m = (want_set ? w[i] : ~w[i]) & (0xffffffffu << (p & 31));
+  while (m == 0) {
+    if (++i >= kWords) return -1;
+    m = want_set ? w[i] : ~w[i];
+  }
+  const int q = i * 32 + __ffs(m) - 1;
+  return q < kCols ? q : -1;
+}
+
+__global__ __launch_bounds__(256) void scene_window_kernel(const SceneCloud* __restrict__ clouds, const double* __restrict__ verts,
+                                                           const int* __restrict__ faces, int* __restrict__ win /*[clouds][2]*/)
+{
+  constexpr int kWords = (kCols + 31) / 32, kPer = 18;   // 250 threads x 18 columns
+  __shared__ int diff[kCols + 1];
+  __shared__ unsigned words[kWords];
+  __shared__ int wsum[4];
+  __shared__ int s_full;
+  const SceneCloud c = clouds[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i <= kCols; i += 256) diff[i] = 0;
+  for (int i = tid; i < kWords; i += 256) words[i] = 0;
+  if (tid == 0) s_full = 0;
+  __syncthreads();
+  for (int f = tid; f < c.nf; f += 256) {
+    const int* fi = faces + (c.f0 + f) * 3;
+    const V3 a = pose(c, verts + (c.v0 + fi[0]) * 3), b = pose(c, verts + (c.v0 + fi[1]) * 3), d = pose(c, verts + (c.v0 + fi[2]) * 3);
+    SceneTri t;
+    tri_setup(a, b, d, t);
+    if (t.N[0] == 0.0 && t.N[1] == 0.0 && t.N[2] == 0.0) continue;   // zero area: never hit
+    // does the xy projection hold the z axis (with margin)?  o_k = cross of consecutive vertices; their sum is twice the projected area
+    const double o1 = a.x * b.y - a.y * b.x, o2 = b.x * d.y - b.y * d.x, o3 = d.x * a.y - d.y * a.x;
+    const double ext = fmax(fmax(fabs(a.x) + fabs(a.y), fabs(b.x) + fabs(b.y)), fabs(d.x) + fabs(d.y));
+    const double m = kSideMargin * ext * ext;
+    bool full;
+    if (fabs(o1 + o2 + o3) > m)
+      full = (o1 >= -m && o2 >= -m && o3 >= -m) || (o1 <= m && o2 <= m && o3 <= m);
+    else   // the projection is a segment: it holds the axis when two vertices lie on opposite sides of it
+      full = fmin(fmin(a.x * b.x + a.y * b.y, b.x * d.x + b.y * d.y), d.x * a.x + d.y * a.y) <= m;
+    if (!full) {
+      const double c0 = col_coord(a.x, a.y);
+      double d1 = col_coord(b.x, b.y) - c0, d2 = col_coord(d.x, d.y) - c0;
+      d1 -= kCols * rint(d1 / kCols); d2 -= kCols * rint(d2 / kCols);   // into [-2250, 2250]
+      const double lo = c0 + fmin(0.0, fmin(d1, d2)), hi = c0 + fmax(0.0, fmax(d1, d2));
+      if (hi - lo >= kCols / 2 - 1.0) full = true;
+      else {
+        const long long ca = (long long)floor(lo - kColMargin), cb = (long long)ceil(hi + kColMargin);
+        const int n = (int)(cb - ca + 1);
+        int s = (int)(ca % kCols); if (s < 0) s += kCols;
+        atomicAdd(&diff[s], 1);
+        if (s + n <= kCols) atomicAdd(&diff[s + n], -1);
+        else { atomicAdd(&diff[0], 1); atomicAdd(&diff[s + n - kCols], -1); }
+      }
+    }
+    if (full) s_full = 1;
+  }
+  __syncthreads();
+  if (s_full) { if (tid == 0) { win[blockIdx.x * 2] = 0; win[blockIdx.x * 2 + 1] = kCols; } return; }
+  // coverage = prefix sum of the difference array > 0: thread t takes columns 18 t .. 18 t + 17
+  int own = 0;
+  if (tid < kCols / kPer)
+    for (int k = 0; k < kPer; ++k) own += diff[tid * kPer + k];
+  int inc = own;
+  for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(inc, o); if (lane >= o) inc += u; }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  int run = inc - own;
+  for (int w = 0; w < wave; ++w) run += wsum[w];
+  if (tid < kCols / kPer) {
+    unsigned bits = 0;
+    for (int k = 0; k < kPer; ++k) { run += diff[tid * kPer + k]; if (run > 0) bits |= 1u << k; }
+    const int p = tid * kPer, sh = p & 31;
+    if (bits) {
+      atomicOr(&words[p >> 5], bits << sh);
+      if (sh + kPer > 32) atomicOr(&words[(p >> 5) + 1], bits >> (32 - sh));
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int s0 = next_bit(words, 0, true);
+    int first = 0, count = 0;
+    if (s0 >= 0) {
+      int best_len = 0, best_start = 0, pos = s0;
+      for (;;) {
+        const int g = next_bit(words, pos, false);   // first uncovered column behind the arc that starts at pos
+        if (g < 0) { if (s0 > best_len) { best_len = s0; best_start = 0; } break; }   // covered up to 4499: the gap is [0, s0)
+        const int n = next_bit(words, g, true);
+        if (n < 0) { const int len = kCols - g + s0; if (len > best_len) { best_len = len; best_start = g; } break; }
+        if (n - g > best_len) { best_len = n - g; best_start = g; }
+        pos = n;
+      }
+      first = (best_start + best_len) % kCols; count = kCols - best_len;
+      if (best_len == 0) first = 0;
+    }
+    win[blockIdx.x * 2] = first; win[blockIdx.x * 2 + 1] = count;
+  }
+}
+
+// ---- stage 2: the cast ---------------------------------------------------------------------------------------------------------------------
+struct SceneCastArgs {
+  const SceneCloud* clouds; const int* tiles /*[tiles][2] = cloud, tile of the window*/;
+  const double* verts; const int* faces; const double* dir /*[4500] x | [4500] y | [64] z*/;
+  double* t; int* tri;          // [64][count] per cloud at tbase; tri only in the traced instantiation
+  int lds_triangles;
+};
+
+template <bool kTrace>
+__global__ __launch_bounds__(kCastThreads) void scene_cast_kernel(const SceneCastArgs a)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  SceneTri* tris = reinterpret_cast<SceneTri*>(lds_raw);
+  __shared__ int wcnt[kCastThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ci = a.tiles[blockIdx.x * 2], j0 = a.tiles[blockIdx.x * 2 + 1] * kTileCols;
+  const SceneCloud c = a.clouds[ci];
+  const int ncol = min(kTileCols, c.count - j0);
+  // the tile's azimuth sector: its first and last column (the window may wrap)
+  const int col_a = (c.first + j0) % kCols, col_b = (c.first + j0 + ncol - 1) % kCols;
+  const double ax = a.dir[col_a], ay = a.dir[kCols + col_a], bx = a.dir[col_b], by = a.dir[kCols + col_b];
+  const double dz = a.dir[2 * kCols + lane];
+  double dx[kColsPerWave], dy[kColsPerWave], best[kColsPerWave];
+  int bid[kColsPerWave];
+#pragma unroll
+  for (int q = 0; q < kColsPerWave; ++q) {
+    const int j = j0 + wave * kColsPerWave + q;
+    const int col = (c.first + min(j, c.count - 1)) % kCols;   // (a column past the tile's end runs along on the last one; never stored)
+    dx[q] = a.dir[col]; dy[q] = a.dir[kCols + col];
+    best[q] = INFINITY; bid[q] = -1;
+  }
+  const int L = a.lds_triangles;
+  for (int f0 = 0; f0 < c.nf; f0 += L) {
+    const int fend = min(c.nf, f0 + L);
+    int n = 0;   // triangles staged so far (the same in every thread)
+    for (int r0 = f0; r0 < fend; r0 += kCastThreads) {
+      const int f = r0 + tid;
+      bool keep = false;
+      SceneTri tr;
+      if (f < fend) {
+        const int* fi = a.faces + (c.f0 + f) * 3;
+        const V3 p = pose(c, a.verts + (c.v0 + fi[0]) * 3), q = pose(c, a.verts + (c.v0 + fi[1]) * 3), r = pose(c, a.verts + (c.v0 + fi[2]) * 3);
+        // side of a column's half plane: s = dir_x y - dir_y x = |p| sin(column azimuth - point azimuth) (> 0: the point lies before the column)
+        const double mp = kSideMargin * 120.0 * (fabs(p.x) + fabs(p.y)), mq = kSideMargin * 120.0 * (fabs(q.x) + fabs(q.y)), mr = kSideMargin * 120.0 * (fabs(r.x) + fabs(r.y));
+        const bool before = ax * p.y - ay * p.x > mp && ax * q.y - ay * q.x > mq && ax * r.y - ay * r.x > mr;
+        const bool behind = bx * p.y - by * p.x < -mp && bx * q.y - by * q.x < -mq && bx * r.y - by * r.x < -mr;
+        keep = !before && !behind;
+        if (keep) { tri_setup(p, q, r, tr); tr.id = f; tr.pad = 0; }
+      }
+      const unsigned long long m = __ballot(keep);
+      if (lane == 0) wcnt[wave] = __popcll(m);
+      __syncthreads();
+      int base = n, total = 0;
+#pragma unroll
+      for (int w = 0; w < kCastThreads / 64; ++w) { const int k = wcnt[w]; if (w < wave) base += k; total += k; }
+      if (keep) tris[base + __popcll(m & ((1ull << lane) - 1ull))] = tr;
+      n += total;
+      __syncthreads();
+    }
+    {
+#pragma clang fp contract(off)
+      for (int k = 0; k < n; ++k) {
+        const SceneTri& t = tris[k];   // every lane reads the same address: a broadcast
+        const double N0 = t.N[0], N1 = t.N[1], N2 = t.N[2], A0 = t.A[0], A1 = t.A[1], A2 = t.A[2], B0 = t.Bv[0], B1 = t.Bv[1], B2 = t.Bv[2], cc = t.c;
+        const int id = t.id;
+        const double nz = dz * N2, az = dz * A2, bz = dz * B2;
+#pragma unroll
+        for (int q = 0; q < kColsPerWave; ++q) {
+          const double den = (dx[q] * N0 + dy[q] * N1) + nz;
+          const double un = (dx[q] * A0 + dy[q] * A1) + az;
+          const double vn = (dx[q] * B0 + dy[q] * B1) + bz;
+          const double sum = un + vn;
+          const bool hit = den > 0.0 ? (un >= 0.0 && vn >= 0.0 && sum <= den && cc > 0.0)
+                                     : (den < 0.0 && un <= 0.0 && vn <= 0.0 && sum >= den && cc < 0.0);
+          if (hit) {
+            const double tt = cc / den;
+            if (tt > 0.0 && (tt < best[q] || (tt == best[q] && id < bid[q]))) { best[q] = tt; bid[q] = id; }
+          }
+        }
+      }
+    }
+    __syncthreads();   // the stage is rewritten by the next chunk
+  }
+#pragma unroll
+  for (int q = 0; q < kColsPerWave; ++q) {
+    const int j = j0 + wave * kColsPerWave + q;
+    if (j < j0 + ncol) {
+      const long long o = c.tbase + (long long)lane * c.count + j;
+      a.t[o] = best[q];
+      if constexpr (kTrace) a.tri[o] = bid[q];
+    }
+  }
+}
+
+// ---- stage 3: compaction into ray order + noise ---------------------------------------------------------------------------------------------
+// position k of a window in ascending COLUMN order -> (column, window column)
+__device__ __forceinline__ void ordered_col(const SceneCloud& c, int k, int* col, int* j)
+{
+  const int wrap = max(0, c.first + c.count - kCols);   // columns 0 .. wrap - 1 are the window's tail
+  if (k < wrap) { *col = k; *j = k + kCols - c.first; }
+  else { *col = c.first + (k - wrap); *j = k - wrap; }
+}
+
+// grid (clouds, 64 rows)
+__global__ __launch_bounds__(256) void scene_count_kernel(const SceneCloud* __restrict__ clouds, const double* __restrict__ t, int* __restrict__ rowcount)
+{
+  __shared__ int wsum[4];
+  const SceneCloud c = clouds[blockIdx.x];
+  const double* row = t + c.tbase + (long long)blockIdx.y * c.count;
+  int n = 0;
+  for (int j = threadIdx.x; j < c.count; j += 256) n += row[j] < INFINITY ? 1 : 0;
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) rowcount[blockIdx.x * kRows + blockIdx.y] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// one workgroup of 1024: per cloud index w, the exclusive scan of rowcount in (scene, row) order -> rowoff; offsets [B + 1][2]
+__global__ __launch_bounds__(1024) void scene_scan_kernel(const int* __restrict__ rowcount, long long* __restrict__ rowoff, long long* __restrict__ offsets, int B)
+{
+  __shared__ long long part[1024];
+  const int tid = threadIdx.x;
+  const long long n = (long long)B * kRows, per = (n + 1023) / 1024;
+  for (int w = 0; w < 2; ++w) {
+    const long long lo = min(n, tid * per), hi = min(n, lo + per);
+    long long s = 0;
+    for (long long e = lo; e < hi; ++e) s += rowcount[((e / kRows) * 2 + w) * kRows + e % kRows];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+      long long run = 0;
+      for (int i = 0; i < 1024; ++i) { const long long v = part[i]; part[i] = run; run += v; }
+      offsets[(long long)B * 2 + w] = run;
+    }
+    __syncthreads();
+    long long run = part[tid];
+    for (long long e = lo; e < hi; ++e) {
+      const long long i = ((e / kRows) * 2 + w) * kRows + e % kRows;
+      rowoff[i] = run;
+      if (e % kRows == 0) offsets[(e / kRows) * 2 + w] = run;
+      run += rowcount[i];
+    }
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x)
+{
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
+// grid (clouds, 64 rows)
+__global__ __launch_bounds__(256) void scene_scatter_kernel(const SceneCloud* __restrict__ clouds, const double* __restrict__ t, const double* __restrict__ dir,
+                                                            const long long* __restrict__ rowoff, uint64_t seed, float clip, float* __restrict__ out0,
+                                                            float* __restrict__ out1)
+{
+  __shared__ int wcnt[4];
+  const SceneCloud c = clouds[blockIdx.x];
+  const int r = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double* row = t + c.tbase + (long long)r * c.count;
+  float* out = (c.which ? out1 : out0) + rowoff[blockIdx.x * kRows + r] * 3;
+  const double dz = dir[2 * kCols + r];
+  int done = 0;   // points of this row written so far (the same in every thread)
+  for (int k0 = 0; k0 < c.count; k0 += 256) {
+    const int k = k0 + tid;
+    int col = 0, j = 0;
+    double tt = INFINITY;
+    if (k < c.count) { ordered_col(c, k, &col, &j); tt = row[j]; }
+    const bool hit = tt < INFINITY;
+    const unsigned long long m = __ballot(hit);
+    if (lane == 0) wcnt[wave] = __popcll(m);
+    __syncthreads();
+    int base = done, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { const int n = wcnt[w]; if (w < wave) base += n; total += n; }
+    if (hit) {
+      float v[3] = {(float)(tt * dir[col]), (float)(tt * dir[kCols + col]), (float)(tt * dz)};
+      if (c.strength > 0.f) {
+        // the dataset sampler's stream (alignnet_dataset.hip), keyed by (seed, scene id, cloud, ray index)
+        const uint64_t ray = (uint64_t)r * kCols + (uint64_t)col;
+        const uint64_t key = mix64(seed ^ (c.scene_id * 0x9E3779B97F4A7C15ull) ^ ((2 * ray + (uint64_t)c.which) * 0xD1B54A32D192ED03ull));
+        const uint64_t k2 = mix64(key + 0x632BE59BD9B4E019ull), k3 = mix64(key + 0xC6BC279692B5C323ull);
+        const float u0 = ((float)(k2 >> 40) + 0.5f) * (1.0f / 16777216.0f), u1 = (float)((k2 >> 16) & 0xFFFFFF) * (1.0f / 16777216.0f);
+        const float u2 = ((float)(k3 >> 40) + 0.5f) * (1.0f / 16777216.0f), u3 = (float)((k3 >> 16) & 0xFFFFFF) * (1.0f / 16777216.0f);
+        const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+        const float z0 = r0 * cosf(6.28318530718f * u1), z1 = r0 * sinf(6.28318530718f * u1), z2 = r1 * cosf(6.28318530718f * u3);
+        v[0] += fminf(fmaxf(c.strength * z0, -clip), clip);
+        v[1] += fminf(fmaxf(c.strength * z1, -clip), clip);
+        v[2] += fminf(fmaxf(c.strength * z2, -clip), clip);
+      }
+      float* o = out + (size_t)(base + __popcll(m & ((1ull << lane) - 1ull))) * 3;
+      o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+    }
+    done += total;
+    __syncthreads();
+  }
+}
+
+// ---- host state ------------------------------------------------------------------------------------------------------------------------------
+struct SceneWS {
+  // mesh library (alignnet_scene_upload_meshes)
+  int M = -1;                               // -1: nothing uploaded
+  std::vector<long long> moff;              // [M + 1][2] first vertex / face
+  std::vector<double> centroid;             // [M][3], normalised frame
+  double* d_verts = nullptr; int* d_faces = nullptr;
+  double* d_dir = nullptr;                  // sensor tables
+  // work buffers, grown on demand
+  SceneCloud* d_clouds = nullptr; int* d_win = nullptr; int* d_rowcount = nullptr; long long* d_rowoff = nullptr; size_t cap_clouds = 0;
+  int* d_tiles = nullptr; size_t cap_tiles = 0;
+  double* d_t = nullptr; int* d_tri = nullptr; size_t cap_t = 0, cap_tri = 0;
+  // the last result (alignnet_scene_generate)
+  int B = -1;
+  std::vector<long long> offsets;           // [B + 1][2]
+  long long* d_offsets = nullptr; size_t cap_off = 0;
+  float* d_pts[2] = {nullptr, nullptr}; size_t cap_pts[2] = {0, 0};
+};
+
+SceneWS* sws(alignnet_handle* h) { return static_cast<SceneWS*>(h->scene_ws); }
+
+template <typename T>
+int grow(alignnet_handle* h, T** p, size_t* cap, size_t need)
+{
+  if (need <= *cap && *p) return 0;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (*p) hipFree(*p);
+  *p = nullptr; *cap = 0;
+  HIP_TRY(h, hipMalloc(p, std::max<size_t>(need, 1) * sizeof(T)));
+  *cap = std::max<size_t>(need, 1);
+  return 0;
+}
+
+void default_sensor(std::vector<double>& dir)
+{
+  dir.resize(2 * kCols + kRows);
+  const double vfov = 26.9, hfov = 360.0;
+  for (int c = 0; c < kCols; ++c) {
+    const double hangle = -hfov / 2.0 + hfov / kCols * c;
+    dir[c] = std::sin(hangle / 180. * M_PI) * 120.0; dir[kCols + c] = std::cos(hangle / 180. * M_PI) * 120.0;
+  }
+  for (int r = 0; r < kRows; ++r) dir[2 * kCols + r] = std::tan((-vfov / 2.0 + vfov / (kRows - 1) * r) / 180. * M_PI) * 120.0;
+}
+
+int ensure_ws(alignnet_handle* h)
+{
+  if (h->scene_ws) return 0;
+  SceneWS* w = new SceneWS();
+  h->scene_ws = w;
+  std::vector<double> dir;
+  default_sensor(dir);
+  HIP_TRY(h, hipMalloc(&w->d_dir, dir.size() * sizeof(double)));
+  HIP_TRY(h, hipMemcpy(w->d_dir, dir.data(), dir.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+struct SceneTrace { int lds_triangles; double* t; int32_t* triangle; int32_t* window; int32_t* lds_triangles_used; };
+
+// B scenes x 2 clouds (or, traced: ONE cloud, pose [4]); results stay on the device
+int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const double* scale, const double* poses, const int64_t* scene_ids, int nclouds,
+              uint64_t seed, double sigma, double clip, const SceneTrace* trace)
+{
+  const std::string name(fn);
+  SceneWS* w = sws(h);
+  const int B = trace ? 1 : nclouds / 2, per = trace ? 1 : 2;
+  std::vector<SceneCloud> cl((size_t)nclouds);
+  for (int i = 0; i < nclouds; ++i) {
+    const int b = i / per;
+    if (mesh[b] < 0 || mesh[b] >= w->M) return fail(h, name + ": mesh " + std::to_string(mesh[b]) + " out of range");
+    if (!std::isfinite(scale[b])) return fail(h, name + ": non-finite scale");
+    const double* p = poses + (size_t)i * 4;
+    for (int k = 0; k < 4; ++k) if (!std::isfinite(p[k])) return fail(h, name + ": non-finite pose");
+    SceneCloud& c = cl[i];
+    std::memset(&c, 0, sizeof(c));
+    c.cs = std::cos(p[3]); c.sn = std::sin(p[3]); c.scale = scale[b]; c.px = p[0]; c.py = p[1]; c.pz = p[2];
+    c.v0 = w->moff[(size_t)mesh[b] * 2]; c.f0 = w->moff[(size_t)mesh[b] * 2 + 1];
+    c.nf = (int)(w->moff[(size_t)(mesh[b] + 1) * 2 + 1] - c.f0);
+    c.scene_id = scene_ids ? (unsigned long long)scene_ids[b] : (unsigned long long)b;
+    c.which = trace ? 0 : i % 2;
+    if (sigma > 0.0) {
+      // mesh.centroid of the posed mesh (area-weighted; a similarity keeps the weights): max(0.005, sigma |centroid| / 80), pointcloud.py:1134
+      const double* g = &w->centroid[(size_t)mesh[b] * 3];
+      const double sx = c.scale * g[0], sy = c.scale * g[1], sz = c.scale * g[2];
+      const double x = (c.cs * sx - c.sn * sy) + c.px, y = (c.sn * sx + c.cs * sy) + c.py, z = sz + c.pz;
+      c.strength = (float)std::max(0.005, sigma * std::sqrt(x * x + y * y + z * z) / 80.);
+    }
+  }
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  const size_t nc = (size_t)std::max(nclouds, 1);
+  if (nc > w->cap_clouds || !w->d_clouds) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (w->d_clouds) { hipFree(w->d_clouds); hipFree(w->d_win); hipFree(w->d_rowcount); hipFree(w->d_rowoff); }
+    w->d_clouds = nullptr; w->cap_clouds = 0;
+    HIP_TRY(h, hipMalloc(&w->d_clouds, nc * sizeof(SceneCloud)));
+    HIP_TRY(h, hipMalloc(&w->d_win, nc * 2 * sizeof(int)));
+    HIP_TRY(h, hipMalloc(&w->d_rowcount, nc * kRows * sizeof(int)));
+    HIP_TRY(h, hipMalloc(&w->d_rowoff, nc * kRows * sizeof(long long)));
+    w->cap_clouds = nc;
+  }
+  if (grow(h, &w->d_offsets, &w->cap_off, (size_t)(B + 1) * 2)) return 1;
+  w->B = -1;   // no result until this call has finished
+  w->offsets.assign((size_t)(B + 1) * 2, 0);
+  std::vector<int> win((size_t)nclouds * 2, 0), tiles;
+  if (nclouds > 0) {
+    HIP_TRY(h, hipMemcpyAsync(w->d_clouds, cl.data(), cl.size() * sizeof(SceneCloud), hipMemcpyHostToDevice, h->stream));
+    {
+      alignnet::ProfScope prof_scope(h, alignnet::PK_SCENE_WINDOW);
+      hipLaunchKernelGGL(scene_window_kernel, dim3(nclouds), dim3(256), 0, h->stream, w->d_clouds, w->d_verts, w->d_faces, w->d_win);
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(win.data(), w->d_win, win.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+  }
+  // deal the work: (cloud, tile of the window); the t tables and the point blobs are sized by the windows
+  size_t nt = 0, npts[2] = {0, 0};
+  for (int i = 0; i < nclouds; ++i) {
+    SceneCloud& c = cl[i];
+    c.first = win[(size_t)i * 2]; c.count = win[(size_t)i * 2 + 1];
+    if (c.first < 0 || c.first >= kCols || c.count < 0 || c.count > kCols) return fail(h, name + ": window out of range (internal)");
+    c.tbase = (long long)nt;
+    nt += (size_t)c.count * kRows;
+    npts[c.which] += (size_t)c.count * kRows;
+    for (int k = 0; k * kTileCols < c.count; ++k) { tiles.push_back(i); tiles.push_back(k); }
+  }
+  if (grow(h, &w->d_t, &w->cap_t, nt)) return 1;
+  if (trace && grow(h, &w->d_tri, &w->cap_tri, nt)) return 1;
+  if (grow(h, &w->d_tiles, &w->cap_tiles, tiles.size())) return 1;
+  for (int k = 0; k < 2; ++k) if (grow(h, &w->d_pts[k], &w->cap_pts[k], npts[k] * 3)) return 1;
+  int L = kLdsTriangles;
+  if (trace && trace->lds_triangles > 0) L = trace->lds_triangles;
+  if (nclouds > 0) {
+    HIP_TRY(h, hipMemcpyAsync(w->d_clouds, cl.data(), cl.size() * sizeof(SceneCloud), hipMemcpyHostToDevice, h->stream));
+    if (!tiles.empty()) {
+      HIP_TRY(h, hipMemcpyAsync(w->d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      SceneCastArgs a;
+      a.clouds = w->d_clouds; a.tiles = w->d_tiles; a.verts = w->d_verts; a.faces = w->d_faces; a.dir = w->d_dir; a.t = w->d_t; a.tri = w->d_tri;
+      a.lds_triangles = L;
+      const size_t lds = (size_t)L * sizeof(SceneTri);
+      alignnet::ProfScope prof_scope(h, alignnet::PK_SCENE_CAST);
+      if (trace)
+        hipLaunchKernelGGL(scene_cast_kernel<true>, dim3((unsigned)(tiles.size() / 2)), dim3(kCastThreads), lds, h->stream, a);
+      else
+        hipLaunchKernelGGL(scene_cast_kernel<false>, dim3((unsigned)(tiles.size() / 2)), dim3(kCastThreads), lds, h->stream, a);
+    }
+    HIP_TRY(h, hipGetLastError());
+  }
+  if (trace) {
+    // the record: t and triangle per ray of the window, laid out by ray index on the host
+    std::vector<double> t(nt); std::vector<int> tri(nt);
+    if (nt) {
+      HIP_TRY(h, hipMemcpyAsync(t.data(), w->d_t, nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(tri.data(), w->d_tri, nt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < kRays; ++i) { trace->t[i] = std::numeric_limits<double>::infinity(); trace->triangle[i] = -1; }
+    const SceneCloud& c = cl[0];
+    for (int r = 0; r < kRows; ++r)
+      for (int j = 0; j < c.count; ++j) {
+        const size_t ray = (size_t)r * kCols + (size_t)((c.first + j) % kCols), o = (size_t)r * c.count + j;
+        trace->t[ray] = t[o]; trace->triangle[ray] = tri[o];
+      }
+    trace->window[0] = c.first; trace->window[1] = c.count;
+    *trace->lds_triangles_used = L;
+    return 0;
+  }
+  if (nclouds > 0) {
+    alignnet::ProfScope prof_scope(h, alignnet::PK_SCENE_COMPACT);
+    hipLaunchKernelGGL(scene_count_kernel, dim3(nclouds, kRows), dim3(256), 0, h->stream, w->d_clouds, w->d_t, w->d_rowcount);
+    hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(1024), 0, h->stream, w->d_rowcount, w->d_rowoff, w->d_offsets, B);
+    hipLaunchKernelGGL(scene_scatter_kernel, dim3(nclouds, kRows), dim3(256), 0, h->stream, w->d_clouds, w->d_t, w->d_dir, w->d_rowoff, seed, (float)clip,
+                       w->d_pts[0], w->d_pts[1]);
+  }
+  HIP_TRY(h, hipGetLastError());
+  if (nclouds > 0)
+    HIP_TRY(h, hipMemcpyAsync(w->offsets.data(), w->d_offsets, w->offsets.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  w->B = B;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" void alignnet_scene_free(alignnet_handle* h)
+{
+  if (!h || !h->scene_ws) return;
+  SceneWS* w = sws(h);
+  if (h->stream) hipStreamSynchronize(h->stream);
+  void* const ptrs[] = {w->d_verts, w->d_faces, w->d_dir, w->d_clouds, w->d_win, w->d_rowcount, w->d_rowoff, w->d_tiles, w->d_t, w->d_tri, w->d_offsets,
+                        w->d_pts[0], w->d_pts[1]};
+  for (void* p : ptrs) if (p) hipFree(p);
+  delete w;
+  h->scene_ws = nullptr;
+}
+
+extern "C" int alignnet_scene_set_sensor(alignnet_handle* h, const double* dir_x, const double* dir_y, const double* dir_z)
+{
+  if (!h) return 1;
+  if (!dir_x || !dir_y || !dir_z) return fail(h, "alignnet_scene_set_sensor: null table");
+  for (int c = 0; c < kCols; ++c) if (!std::isfinite(dir_x[c]) || !std::isfinite(dir_y[c])) return fail(h, "alignnet_scene_set_sensor: non-finite direction");
+  for (int r = 0; r < kRows; ++r) if (!std::isfinite(dir_z[r])) return fail(h, "alignnet_scene_set_sensor: non-finite direction");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  if (ensure_ws(h)) return 1;
+  SceneWS* w = sws(h);
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(w->d_dir, dir_x, kCols * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(w->d_dir + kCols, dir_y, kCols * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(w->d_dir + 2 * kCols, dir_z, kRows * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+extern "C" int alignnet_scene_free_meshes(alignnet_handle* h)
+{
+  if (!h) return 1;
+  if (!h->scene_ws) return 0;
+  SceneWS* w = sws(h);
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (w->d_verts) hipFree(w->d_verts);
+  if (w->d_faces) hipFree(w->d_faces);
+  w->d_verts = nullptr; w->d_faces = nullptr; w->M = -1; w->moff.clear(); w->centroid.clear();
+  return 0;
+}
+
+extern "C" int alignnet_scene_upload_meshes(alignnet_handle* h, const double* vertices, const int32_t* faces, const int64_t* offsets, const double* centroids,
+                                            int32_t M)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_scene_upload_meshes");
+  if (M < 0 || !offsets || (M > 0 && !centroids)) return fail(h, name + ": M < 0 or a null table");
+  if (offsets[0] != 0 || offsets[1] != 0) return fail(h, name + ": offsets must start at 0");
+  for (int m = 0; m < M; ++m) {
+    const int64_t nv = offsets[(m + 1) * 2] - offsets[m * 2], nf = offsets[(m + 1) * 2 + 1] - offsets[m * 2 + 1];
+    if (nv < 0 || nf < 0) return fail(h, name + ": offsets must be non-decreasing");
+    if (nv > 0x7fffffff || nf > 0x7fffffff / 3) return fail(h, name + ": mesh " + std::to_string(m) + " too large");
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(centroids[m * 3 + k])) return fail(h, name + ": non-finite centroid of mesh " + std::to_string(m));
+  }
+  const size_t nv = (size_t)offsets[(size_t)M * 2], nf = (size_t)offsets[(size_t)M * 2 + 1];
+  if ((nv && !vertices) || (nf && !faces)) return fail(h, name + ": null vertices / faces");
+  for (size_t i = 0; i < nv * 3; ++i) if (!std::isfinite(vertices[i])) return fail(h, name + ": non-finite vertex " + std::to_string(i / 3));
+  for (int m = 0; m < M; ++m) {
+    const int64_t mv = offsets[(m + 1) * 2] - offsets[m * 2];
+    for (int64_t f = offsets[m * 2 + 1] * 3; f < offsets[(m + 1) * 2 + 1] * 3; ++f)
+      if (faces[f] < 0 || faces[f] >= mv)
+        return fail(h, name + ": face " + std::to_string(f / 3 - offsets[m * 2 + 1]) + " of mesh " + std::to_string(m) + " names vertex " + std::to_string(faces[f]) +
+                           " (the mesh has " + std::to_string(mv) + ")");
+  }
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  if (ensure_ws(h)) return 1;
+  if (alignnet_scene_free_meshes(h)) return 1;
+  SceneWS* w = sws(h);
+  HIP_TRY(h, hipMalloc(&w->d_verts, std::max<size_t>(nv, 1) * 3 * sizeof(double)));
+  HIP_TRY(h, hipMalloc(&w->d_faces, std::max<size_t>(nf, 1) * 3 * sizeof(int)));
+  if (nv) HIP_TRY(h, hipMemcpy(w->d_verts, vertices, nv * 3 * sizeof(double), hipMemcpyHostToDevice));
+  if (nf) HIP_TRY(h, hipMemcpy(w->d_faces, faces, nf * 3 * sizeof(int), hipMemcpyHostToDevice));
+  w->moff.assign(offsets, offsets + (size_t)(M + 1) * 2);
+  w->centroid.assign(centroids, centroids + (size_t)M * 3);
+  w->M = M;
+  w->B = -1;
+  return 0;
+}
+
+extern "C" int alignnet_scene_generate(alignnet_handle* h, const int32_t* mesh, const double* scale, const double* poses, const int64_t* scene_ids, int32_t B,
+                                       uint64_t seed, double sigma, double clip, int64_t* offsets)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_scene_generate");
+  if (!h->scene_ws || sws(h)->M < 0) return fail(h, name + ": no meshes uploaded");
+  if (B < 0 || B > (1 << 20)) return fail(h, name + ": B out of range");
+  if (B > 0 && (!mesh || !scale || !poses)) return fail(h, name + ": null argument");
+  if (!std::isfinite(sigma) || (sigma > 0.0 && !(clip > 0.0 && std::isfinite(clip)))) return fail(h, name + ": sigma must be finite, clip > 0 with noise on");
+  if (run_scene(h, name.c_str(), mesh, scale, poses, scene_ids, 2 * B, seed, sigma, clip, nullptr)) return 1;
+  if (offsets) for (size_t i = 0; i < sws(h)->offsets.size(); ++i) offsets[i] = sws(h)->offsets[i];
+  return 0;
+}
+
+extern "C" int alignnet_scene_read(alignnet_handle* h, float* points1, float* points2)
+{
+  if (!h) return 1;
+  if (!h->scene_ws || sws(h)->B < 0) return fail(h, "alignnet_scene_read: nothing generated yet");
+  SceneWS* w = sws(h);
+  float* const dst[2] = {points1, points2};
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  for (int k = 0; k < 2; ++k) {
+    const size_t n = (size_t)w->offsets[(size_t)w->B * 2 + k];
+    if (n && dst[k]) HIP_TRY(h, hipMemcpyAsync(dst[k], w->d_pts[k], n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int alignnet_scene_install_dataset(alignnet_handle* h, const float* labels)
+{
+  if (!h) return 1;
+  if (!h->scene_ws || sws(h)->B < 0) return fail(h, "alignnet_scene_install_dataset: nothing generated yet");
+  SceneWS* w = sws(h);
+  if (w->B < 1 || !labels) return fail(h, "alignnet_scene_install_dataset: no scenes or null labels");
+  static_assert(sizeof(long long) == sizeof(int64_t), "offsets");
+  return alignnet_dataset_install(h, w->d_pts[0], w->d_pts[1], true, reinterpret_cast<const int64_t*>(w->offsets.data()), labels, w->B,
+                                  "alignnet_scene_install_dataset");
+}
+
+extern "C" int alignnet_debug_scene_cast(alignnet_handle* h, int32_t mesh, double scale, const double* pose, int32_t lds_triangles, double* t, int32_t* triangle,
+                                         int32_t* window, int32_t* lds_triangles_used)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_debug_scene_cast");
+  if (!h->scene_ws || sws(h)->M < 0) return fail(h, name + ": no meshes uploaded");
+  if (!pose || !t || !triangle || !window || !lds_triangles_used) return fail(h, name + ": null argument");
+  if (lds_triangles < 0 || lds_triangles > kLdsTriangles)
+    return fail(h, name + ": lds_triangles must be in [0, " + std::to_string(kLdsTriangles) + "] (0 = as shipped)");
+  const SceneTrace tr = {lds_triangles, t, triangle, window, lds_triangles_used};
+  return run_scene(h, name.c_str(), &mesh, &scale, pose, nullptr, 1, 0, 0.0, 0.0, &tr);
+}

@@ -37,9 +37,9 @@ struct Stack { int first, n; };   // range of layers
 // Kernels whose launches are bracketed with HIP events on the handle's stream while profiling is enabled
 // (alignnet_profile_enable; read back by name through alignnet_profile_read_kernel -- bench.py's roofline legs).
 enum ProfKernel { PK_BACKBONE = 0, PK_KNN, PK_TRAIN_PHASE2, PK_TRAIN_PHASE3, PK_TRAIN_GRAM, PK_TRAIN_B2, PK_TRAIN_B1, PK_DG_FWD, PK_DG_BWD_EDGE,
-                  PK_ALLREDUCE, PK_OPTIMIZER, PK_COUNT };
+                  PK_ALLREDUCE, PK_OPTIMIZER, PK_SCENE_WINDOW, PK_SCENE_CAST, PK_SCENE_COMPACT, PK_COUNT };
 static const char* const kProfKernelNames[PK_COUNT] = {"backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2",
-                                                       "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer"};
+                                                       "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact"};
 
 struct Workspace {
   int cap = 0;                     // pairs
@@ -86,6 +86,9 @@ static const struct { const char* key; unsigned bit; } kAbKeys[] = {
   {"ab_dg_sparse", AB_DG_SPARSE}, {"ab_no_glue_fold", AB_NO_GLUE_FOLD}, {"ab_gemm_jobs_ksplit", AB_GEMM_JOBS_KSPLIT}, {"ab_fc_direct", AB_FC_DIRECT}, {"ab_fc_no_splitk", AB_FC_NO_SPLITK}, {"ab_split_tilewise", AB_SPLIT_TILEWISE}};
 struct alignnet_handle;
 bool alignnet_dataset_tables(alignnet_handle* h, alignnet::DatasetTables* out);   // alignnet_dataset.hip; false when none uploaded
+// alignnet_dataset.hip: what alignnet_dataset_upload does, the point blobs read from host or (device_points) from device memory; `fn` names the caller in messages
+int alignnet_dataset_install(alignnet_handle* h, const float* points1, const float* points2, bool device_points, const int64_t* offsets, const float* labels,
+                             int64_t n_examples, const char* fn);
 int alignnet_drain_profile(alignnet_handle* h);
 // options that live with the training / communicator code (alignnet_train.hip); -1 = not one of its keys
 int alignnet_train_set_option(alignnet_handle* h, const std::string& key, int64_t value);
@@ -137,6 +140,7 @@ struct alignnet_handle {
   void* dataset_ws = nullptr;      // HBM-resident dataset + batch buffers (alignnet_dataset.hip)
   void* globalreg_ws = nullptr;    // stage arrays of the global registration (alignnet_globalreg.hip), grown on demand
   size_t globalreg_ws_bytes = 0;
+  void* scene_ws = nullptr;        // mesh library, work buffers and the last result of the scene generator (alignnet_scene.hip)
   void* pipe = nullptr;            // pipelined host path: two staging slots, copy streams, events (alignnet_api.hip: alignnet_forward_submit / _wait)
   // seed base of the device-side dropout stream at the current step counter (alignnet_train.hip: bn_args, dropout_uniforms_kernel)
   uint64_t dropout_seed_base() const { return (cfg.seed + dropout_stream * 0xD1B54A32D192ED03ull) * 0x9E3779B97F4A7C15ull + (uint64_t)step * 16; }

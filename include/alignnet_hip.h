@@ -415,6 +415,47 @@ int alignnet_debug_fgr_stages(alignnet_handle* h, const float* points1, int64_t 
                               double* out_T, double* out_fitness, double* out_rmse, int32_t* out_correspondences,
                               int64_t* out_trials);
 
+/* ---- spinning-LiDAR scene generator (the SynthCars-style datasets, tp_utils/pointcloud.py:945-971,1055-1186) -------
+ * A 64 x 4500-ray sensor at the origin (ray index = row * 4500 + column, direction 120 (sin h, cos h, tan v), vfov 26.9
+ * degrees, 360 degrees around) is cast against a triangle mesh at two poses per scene; the first hit of every ray is kept
+ * in ascending ray index and clipped range-dependent noise is added (SyntheticScene.generate_pointcloud_embree).  trimesh
+ * and embree are not available: the computation is DEFINED by tests/scene_ref.py (fp64: hit or miss and the smallest
+ * t > 0 are decided in double precision; triangles are two-sided, zero-area triangles never hit).  The noise is
+ * clip(strength z, +-clip) added in float32 to float32(t d), strength = max(0.005, sigma |centroid| / 80) with the
+ * area-weighted centroid of the posed mesh, z standard normal from the dataset sampler's counter hash keyed by (seed,
+ * scene id, cloud, ray index): a result never depends on the batch it was generated in, and it is NOT
+ * np.random.randn's stream (parity unpinned by construction).
+ * alignnet_scene_set_sensor: the direction tables (dir_x, dir_y [4500] = 120 sin h, 120 cos h; dir_z [64] = 120 tan v)
+ *   as the caller computed them, so that device and caller cast the same rays bit for bit; without it the library's own
+ *   evaluation of the same formulas is used.
+ * alignnet_scene_upload_meshes: a library of M meshes: vertices [sum nv][3] (normalised as Mesh.__init__ does: bounds
+ *   midpoint at 0, longest half extent 0.5), faces [sum nf][3] indices into the mesh's own vertices, offsets [M + 1][2]
+ *   = first vertex / first face of every mesh, centroids [M][3] the area-weighted centroid of every (normalised) mesh.
+ *   Everything is copied, nothing retained.  A face index out of range, a non-finite number or decreasing offsets fail.
+ * alignnet_scene_generate: B >= 0 scenes; mesh [B] library index, scale [B] mesh_scale, poses [B][2][4] = x y z angle of
+ *   the two clouds (world vertex = Rz(angle) (scale v) + position), scene_ids [B] (NULL = 0 .. B - 1) for the noise key.
+ *   sigma <= 0: no noise.  The clouds stay on the device; offsets [B + 1][2] (may be NULL) receives the row offsets of
+ *   the two point blobs in the layout of alignnet_dataset_upload / alignnet_icp_register.
+ * alignnet_scene_read: copies the blobs of the last alignnet_scene_generate out (points1 / points2 [offsets[B][k]][3]).
+ * alignnet_scene_install_dataset: makes the last result the HBM-resident dataset (device to device), labels [B][12] as
+ *   for alignnet_dataset_upload; alignnet_dataset_sample, alignnet_train_step_dataset, alignnet_icp_register_dataset,
+ *   alignnet_global_register_dataset and alignnet_fgr_register_dataset then work on it.
+ * alignnet_debug_scene_cast (test hook, outside the stable surface): ONE cloud (pose [4]) by the shipped cast kernel
+ *   with a record behind it, no noise: t [288000] per ray index (inf = miss), triangle [288000] the face hit (-1),
+ *   window [2] = first column and number of columns of the azimuth window that was cast (it may wrap 4499 -> 0),
+ *   lds_triangles: triangles per LDS chunk, 0 = as shipped (512), 1 .. 512 forces several chunks on small meshes;
+ *   lds_triangles_used [1].  It discards the result of an earlier alignnet_scene_generate. */
+int alignnet_scene_set_sensor(alignnet_handle* h, const double* dir_x, const double* dir_y, const double* dir_z);
+int alignnet_scene_upload_meshes(alignnet_handle* h, const double* vertices, const int32_t* faces, const int64_t* offsets,
+                                 const double* centroids, int32_t M);
+int alignnet_scene_free_meshes(alignnet_handle* h);
+int alignnet_scene_generate(alignnet_handle* h, const int32_t* mesh, const double* scale, const double* poses,
+                            const int64_t* scene_ids, int32_t B, uint64_t seed, double sigma, double clip, int64_t* offsets);
+int alignnet_scene_read(alignnet_handle* h, float* points1, float* points2);
+int alignnet_scene_install_dataset(alignnet_handle* h, const float* labels);
+int alignnet_debug_scene_cast(alignnet_handle* h, int32_t mesh, double scale, const double* pose, int32_t lds_triangles,
+                              double* t, int32_t* triangle, int32_t* window, int32_t* lds_triangles_used);
+
 /* ---- run-time options with no counterpart in the reference's config surface --------
  * "train_matmul_bf16" (0/1, default 0): training only -- the two MFMA convs of every backbone (the hidden 1x1 conv
  *   and the -> C3 feature lift, 96 % of the step's FLOPs, models/tp8.py:55-57), in the forward and in the backward's
@@ -502,7 +543,8 @@ int alignnet_profile_read(alignnet_handle* h, double* backbone_ms, int64_t* back
 /* HIP-event time (ms, summed) and launch count of one timed kernel since the last reset (alignnet_profile_read(..., reset = 1)), measured
  * on the stream it is launched on while profiling is enabled.  name: "backbone" (eval-mode fused backbone), "knn",
  * "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge",
- * "allreduce" (what the compute stream waits for), "optimizer". */
+ * "allreduce" (what the compute stream waits for), "optimizer", and the stages of alignnet_scene_generate: "scene_window" (azimuth windows),
+ * "scene_cast", "scene_compact" (counts, scan, scatter + noise). */
 int alignnet_profile_read_kernel(alignnet_handle* h, const char* name, double* ms, int64_t* launches);
 
 #ifdef __cplusplus
