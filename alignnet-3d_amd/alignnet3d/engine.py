@@ -411,6 +411,25 @@ class Engine:
         return dict(index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1, lanes=np.stack([(paths >> (2 * s)) & 3 for s in range(4)], -1),
                     tail_won=(paths & 256) != 0, lds_points=int(used[0]), fitness=float(fit[0]), rmse=float(rmse[0]))
 
+    def debug_icp_grid(self, source, target, T, radius=0.1, constrained=True):
+        """Test hook: the grid build and ONE evaluation (correspondence step at the 4x4 `T`) of one pair by the ICP kernel's grid search
+        (set_option("icp_search", 1) selects it for icp_refine*; this read-back takes it whatever the option says).  Returns dict(index [n1]
+        chosen target's original index, -1 without a candidate; dist2 [n1] fp64 squared distance, inf without; inlier [n1] bool; candidates
+        [n1] records evaluated; cell_edge; buckets_occupied; largest_bucket; fitness; rmse)."""
+        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+        Tm = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+        n = max(len(p1), 1)
+        idx, d2, inl, cand = np.full(n, -1, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        edge, occ, big, fit, rmse = np.zeros(1, np.float64), np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.float64), np.zeros(1, np.float64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.alignnet_debug_icp_grid(self._h, _fp(p1), len(p1), _fp(p2), len(p2), dp(Tm), float(radius),
+                                                      0 if constrained else ICP_FULL_ROTATION, ip(idx), dp(d2), ip(inl), ip(cand), dp(edge), ip(occ), ip(big),
+                                                      dp(fit), dp(rmse)))
+        n1 = len(p1)
+        return dict(index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1, candidates=cand[:n1].copy(), cell_edge=float(edge[0]),
+                    buckets_occupied=int(occ[0]), largest_bucket=int(big[0]), fitness=float(fit[0]), rmse=float(rmse[0]))
+
     # ---- global registration: RANSAC on FPFH feature matches (csrc/alignnet_globalreg.hip) ----
     @staticmethod
     def _global_bufs(B, streams, default_streams):
@@ -801,7 +820,8 @@ class Engine:
         self._check(self._lib.alignnet_profile_enable(self._h, int(on)))
 
     PROFILED_KERNELS = ("backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1",
-                        "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact")
+                        "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact",
+                        "icp_grid_build", "icp_grid")
 
     def profile_kernels(self):
         """{kernel: (ms, launches)} accumulated since the last profile_read(reset=True); call BEFORE that reset."""

@@ -197,6 +197,7 @@ extern "C" int alignnet_dataset_free(alignnet_handle* h);
 extern "C" void alignnet_comm_free(alignnet_handle* h);
 extern "C" void alignnet_globalreg_free(alignnet_handle* h);
 extern "C" void alignnet_scene_free(alignnet_handle* h);
+extern "C" void alignnet_icp_free(alignnet_handle* h);
 
 namespace { void pipe_free(alignnet_handle* h); hipStream_t pipe_stream(alignnet_handle* h, int which); }   // pipelined host path, defined with alignnet_forward_submit below
 
@@ -210,6 +211,7 @@ extern "C" void alignnet_destroy(alignnet_handle* h)
   alignnet_dataset_free(h);
   alignnet_globalreg_free(h);
   alignnet_scene_free(h);
+  alignnet_icp_free(h);
   pipe_free(h);
   free_ws(h);
   for (auto& pr : h->prof_pending) { hipEventDestroy(pr.a); hipEventDestroy(pr.b); }
@@ -988,6 +990,7 @@ extern "C" int alignnet_set_option(alignnet_handle* h, const char* key, int64_t 
   if (k == "infer_tile_points") { if (value != 0 && value != 64 && value != 128) return fail(h, "infer_tile_points must be 0 (automatic), 64 or 128"); h->infer_tile_opt = (int)value; return 0; }
   if (k == "dg_cloud_parts") { if (value < 0 || value > 8) return fail(h, "dg_cloud_parts must be 0 (automatic) .. 8"); h->dg_parts_opt = (int)value; return 0; }
   if (k == "pn_cloud_parts") { if (value < 0 || value > 8) return fail(h, "pn_cloud_parts must be 0 (automatic) .. 8"); h->pn_parts_opt = (int)value; return 0; }
+  if (k == "icp_search") { if (value < 0 || value > 2) return fail(h, "icp_search must be 0 (scan), 1 (grid) or 2 (automatic)"); h->icp_search = (int)value; return 0; }
   for (const auto& ak : kAbKeys)
     if (k == ak.key) {
       const unsigned before = h->ab;
@@ -1024,6 +1027,8 @@ extern "C" int alignnet_get_option(alignnet_handle* h, const char* key, int64_t*
   if (k == "dg_cloud_parts") { *value = h->dg_parts_opt; return 0; }
   if (k == "infer_tile_points") { *value = h->infer_tile_opt; return 0; }
   if (k == "pn_cloud_parts") { *value = h->pn_parts_opt; return 0; }
+  if (k == "icp_search") { *value = h->icp_search; return 0; }
+  if (k == "icp_grid_ws_bytes") { *value = (int64_t)h->icp_grid_ws_used; return 0; }
   if (k == "ab_mask") { *value = h->ab; return 0; }
   for (const auto& ak : kAbKeys) if (k == ak.key) { *value = (h->ab & ak.bit) ? 1 : 0; return 0; }
   if (k == "comm_buckets") { *value = h->comm_buckets; return 0; }

@@ -17,6 +17,7 @@ namespace {
 struct DatasetWS {
   float* pts[2] = {nullptr, nullptr};
   long long* off = nullptr;      // [n + 1][2]
+  std::vector<long long> h_off;  // the same table on the host (the ICP grid search sizes its workspace per pair)
   float* labels = nullptr;       // [n][12]
   long long n = 0;
   int cap = 0;                   // pairs the batch buffers hold
@@ -121,7 +122,7 @@ bool alignnet_dataset_tables(alignnet_handle* h, alignnet::DatasetTables* out)
 {
   if (!h || !h->dataset_ws) return false;
   DatasetWS* w = dws(h);
-  out->pts[0] = w->pts[0]; out->pts[1] = w->pts[1]; out->off = w->off; out->n = w->n;
+  out->pts[0] = w->pts[0]; out->pts[1] = w->pts[1]; out->off = w->off; out->n = w->n; out->h_off = w->h_off.data();
   return true;
 }
 
@@ -166,6 +167,7 @@ int alignnet_dataset_install(alignnet_handle* h, const float* points1, const flo
   HIP_TRY(h, hipMemcpy(w->off, offsets, (size_t)(n_examples + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice));
   HIP_TRY(h, hipMalloc(&w->labels, (size_t)n_examples * 12 * sizeof(float)));
   HIP_TRY(h, hipMemcpy(w->labels, labels, (size_t)n_examples * 12 * sizeof(float), hipMemcpyHostToDevice));
+  w->h_off.assign(offsets, offsets + (size_t)(n_examples + 1) * 2);
   w->n = n_examples;
   return 0;
 }

@@ -9,8 +9,10 @@
 // One workgroup per pair, all arithmetic in fp64 (Open3D computes in double; nearest-neighbour decisions then agree
 // with the oracle).  The target cloud sits in LDS as doubles (structure of arrays: no conversion in the inner loop),
 // the source cloud is re-read from HBM/L2 each iteration (a few thousand points).  Brute force n1 x n2 per
-// iteration: at the datasets' cloud sizes that is a few million distance evaluations per pair -- a KD-tree would be
-// slower to build than this is to run.
+// iteration: at the cloud sizes this scan was built for (about 1,500 points: a few million distance evaluations per pair, every target in the LDS
+// stage) a search structure would be slower to build than this is to run.  That stops holding where the scan leaves its LDS stage (4266 targets:
+// everything beyond is an all-fp64 walk from L2, in every iteration, for every source point) -- the scene generator's clouds have 2,000 to 58,600
+// points -- and there the GRID search below takes over when alignnet_set_option "icp_search" asks for it (1: every pair, 2: pairs above that size).
 // Round 6: sixteen waves per pair instead of four, and FOUR LANES PER SOURCE POINT (lane s of a quad scans targets s, s + 4, ...; the
 // quad's (distance, index) minima meet in two shuffles, equal distances going to the lower index = the oracle's argmin): 256 pairs x 256
 // threads put one wave on every SIMD and 1500 points on 256 threads (six rounds of a serial 1500-long scan each); now a CU holds four
@@ -28,7 +30,9 @@
 // distances, all about the same pivot), then the 3x3 Umeyama rotation in fp64 on one lane (icp_umeyama_rotation: one-sided Jacobi SVD).
 #include "engine.h"
 #include "icp_estimate.h"
+#include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -78,6 +82,58 @@ struct IcpArgs {
   int* tr_index; double* tr_dist; int* tr_inlier; int* tr_paths;
 };
 
+// ---- grid search (alignnet_set_option "icp_search"): a fixed-radius nearest-neighbour search on a uniform grid --------------------------------------
+// ICP accepts a correspondence only within `radius`, so the nearest target that can count lies in the 27 cells around the query's cell when cells are
+// at least one radius wide.  Per pair, once per call (icp_grid_build_kernel): the targets are bucket-sorted by hashed cell (count, exclusive scan,
+// scatter) into float4 (x, y, z, original index) records behind a table of bucket starts -- H = icp_grid_buckets(n2) <= 32768 buckets whatever the
+// cloud's extent (a hash of the integer cell coordinates, not a dense box: O(n2) memory; two cells in one bucket only ADD candidates).  The ICP
+// kernel (icp_kernel<kFull, kTrace, true>) holds the table in LDS and reads the records from L2; ONE lane per source point walks the buckets of its 27
+// cells and evaluates every record in fp64 exactly as the scan's fp64 step does, keeping the smallest (distance, original index) pair -- a minimum over
+// a set, so neither the order inside a bucket (the scatter's atomics) nor visiting a bucket twice (two of the 27 cells hashing alike) can change it.
+//
+// Cell edge e = max(radius (1 + 2^-20), (M + radius) 2^-20), M = max |target coordinate| of the pair; cell(x) = clamp(floor(x / e), +-2^30), all fp64.
+// Claim: a target the kernel accepts (fp64 distance d <= r2 = fl(radius^2)) differs from the query by at most one cell per axis.  With u = 2^-53: the
+// three differences, squares and sums round d by <= 5 u d, r2 by u, so per axis |p - q| <= radius (1 + 4 u); both coordinates are <= M + radius (1 + 4 u)
+// in magnitude, and each quotient x / e rounds once: the two computed quotients differ by <= [radius (1 + 4 u) + 2 u (M + 2 radius)] / e.  Where
+// e = radius (1 + 2^-20) >= (M + radius) 2^-20, M <= 2^20 radius and the bracket is <= radius (1 + 4 u + 2^-32 + 2^-51) < e.  Where e = (M + radius) 2^-20
+// > radius (1 + 2^-20): radius (1 + 4 u) < e (1 - 2^-21) and 2 u (M + 2 radius) <= 4 u 2^20 e = 2^-31 e, together < e.  (The roundings of e itself, 2 u,
+// sit inside the 2^-21 of slack.)  Quotients that differ by <= 1 have floors that differ by <= 1, and the clamp is monotone.  (On 1.5 M random and
+// planted float32 pairs within a radius of 0.1, cells exactly one radius wide lost none either, tests/test_icp_grid_cpu.py: the margin is what makes the
+// claim hold for every radius and magnitude, not the cure of a loss seen.)
+// Integer range: a target's |cell| <= M / e <= 2^20; a query anywhere (a far initial transform, a non-finite coordinate) is clamped to +-2^30 before the
+// conversion, so cell +- 1 never overflows -- such a query meets whatever shares its buckets, all of it farther than the radius.  A radius below
+// 2^-20 of the coordinates' magnitude is what enlarges e: cells wider than the radius stay correct, they only hold more candidates.
+constexpr int kGridMinBuckets = 64, kGridMaxBuckets = 32768;   // the table (H + 1 ints) stays within 128 KiB + 4 of LDS
+constexpr double kGridCellMax = 1073741824.0, kGridSpan = 9.5367431640625e-07;   // 2^30, 2^-20
+constexpr size_t kIcpGridWsBudget = (size_t)1 << 30;   // workspace of one chunk of grid pairs
+struct IcpGridInfo { double edge; int buckets, occupied, largest, pad; };   // per pair, at the head of its workspace
+
+__host__ __device__ inline int icp_grid_buckets(long long n2)
+{
+  int H = kGridMinBuckets;
+  while (H < n2 && H < kGridMaxBuckets) H <<= 1;
+  return H;
+}
+// a pair's workspace: IcpGridInfo (256 bytes) | bucket starts [H + 1] ints | records [n2] float4
+__host__ __device__ inline size_t icp_grid_table_bytes(long long n2) { return (((size_t)icp_grid_buckets(n2) + 1) * 4 + 255) & ~(size_t)255; }
+__host__ __device__ inline size_t icp_grid_pair_bytes(long long n2) { return 256 + icp_grid_table_bytes(n2) + (((size_t)n2 * 16 + 255) & ~(size_t)255); }
+__device__ __forceinline__ int icp_grid_cell(double x, double e)
+{
+  const double c = fmin(fmax(floor(x / e), -kGridCellMax), kGridCellMax);   // (fmax / fmin drop a NaN)
+  return (int)c;
+}
+__device__ __forceinline__ unsigned icp_grid_hash(int cx, int cy, int cz)
+{
+  unsigned v = (unsigned)cx * 73856093u ^ (unsigned)cy * 19349663u ^ (unsigned)cz * 83492791u;
+  v ^= v >> 15; v *= 0x2c1b3c6du; v ^= v >> 12;
+  return v;
+}
+
+struct IcpGridArgs : IcpArgs {
+  char* ws;                     // the chunk's workspace
+  const long long* ws_off;      // [B] byte offset of pair b's part
+};
+
 // path record of a quad (tr_paths): bits 2 s, 2 s + 1 = what lane s did with its slice of the LDS-resident targets, bit 8 = the winner came from the tail
 constexpr int kIcpPathNone = 0, kIcpPathSingle = 1, kIcpPathWalk = 2, kIcpPathTailWon = 256;
 
@@ -102,14 +158,16 @@ __device__ __forceinline__ void block_reduce(double (&v)[N], double* red /*[wave
 
 // kTrace: the SAME scan, and behind the quad's merge one record per source point (IcpArgs::tr_*) -- the test hook's instantiations; the
 // shipped ones (kTrace = false) compile to what they were without it (per-kernel resource remarks unchanged)
-template <bool kFull, bool kTrace = false>
-__global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
+// kGrid: the grid search in place of the scan (one lane per source point, the bucket table in LDS); loop, sums, estimate and stop are the same source
+template <bool kFull, bool kTrace = false, bool kGrid = false>
+__global__ __launch_bounds__(kIcpThreads) void icp_kernel(const std::conditional_t<kGrid, IcpGridArgs, IcpArgs> a)
 {
+  constexpr int kSplit = kGrid ? 1 : kIcpSplit;   // lanes per source point
   constexpr int kSums = kFull ? kIcpSumsFull : kIcpSums;
   extern __shared__ __attribute__((aligned(16))) double tgt[];   // [3][lds_points] doubles | [3][4 slices][S4] floats
   __shared__ double T[12];            // rows 0..2 of the 4x4
   __shared__ double red[(kIcpThreads / 64) * kSums], tot[kSums];
-  const int b = blockIdx.x, tid = threadIdx.x, sub = tid & (kIcpSplit - 1);
+  const int b = blockIdx.x, tid = threadIdx.x, sub = tid & (kSplit - 1);
   const long long row = a.rows ? a.rows[b] : b;
   const long long s_lo = a.off[row * 2], n1 = a.off[(row + 1) * 2] - s_lo;
   const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
@@ -120,6 +178,20 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
   const double* tx = tgt; const double* ty = tgt + a.lds_points; const double* tz = tgt + 2 * a.lds_points;
   const int S4 = icp_slice_len(a.lds_points);
   float* t32 = reinterpret_cast<float*>(tgt + 3 * (size_t)a.lds_points);   // [coordinate][slice][S4]
+  // grid search: the pair's bucket starts (LDS), its records (L2) and its cell edge
+  [[maybe_unused]] int* const gstart = reinterpret_cast<int*>(tgt);
+  [[maybe_unused]] const float4* grec = nullptr;
+  [[maybe_unused]] unsigned gmask = 0;
+  [[maybe_unused]] double gedge = 1.0;
+  if constexpr (kGrid) {
+    const char* const w = a.ws + a.ws_off[b];
+    const int H = icp_grid_buckets(n2);
+    const int* const st = reinterpret_cast<const int*>(w + 256);
+    for (int j = tid; j <= H; j += kIcpThreads) gstart[j] = st[j];
+    grec = reinterpret_cast<const float4*>(w + 256 + icp_grid_table_bytes(n2));
+    gmask = (unsigned)H - 1u;
+    gedge = reinterpret_cast<const IcpGridInfo*>(w)->edge;
+  } else {
   for (int j = tid; j < 3 * kIcpSplit * S4; j += kIcpThreads) t32[j] = kIcpFar;
   __syncthreads();
   for (int j = tid; j < nl; j += kIcpThreads) {
@@ -127,6 +199,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
     tgt[j] = (double)x; tgt[a.lds_points + j] = (double)y; tgt[2 * a.lds_points + j] = (double)z;
     const int o = (j & (kIcpSplit - 1)) * S4 + (j >> 2);
     t32[o] = x; t32[kIcpSplit * S4 + o] = y; t32[2 * kIcpSplit * S4 + o] = z;
+  }
   }
   __syncthreads();
   const int Lp = ((nl + kIcpSplit - 1) / kIcpSplit + 1) & ~1;   // slice positions walked (even; the padding behind a slice's end is kIcpFar)
@@ -144,8 +217,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
       double v[kSums];
 #pragma unroll
       for (int q = 0; q < kSums; ++q) v[q] = 0.0;
-      for (long long i0 = 0; i0 < n1; i0 += kIcpThreads / kIcpSplit) {
-        const long long i = i0 + (tid / kIcpSplit);
+      for (long long i0 = 0; i0 < n1; i0 += kIcpThreads / kSplit) {
+        const long long i = i0 + (tid / kSplit);
         const bool active = i < n1;                      // (inactive quads run along on the last point: the shuffles below want every lane)
         const long long ic = active ? i : n1 - 1;
         const double sx = src[ic * 3], sy = src[ic * 3 + 1], sz = src[ic * 3 + 2];
@@ -154,6 +227,26 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
         const double pz = T[8] * sx + T[9] * sy + T[10] * sz + T[11];
         double best = 1e300; int bj = 0x7fffffff;
         int path = kIcpPathNone;
+        [[maybe_unused]] float4 brec = {0.f, 0.f, 0.f, 0.f};   // grid search: the winner's record
+        if constexpr (kGrid) {
+          if (active) {
+            const int gx = icp_grid_cell(px, gedge), gy = icp_grid_cell(py, gedge), gz = icp_grid_cell(pz, gedge);
+#pragma unroll 1
+            for (int c = 0; c < 27; ++c) {
+              const unsigned hb = icp_grid_hash(gx + c % 3 - 1, gy + (c / 3) % 3 - 1, gz + c / 9 - 1) & gmask;
+              const int lo = gstart[hb], hi = gstart[hb + 1];
+#pragma unroll 1
+              for (int j = lo; j < hi; ++j) {
+                const float4 q = grec[j];
+                const int oj = __float_as_int(q.w);
+                const double ddx = px - (double)q.x, ddy = py - (double)q.y, ddz = pz - (double)q.z;
+                const double d = ddx * ddx + ddy * ddy + ddz * ddz;
+                if (d < best || (d == best && oj < bj)) { best = d; bj = oj; brec = q; }   // equal distances: the lower original index
+              }
+              if constexpr (kTrace) path += hi - lo;   // candidates evaluated
+            }
+          }
+        } else {
         {
           // one fp32 pass over the slice: its smallest distance m1 with the position it sits at, and its second smallest m2 (v_med3 of the
           // ordered pair and the newcomer) -- four vector instructions per target next to the packed arithmetic, no branch
@@ -210,7 +303,14 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
           const int oj = __shfl_xor(bj, o);
           if (ob < best || (ob == best && oj < bj)) { best = ob; bj = oj; }
         }
-        if constexpr (kTrace) {
+        }
+        if constexpr (kTrace && kGrid) {
+          if (active && k == 0) {
+            const bool found = bj != 0x7fffffff;
+            a.tr_index[i] = found ? bj : -1; a.tr_dist[i] = found ? best : __builtin_huge_val(); a.tr_inlier[i] = best <= r2; a.tr_paths[i] = path;
+          }
+        }
+        if constexpr (kTrace && !kGrid) {
           path <<= 2 * sub;
           path |= __shfl_xor(path, 1);
           path |= __shfl_xor(path, 2);
@@ -220,9 +320,9 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
           }
         }
         if (active && sub == 0 && best <= r2) {
-          const double qx = bj < nl ? tx[bj] : (double)dst[(long long)bj * 3];
-          const double qy = bj < nl ? ty[bj] : (double)dst[(long long)bj * 3 + 1];
-          const double qz = bj < nl ? tz[bj] : (double)dst[(long long)bj * 3 + 2];
+          const double qx = kGrid ? (double)brec.x : bj < nl ? tx[bj] : (double)dst[(long long)bj * 3];
+          const double qy = kGrid ? (double)brec.y : bj < nl ? ty[bj] : (double)dst[(long long)bj * 3 + 1];
+          const double qz = kGrid ? (double)brec.z : bj < nl ? tz[bj] : (double)dst[(long long)bj * 3 + 2];
           const double ax = px - cx, ay = py - cy, az = pz - cz, bx = qx - cx, by = qy - cy, bz = qz - cz;
           v[0] += 1.0; v[1] += ax; v[2] += ay; v[3] += az; v[4] += bx; v[5] += by; v[6] += bz;
           if constexpr (kFull) {   // sum b a^T, row-major
@@ -303,29 +403,135 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const IcpArgs a)
   }
 }
 
+// Grid build, one workgroup per pair: cell edge from the pair's largest |coordinate|, then a counting sort of the targets by hashed cell -- counts by
+// LDS atomics, an exclusive scan over the H buckets (each thread a contiguous run, the runs' totals scanned across the block), the starts written
+// out, the scatter by LDS atomics on the running starts.  Both passes hash the same values, so the positions handed out stay inside [0, n2).
+__global__ __launch_bounds__(kIcpThreads) void icp_grid_build_kernel(const IcpGridArgs a)
+{
+  extern __shared__ int cnt[];        // [H + 1]
+  __shared__ double wmax[kIcpThreads / 64];
+  __shared__ int wsum[kIcpThreads / 64], wocc[kIcpThreads / 64], wbig[kIcpThreads / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long row = a.rows ? a.rows[b] : b;
+  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
+  const float* dst = a.pts[1] + t_lo * 3;
+  char* const w = a.ws + a.ws_off[b];
+  const int H = icp_grid_buckets(n2);
+  int* const st = reinterpret_cast<int*>(w + 256);
+  float4* const rec = reinterpret_cast<float4*>(w + 256 + icp_grid_table_bytes(n2));
+  double m = 0.0;
+  for (long long j = tid; j < n2; j += kIcpThreads)
+    m = fmax(m, (double)fmaxf(fmaxf(fabsf(dst[j * 3]), fabsf(dst[j * 3 + 1])), fabsf(dst[j * 3 + 2])));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+  if (lane == 0) wmax[wave] = m;
+  for (int j = tid; j <= H; j += kIcpThreads) cnt[j] = 0;
+  __syncthreads();
+  for (int q = 0; q < kIcpThreads / 64; ++q) m = fmax(m, wmax[q]);
+  const double e = fmax(a.radius * (1.0 + kGridSpan), (m + a.radius) * kGridSpan);
+  const unsigned mask = (unsigned)H - 1u;
+  for (long long j = tid; j < n2; j += kIcpThreads) {
+    const unsigned hb = icp_grid_hash(icp_grid_cell((double)dst[j * 3], e), icp_grid_cell((double)dst[j * 3 + 1], e), icp_grid_cell((double)dst[j * 3 + 2], e)) & mask;
+    atomicAdd(&cnt[hb], 1);
+  }
+  __syncthreads();
+  // exclusive scan: thread t owns buckets [t per, (t + 1) per)
+  const int per = (H + kIcpThreads - 1) / kIcpThreads, lo = min(tid * per, H), hi = min(lo + per, H);
+  int sum = 0, occ = 0, big = 0;
+  for (int q = lo; q < hi; ++q) { const int c = cnt[q]; sum += c; occ += c > 0; big = max(big, c); }
+  int inc = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int up = __shfl_up(inc, o); if (lane >= o) inc += up; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { occ += __shfl_xor(occ, o); big = max(big, __shfl_xor(big, o)); }
+  if (lane == 63) wsum[wave] = inc;
+  if (lane == 0) { wocc[wave] = occ; wbig[wave] = big; }
+  __syncthreads();
+  int run = inc - sum;
+  for (int q = 0; q < wave; ++q) run += wsum[q];
+  __syncthreads();
+  for (int q = lo; q < hi; ++q) { const int c = cnt[q]; cnt[q] = run; run += c; }
+  if (tid == 0) {
+    cnt[H] = (int)n2;
+    int o2 = 0, b2 = 0;
+    for (int q = 0; q < kIcpThreads / 64; ++q) { o2 += wocc[q]; b2 = max(b2, wbig[q]); }
+    IcpGridInfo* info = reinterpret_cast<IcpGridInfo*>(w);
+    info->edge = e; info->buckets = H; info->occupied = o2; info->largest = b2; info->pad = 0;
+  }
+  __syncthreads();
+  for (int j = tid; j <= H; j += kIcpThreads) st[j] = cnt[j];
+  __syncthreads();
+  for (long long j = tid; j < n2; j += kIcpThreads) {
+    const float x = dst[j * 3], y = dst[j * 3 + 1], z = dst[j * 3 + 2];
+    const unsigned hb = icp_grid_hash(icp_grid_cell((double)x, e), icp_grid_cell((double)y, e), icp_grid_cell((double)z, e)) & mask;
+    const int pos = atomicAdd(&cnt[hb], 1);
+    rec[pos] = make_float4(x, y, z, __int_as_float((int)j));
+  }
+}
+
 // shared driver: tables already on the device
 // alignnet_debug_icp_scan: host arrays [n1] for the records of pair 0's first evaluation; lds_points > 0 overrides the LDS stage's size (<= the budget)
-struct IcpTraceOut { long long n1; int lds_points; int* index; double* dist; int* inlier; int* paths; int* lds_points_used; };
+// alignnet_debug_icp_grid (grid = true): the same through the grid search, paths = candidates evaluated, info = pair 0's IcpGridInfo
+struct IcpTraceOut { long long n1; int lds_points; int* index; double* dist; int* inlier; int* paths; int* lds_points_used; bool grid; IcpGridInfo* info; };
 
 constexpr long long kIcpLdsBudget = (150 * 1024) / 36;   // doubles x 3 + floats x 3 per point within one CU's LDS
+constexpr long long kIcpGridAuto = kIcpLdsBudget;        // "icp_search" = 2: pairs with n2 above this take the grid (where the scan leaves its certified LDS path)
 
-int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long long* d_off, const int* d_rows, long long max_n2,
-            int B, const double* init, double radius, int its, bool full, double* out, double* fitness, double* rmse, int* iters,
+template <class Args>
+Args icp_args_from(const Args& a, int lo)   // the arguments of pairs lo.. as a launch of their own
+{
+  Args r = a;
+  r.init += (size_t)lo * 16; r.out += (size_t)lo * 16; r.fitness += lo; r.rmse += lo; r.iters += lo;
+  if (r.rows) r.rows += lo; else r.off += (size_t)lo * 2;
+  return r;
+}
+
+// n2: the target sizes of the B pairs as the host knows them; stage_n2: what the scan's LDS stage is sized for
+int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long long* d_off, const int* d_rows, const std::vector<long long>& n2,
+            long long stage_n2, int B, const double* init, double radius, int its, bool full, double* out, double* fitness, double* rmse, int* iters,
             const IcpTraceOut* trace = nullptr)
 {
   if (!init || !out) return fail(h, "icp: null init / out");
   if (!(radius > 0.0) || its < 0) return fail(h, "icp: radius must be > 0 and its >= 0");
-  double *d_init = nullptr, *d_out = nullptr, *d_fr = nullptr; int* d_it = nullptr;
+  // which search each pair takes ("icp_search"; the read-backs choose their own), and the grid pairs' workspace: consecutive grid pairs form
+  // chunks of at most kIcpGridWsBudget (one pair may exceed it alone), every chunk reuses the handle's workspace in stream order
+  const int mode = trace ? (trace->grid ? 1 : 0) : h->icp_search;
+  std::vector<char> grid(B, 0);
+  std::vector<long long> ws_off(B, 0);
+  size_t need = 0, cur = 0; int open = -1;
+  for (int b = 0; b < B; ++b) {
+    grid[b] = mode == 1 || (mode == 2 && n2[b] > kIcpGridAuto);
+    if (!grid[b]) { open = -1; continue; }
+    if (n2[b] > 0x7fffffff) return fail(h, "icp: more than 2^31 - 1 target points in a pair");
+    const size_t bytes = icp_grid_pair_bytes(n2[b]);
+    if (open < 0 || cur + bytes > kIcpGridWsBudget) { open = b; cur = 0; }
+    ws_off[b] = (long long)cur; cur += bytes;
+    need = std::max(need, cur);
+  }
+  if (need) {
+    if (h->icp_grid_ws_bytes < need) {
+      if (h->icp_grid_ws) { HIP_TRY(h, hipStreamSynchronize(h->stream)); hipFree(h->icp_grid_ws); h->icp_grid_ws = nullptr; h->icp_grid_ws_bytes = 0; }
+      HIP_TRY(h, hipMalloc(&h->icp_grid_ws, need));
+      h->icp_grid_ws_bytes = need;
+    }
+    h->icp_grid_ws_used = need;
+  }
+  double *d_init = nullptr, *d_out = nullptr, *d_fr = nullptr; int* d_it = nullptr; long long* d_wsoff = nullptr;
   HIP_TRY(h, hipMalloc(&d_init, (size_t)B * 16 * sizeof(double)));
   HIP_TRY(h, hipMalloc(&d_out, (size_t)B * 16 * sizeof(double)));
   HIP_TRY(h, hipMalloc(&d_fr, (size_t)B * 2 * sizeof(double)));
   HIP_TRY(h, hipMalloc(&d_it, (size_t)B * sizeof(int)));
   HIP_TRY(h, hipMemcpyAsync(d_init, init, (size_t)B * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  IcpArgs a;
+  if (need) {
+    HIP_TRY(h, hipMalloc(&d_wsoff, (size_t)B * sizeof(long long)));
+    HIP_TRY(h, hipMemcpyAsync(d_wsoff, ws_off.data(), (size_t)B * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  }
+  IcpGridArgs a;
   a.pts[0] = d_p0; a.pts[1] = d_p1; a.off = d_off; a.rows = d_rows; a.init = d_init; a.radius = radius; a.its = its;
-  a.lds_points = (int)std::max<long long>(1, std::min(kIcpLdsBudget, max_n2));
+  a.lds_points = (int)std::max<long long>(1, std::min(kIcpLdsBudget, stage_n2));
   a.out = d_out; a.fitness = d_fr; a.rmse = d_fr + B; a.iters = d_it;
   a.tr_index = a.tr_inlier = a.tr_paths = nullptr; a.tr_dist = nullptr;
+  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = d_wsoff;
   char* d_tr = nullptr;   // [n1] doubles | 3 x [n1] ints
   if (trace) {
     if (trace->lds_points > 0) a.lds_points = trace->lds_points;
@@ -335,23 +541,55 @@ int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long
     a.tr_dist = reinterpret_cast<double*>(d_tr);
     a.tr_index = reinterpret_cast<int*>(d_tr + n * 8); a.tr_inlier = a.tr_index + n; a.tr_paths = a.tr_inlier + n;
   }
-  static alignnet::PerDeviceOnce attr[4];
+  static alignnet::PerDeviceOnce attr[9];
   const int which = (full ? 1 : 0) + (trace ? 2 : 0);
-  const void* const kernels[4] = {reinterpret_cast<const void*>(icp_kernel<false>), reinterpret_cast<const void*>(icp_kernel<true>),
-                                  reinterpret_cast<const void*>(icp_kernel<false, true>), reinterpret_cast<const void*>(icp_kernel<true, true>)};
-  if (attr[which].need(h->cfg.device)) {
-    HIP_TRY(h, hipFuncSetAttribute(kernels[which], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
-    attr[which].mark(h->cfg.device);
+  const void* const kernels[9] = {reinterpret_cast<const void*>(icp_kernel<false>), reinterpret_cast<const void*>(icp_kernel<true>),
+                                  reinterpret_cast<const void*>(icp_kernel<false, true>), reinterpret_cast<const void*>(icp_kernel<true, true>),
+                                  reinterpret_cast<const void*>(icp_kernel<false, false, true>), reinterpret_cast<const void*>(icp_kernel<true, false, true>),
+                                  reinterpret_cast<const void*>(icp_kernel<false, true, true>), reinterpret_cast<const void*>(icp_kernel<true, true, true>),
+                                  reinterpret_cast<const void*>(icp_grid_build_kernel)};
+  for (const int kn : {which, which + 4, 8})
+    if ((kn < 4 || need) && attr[kn].need(h->cfg.device)) {
+      HIP_TRY(h, hipFuncSetAttribute(kernels[kn], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+      attr[kn].mark(h->cfg.device);
+    }
+  for (int lo = 0; lo < B;) {
+    int hi = lo + 1;
+    if (!grid[lo]) {
+      while (hi < B && !grid[hi]) ++hi;
+      const IcpArgs r = icp_args_from<IcpArgs>(a, lo);
+      const size_t lds = icp_lds_bytes(a.lds_points);
+      if (which == 3)
+        hipLaunchKernelGGL((icp_kernel<true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      else if (which == 2)
+        hipLaunchKernelGGL((icp_kernel<false, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      else if (full)
+        hipLaunchKernelGGL(icp_kernel<true>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      else
+        hipLaunchKernelGGL(icp_kernel<false>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+    } else {
+      long long big = n2[lo];
+      while (hi < B && grid[hi] && ws_off[hi] != 0) { big = std::max(big, n2[hi]); ++hi; }   // (a chunk's first pair sits at offset 0)
+      IcpGridArgs r = icp_args_from<IcpGridArgs>(a, lo);
+      r.ws_off += lo;
+      const size_t lds = ((size_t)icp_grid_buckets(big) + 1) * 4;
+      {
+        alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID_BUILD);
+        hipLaunchKernelGGL(icp_grid_build_kernel, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      }
+      alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID);
+      if (which == 3)
+        hipLaunchKernelGGL((icp_kernel<true, true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      else if (which == 2)
+        hipLaunchKernelGGL((icp_kernel<false, true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      else if (full)
+        hipLaunchKernelGGL((icp_kernel<true, false, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      else
+        hipLaunchKernelGGL((icp_kernel<false, false, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+    }
+    HIP_TRY(h, hipGetLastError());
+    lo = hi;
   }
-  if (which == 3)
-    hipLaunchKernelGGL((icp_kernel<true, true>), dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
-  else if (which == 2)
-    hipLaunchKernelGGL((icp_kernel<false, true>), dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
-  else if (full)
-    hipLaunchKernelGGL(icp_kernel<true>, dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
-  else
-    hipLaunchKernelGGL(icp_kernel<false>, dim3(B), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, a);
-  HIP_TRY(h, hipGetLastError());
   if (trace) {
     const size_t n = (size_t)std::max<long long>(trace->n1, 1), m = (size_t)trace->n1;
     if (m) {
@@ -360,14 +598,15 @@ int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long
       HIP_TRY(h, hipMemcpyAsync(trace->inlier, d_tr + n * 12, m * 4, hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(h, hipMemcpyAsync(trace->paths, d_tr + n * 16, m * 4, hipMemcpyDeviceToHost, h->stream));
     }
-    *trace->lds_points_used = a.lds_points;
+    if (trace->grid) HIP_TRY(h, hipMemcpyAsync(trace->info, h->icp_grid_ws, sizeof(IcpGridInfo), hipMemcpyDeviceToHost, h->stream));
+    else *trace->lds_points_used = a.lds_points;
   }
   HIP_TRY(h, hipMemcpyAsync(out, d_out, (size_t)B * 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (fitness) HIP_TRY(h, hipMemcpyAsync(fitness, d_fr, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (rmse) HIP_TRY(h, hipMemcpyAsync(rmse, d_fr + B, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (iters) HIP_TRY(h, hipMemcpyAsync(iters, d_it, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  hipFree(d_init); hipFree(d_out); hipFree(d_fr); hipFree(d_it); hipFree(d_tr);
+  hipFree(d_init); hipFree(d_out); hipFree(d_fr); hipFree(d_it); hipFree(d_tr); hipFree(d_wsoff);
   return 0;
 }
 
@@ -379,10 +618,10 @@ int icp_host(alignnet_handle* h, const char* fn, const float* points1, const flo
   const std::string name(fn);
   if (!offsets || B < 1) return fail(h, name + ": null offsets or B < 1");
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  long long max_n2 = 0;
+  std::vector<long long> n2(B);
   for (int i = 0; i < B; ++i) {
     if (offsets[(i + 1) * 2] < offsets[i * 2] || offsets[(i + 1) * 2 + 1] < offsets[i * 2 + 1]) return fail(h, name + ": offsets must be non-decreasing");
-    max_n2 = std::max<long long>(max_n2, offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1]);
+    n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1];
   }
   const size_t n0 = (size_t)offsets[B * 2], n1 = (size_t)offsets[B * 2 + 1];
   if ((n0 && !points1) || (n1 && !points2)) return fail(h, name + ": null point blob");
@@ -393,7 +632,7 @@ int icp_host(alignnet_handle* h, const char* fn, const float* points1, const flo
   if (n0) HIP_TRY(h, hipMemcpyAsync(d0, points1, n0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   if (n1) HIP_TRY(h, hipMemcpyAsync(d1, points2, n1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(doff, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  const int rc = run_icp(h, d0, d1, doff, nullptr, max_n2, B, init, radius, its, full, out, fitness, rmse, iterations, trace);
+  const int rc = run_icp(h, d0, d1, doff, nullptr, n2, *std::max_element(n2.begin(), n2.end()), B, init, radius, its, full, out, fitness, rmse, iterations, trace);
   hipFree(d0); hipFree(d1); hipFree(doff);
   return rc;
 }
@@ -413,8 +652,11 @@ int icp_rows(alignnet_handle* h, const char* fn, const int32_t* rows, int32_t B,
   int* d_rows = nullptr;
   HIP_TRY(h, hipMalloc(&d_rows, (size_t)B * sizeof(int)));
   HIP_TRY(h, hipMemcpyAsync(d_rows, rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  // the largest target cloud is not known on the host: size the LDS stage for the budget, the kernel clamps per pair
-  const int rc = run_icp(h, t.pts[0], t.pts[1], t.off, d_rows, kIcpLdsBudget, B, init, radius, its, full, out, fitness, rmse, iterations);
+  // target sizes from the host's copy of the offsets (the grid search carves its workspace per pair).  The scan's LDS stage stays sized for
+  // the budget whatever the rows hold, as it was when the host did not know the sizes: the kernel clamps per pair
+  std::vector<long long> n2(B);
+  for (int i = 0; i < B; ++i) n2[i] = t.h_off[((size_t)rows[i] + 1) * 2 + 1] - t.h_off[(size_t)rows[i] * 2 + 1];
+  const int rc = run_icp(h, t.pts[0], t.pts[1], t.off, d_rows, n2, kIcpLdsBudget, B, init, radius, its, full, out, fitness, rmse, iterations);
   hipFree(d_rows);
   return rc;
 }
@@ -473,7 +715,33 @@ extern "C" int alignnet_debug_icp_scan(alignnet_handle* h, const float* points1,
   if (lds_points < 0 || lds_points > kIcpLdsBudget) return fail(h, name + ": lds_points must be in [0, " + std::to_string(kIcpLdsBudget) + "] (0 = as shipped)");
   if (!index || !dist2 || !inlier || !paths || !lds_points_used) return fail(h, name + ": null output");
   const int64_t off[4] = {0, 0, n1, n2};
-  const IcpTraceOut tr = {n1, lds_points, index, dist2, inlier, paths, lds_points_used};
+  const IcpTraceOut tr = {n1, lds_points, index, dist2, inlier, paths, lds_points_used, false, nullptr};
   double out[16];
   return icp_host(h, name.c_str(), points1, points2, off, 1, T, radius, 0, full, out, fitness, rmse, nullptr, &tr);
+}
+
+extern "C" int alignnet_debug_icp_grid(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2, const double* T,
+                                       double radius, int32_t flags, int32_t* index, double* dist2, int32_t* inlier, int32_t* candidates,
+                                       double* cell_edge, int32_t* buckets_occupied, int32_t* largest_bucket, double* fitness, double* rmse)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_debug_icp_grid");
+  bool full = false;
+  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
+  if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(h, name + ": n1 / n2 out of range");
+  if (!index || !dist2 || !inlier || !candidates || !cell_edge || !buckets_occupied || !largest_bucket) return fail(h, name + ": null output");
+  const int64_t off[4] = {0, 0, n1, n2};
+  IcpGridInfo info = {0.0, 0, 0, 0, 0};
+  const IcpTraceOut tr = {n1, 0, index, dist2, inlier, candidates, nullptr, true, &info};
+  double out[16];
+  if (icp_host(h, name.c_str(), points1, points2, off, 1, T, radius, 0, full, out, fitness, rmse, nullptr, &tr)) return 1;
+  *cell_edge = info.edge; *buckets_occupied = info.occupied; *largest_bucket = info.largest;
+  return 0;
+}
+
+extern "C" void alignnet_icp_free(alignnet_handle* h)
+{
+  if (!h || !h->icp_grid_ws) return;
+  hipFree(h->icp_grid_ws);
+  h->icp_grid_ws = nullptr; h->icp_grid_ws_bytes = h->icp_grid_ws_used = 0;
 }

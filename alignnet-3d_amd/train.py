@@ -112,6 +112,8 @@ class Run:
             # ICP refines on the FULL clouds (train.py:469), which live in HBM next to the network (alignnet_icp_refine_dataset)
             self.icp_data = provider.use_packed_cache()
             self.icp_data.upload(self.engine)
+        if flags.refineICP:
+            set_icp_search(self.engine)
         self.train_idx = provider.getDataFiles("%s/split/train.txt" % cfg.data.basepath)
         self.val_idx = provider.getDataFiles("%s/split/val.txt" % cfg.data.basepath)
         self.batches_per_epoch = len(self.train_idx) // cfg.training.batch_size
@@ -324,6 +326,27 @@ class Run:
 
 # ---- ICP baseline evaluation mode (evaluation.special.mode = "icp", icp.py:150-213) ---------------------------------------
 ICP_CHUNK = 4096   # pairs per registration call
+ICP_SEARCH = {"scan": 0, "grid": 1, "auto": 2}   # engine option icp_search (include/alignnet_hip.h)
+
+
+def icp_search_option(config=None, environ=None):
+    """Optional, not a reference key: "evaluation": {"icp_search": "scan" | "grid" | "auto"} (or ALIGNNET_ICP_SEARCH, which wins when set) selects
+    the correspondence search of every ICP call -- the brute-force scan (default), the uniform-grid search for dense clouds, or per pair by target
+    size.  Same registration either way.  Returns (name, option value)."""
+    config = cfg if config is None else config
+    environ = os.environ if environ is None else environ
+    name = environ.get("ALIGNNET_ICP_SEARCH", "") or getattr(getattr(config, "evaluation", None), "icp_search", "scan")
+    name = str(name).lower()
+    if name not in ICP_SEARCH:
+        raise ValueError("evaluation.icp_search / ALIGNNET_ICP_SEARCH = %r: expected one of %s" % (name, ", ".join(sorted(ICP_SEARCH))))
+    return name, ICP_SEARCH[name]
+
+
+def set_icp_search(engine):
+    name, value = icp_search_option()
+    engine.set_option("icp_search", value)
+    if value:
+        logger.info("ICP correspondence search: %s" % name)
 
 
 def icp_plan(icp):
@@ -386,6 +409,7 @@ def run_icp_mode(flags):
     else:
         import alignnet3d
         engine = alignnet3d.Engine(cfg, device=local_rank if world > 1 else None)
+        set_icp_search(engine)
         packed.upload(engine)
         rows = packed.rows_of(val)
         pred_t, pred_a = np.empty((nval, 3), np.float32), np.empty((nval, 1), np.float32)

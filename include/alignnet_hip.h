@@ -338,6 +338,16 @@ int alignnet_debug_icp_scan(alignnet_handle* h, const float* points1, int64_t n1
                             const double* T, double radius, int32_t flags, int32_t lds_points, int32_t* index,
                             double* dist2, int32_t* inlier, int32_t* paths, int32_t* lds_points_used, double* fitness,
                             double* rmse);
+/* The same read-back through the GRID search (alignnet_set_option "icp_search"): the grid build and ONE evaluation of one
+ * pair by the shipped grid kernel's source, compiled with a record behind it.  index [n1] the chosen target's original
+ * index (-1: no candidate in the 27 cells around the point); dist2 [n1] its fp64 squared distance (+inf if none; beyond
+ * radius^2 it is the nearest CANDIDATE, which need not be the nearest target); inlier [n1]; candidates [n1] the
+ * records evaluated for the point (a bucket met twice counts twice).  cell_edge [1] the cell edge used (> radius);
+ * buckets_occupied / largest_bucket [1] of the pair's hashed cell table.  flags, fitness, rmse as above. */
+int alignnet_debug_icp_grid(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2,
+                            const double* T, double radius, int32_t flags, int32_t* index, double* dist2, int32_t* inlier,
+                            int32_t* candidates, double* cell_edge, int32_t* buckets_occupied, int32_t* largest_bucket,
+                            double* fitness, double* rmse);
 
 /* ---- global registration: RANSAC on FPFH feature matches (the `o3_gicp` baseline, icp.py:85-143) --------------
  * Per pair: voxel downsample (0.05 m) of both clouds, normals (radius 0.10, 30 nearest), FPFH (radius 0.25, 100
@@ -500,6 +510,16 @@ int alignnet_debug_scene_cast(alignnet_handle* h, int32_t mesh, double scale, co
  * "sync_bn_emulate_world" (test hook, default 1): without a communicator, stand for this many ranks holding identical shards.
  * "dropout_stream" (default 0): selects one of 2^64 independent device-side dropout streams under the same cfg.seed; data-parallel
  *   ranks set it to their rank so that they do not draw identical masks for their local rows (initialisation stays cfg.seed's).
+ * "icp_search" (0/1/2, default 0): the correspondence search of alignnet_icp_refine, _refine_dataset, _register and _register_dataset.
+ *   0 = the brute-force scan for every pair (n1 x n2 distances per iteration; built for clouds of a few thousand points, and every result
+ *   bit for bit what it was before the key existed).  1 = a uniform-grid search for every pair: per call the pair's targets are bucket-sorted
+ *   by hashed cell (cells just over one radius wide, O(n2) memory whatever the extent), and every source point evaluates in fp64 only the
+ *   targets in the 27 cells around it -- exact: the same nearest target within the radius, equal distances to the lower index; the sums run
+ *   over another assignment of points to threads, so transforms agree with the scan's to rounding (1e-9), not bit for bit.  2 = automatic:
+ *   a pair takes the grid when its target has more than 4266 points (where the scan leaves its LDS stage), else the scan; each pair's
+ *   result is bit-identical to what 0 (scan pairs) or 1 (grid pairs) gives it.  Other values are an error.
+ *   "icp_grid_ws_bytes" (read-only): the workspace the last call with grid pairs carved (per chunk of pairs, at most 1 GiB unless one pair
+ *   needs more; freed with the handle).
  * "ab_*" (0/1, default 0): A/B dispatch overrides -- each selects an earlier kernel variant of the SAME arithmetic for same-box comparisons
  *   (results agree up to summation order; tests/test_train_gpu.py runs them against the default): "ab_no_ld_const", "ab_infer_tile64",
  *   "ab_phase2_legacy", "ab_b1_legacy", "ab_b1_fp32", "ab_p3_bf16_generic", "ab_p3_nogram", "ab_no_defer", "ab_dg_sparse",
@@ -544,7 +564,7 @@ int alignnet_profile_read(alignnet_handle* h, double* backbone_ms, int64_t* back
  * on the stream it is launched on while profiling is enabled.  name: "backbone" (eval-mode fused backbone), "knn",
  * "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge",
  * "allreduce" (what the compute stream waits for), "optimizer", and the stages of alignnet_scene_generate: "scene_window" (azimuth windows),
- * "scene_cast", "scene_compact" (counts, scan, scatter + noise). */
+ * "scene_cast", "scene_compact" (counts, scan, scatter + noise), and of the ICP grid search: "icp_grid_build", "icp_grid" (the iterations). */
 int alignnet_profile_read_kernel(alignnet_handle* h, const char* name, double* ms, int64_t* launches);
 
 #ifdef __cplusplus
