@@ -14,9 +14,12 @@ wrong result from a decision that sits within rounding of its boundary:
   neighbour sets    |d^2 - r^2| / r^2 over the candidates, and the relative gap between the max_nn-th and the next d^2
   normals           (l1 - l0) / l2 of the covariance's ascending eigenvalues l0 <= l1 <= l2 (the gap that conditions the eigenvector), and |n . z|
   swap test (SPFH)  | acos|a1| - acos|a2| |
-  matches           relative gap between the best and the second-best feature distance
+  matches           relative gap between the best and the second-best feature distance; target rows equal to the best one count as one
+                    candidate, whose lowest index wins (`matches`)
   RANSAC            the smallest relative margin over every comparison taken for the pair (a < 0.9 b, d^2 > tau^2, d^2 <= tau^2)
 """
+import functools
+
 import numpy as np
 from scipy.spatial import cKDTree
 
@@ -187,20 +190,32 @@ def fpfh(points, sp, radius=5 * VOXEL, max_nn=100):
 
 
 # ---- 5. matches ------------------------------------------------------------------------------------------------------------------------
-def matches(fs, ft):
-    """Nearest target feature of every source feature (lowest index wins a tie).  Returns (index [ms], margin [ms])."""
+def matches(fs, ft, with_ties=False):
+    """Nearest target feature of every source feature (lowest index wins a tie).  Returns (index [ms], margin [ms]), and with_ties also
+    tied [ms] bool.
+
+    Target rows that are EQUAL to the nearest row, entry for entry, form its group: the same operations on the same values give the same
+    distance on any arithmetic, so among them the tie is decided and the lowest index of the group is the answer (an isolated point's
+    all-zero row, and the rows of points with one neighbour, which hold nothing but 0 and 100, repeat across a cloud).  The margin is the
+    relative gap between the group's distance and the best distance over the rows outside the group, inf when every row is in it; tied =
+    the group has more than one member.  Without equal rows this is the gap between the best and the second-best distance."""
     ms, mt = len(fs), len(ft)
-    idx, margin = np.zeros(ms, np.int64), np.full(ms, np.inf)
-    if mt == 0:
-        return idx, margin
-    for s in range(0, ms, 64):
-        d = ((fs[s:s + 64, None, :] - ft[None, :, :]) ** 2).sum(-1)
-        j = d.argmin(1)
-        idx[s:s + 64] = j
-        if mt > 1:
-            part = np.partition(d, 1, axis=1)
-            margin[s:s + 64] = (part[:, 1] - part[:, 0]) / np.maximum(part[:, 1], 1e-300)
-    return idx, margin
+    idx, margin, tied = np.zeros(ms, np.int64), np.full(ms, np.inf), np.zeros(ms, bool)
+    if mt and ms:
+        _, gid = np.unique(ft, axis=0, return_inverse=True)
+        gid = gid.reshape(-1)
+        first = np.full(gid.max() + 1, mt, np.int64)
+        np.minimum.at(first, gid, np.arange(mt))
+        size = np.bincount(gid)
+        for s in range(0, ms, 64):
+            d = ((fs[s:s + 64, None, :] - ft[None, :, :]) ** 2).sum(-1)
+            g = gid[d.argmin(1)]
+            idx[s:s + 64] = first[g]
+            tied[s:s + 64] = size[g] > 1
+            other = np.where(gid[None, :] == g[:, None], np.inf, d).min(1)
+            with np.errstate(invalid="ignore"):
+                margin[s:s + 64] = np.where(np.isinf(other), np.inf, (other - d.min(1)) / np.maximum(other, 1e-300))
+    return (idx, margin, tied) if with_ties else (idx, margin)
 
 
 # ---- 6. RANSAC -------------------------------------------------------------------------------------------------------------------------
@@ -326,18 +341,21 @@ class Ransac:
         return best
 
 
-def global_register(src, dst, constrained=True, seed=0, stream=0, max_iteration=4000000, max_validation=500):
-    """The whole pipeline on one pair of raw clouds.  Returns the RANSAC dict plus the stage outputs."""
-    st = []
-    for pc in (src, dst):
-        ds = voxel_downsample(pc)
-        nr = normals(ds["points"])
-        sp = spfh(ds["points"], nr["normals"])
-        fp = fpfh(ds["points"], sp["spfh"])
-        st.append(dict(ds=ds, normals=nr, spfh=sp, fpfh=fp))
-    m, mm = matches(st[0]["fpfh"]["fpfh"], st[1]["fpfh"]["fpfh"])
+def front_end(pc):
+    """Stages 1-4 on one raw cloud: dict(ds, normals, spfh, fpfh) of the stages' outputs."""
+    ds = voxel_downsample(pc)
+    nr = normals(ds["points"])
+    sp = spfh(ds["points"], nr["normals"])
+    return dict(ds=ds, normals=nr, spfh=sp, fpfh=fpfh(ds["points"], sp["spfh"]))
+
+
+def global_register(src, dst, constrained=True, seed=0, stream=0, max_iteration=4000000, max_validation=500, stages=None):
+    """The whole pipeline on one pair of raw clouds (`stages`: their front ends, when already computed).  Returns the RANSAC dict plus the
+    stage outputs, the matches, their margins and which of them are ties between equal target rows."""
+    st = list(stages) if stages is not None else [front_end(src), front_end(dst)]
+    m, mm, tied = matches(st[0]["fpfh"]["fpfh"], st[1]["fpfh"]["fpfh"], with_ties=True)
     res = Ransac(st[0]["ds"]["points"], st[1]["ds"]["points"], m, constrained, seed, stream).run(max_iteration, max_validation)
-    res.update(stages=st, matches=m, match_margin=mm)
+    res.update(stages=st, matches=m, match_margin=mm, match_tied=tied)
     return res
 
 
@@ -363,8 +381,23 @@ def _surface(rng, n):
     return out
 
 
-def car_pairs(n_pairs, seed, n_points=4500, noise=0.01, max_shift=0.6, yaw_only=True, tilt=0.05, scale=1.0):
-    """Targets: n_points on the surface of the object with clipped noise, somewhere within +-15 m; sources: a 70 % subset of them moved by
+def _planted_motion(rng, ctr, max_shift, yaw_only, tilt):
+    """(R, t) of x = R p + t: a yaw anywhere in (-pi, pi] (plus tilts up to `tilt` rad when not yaw_only) about `ctr`, and up to max_shift in
+    x and y."""
+    yaw = rng.uniform(-np.pi, np.pi)
+    c, s = np.cos(yaw), np.sin(yaw)
+    R = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    if not yaw_only:
+        a, b = rng.uniform(-tilt, tilt, 2)
+        Rx = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
+        Ry = np.array([[np.cos(b), 0, np.sin(b)], [0, 1, 0], [-np.sin(b), 0, np.cos(b)]])
+        R = R @ Ry @ Rx
+    return R, ctr - R @ ctr + np.r_[rng.uniform(-max_shift, max_shift, 2), 0.0]
+
+
+def car_pairs(n_pairs, seed, n_points=4500, noise=0.01, max_shift=0.6, yaw_only=True, tilt=0.05, scale=1.0, offset=None):
+    """Targets: n_points on the surface of the object with clipped noise, somewhere within +-15 m (moved by `offset` before the rounding to
+    float32, when given); sources: a 70 % subset of them moved by
     a yaw anywhere in (-pi, pi] (plus tilts up to `tilt` rad when not yaw_only) and up to max_shift in x and y; `scale` shrinks the object (fewer points then cover it as densely).  Returns (sources, targets,
     truths): truth maps the source onto the target."""
     rng = np.random.default_rng(seed)
@@ -372,16 +405,9 @@ def car_pairs(n_pairs, seed, n_points=4500, noise=0.01, max_shift=0.6, yaw_only=
     for _ in range(n_pairs):
         x = _surface(rng, n_points) * scale + rng.uniform(-15, 15, 3)
         x = x + np.clip(rng.normal(0, noise, x.shape), -2 * noise, 2 * noise)
-        yaw = rng.uniform(-np.pi, np.pi)
-        c, s = np.cos(yaw), np.sin(yaw)
-        R = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
-        if not yaw_only:
-            a, b = rng.uniform(-tilt, tilt, 2)
-            Rx = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
-            Ry = np.array([[np.cos(b), 0, np.sin(b)], [0, 1, 0], [-np.sin(b), 0, np.cos(b)]])
-            R = R @ Ry @ Rx
-        ctr = x.mean(0)
-        t = ctr - R @ ctr + np.r_[rng.uniform(-max_shift, max_shift, 2), 0.0]
+        if offset is not None:
+            x = x + np.asarray(offset, np.float64)
+        R, t = _planted_motion(rng, x.mean(0), max_shift, yaw_only, tilt)
         keep = rng.permutation(n_points)[: int(n_points * 0.7)]
         p = (x[keep] - t) @ R          # x = R p + t
         T = np.eye(4); T[:3, :3] = R; T[:3, 3] = t
@@ -410,6 +436,121 @@ def large_pair():
     """A target that downsamples to more points than the LDS-resident validation grid holds (6314); the source is half of the object."""
     s, d, t = car_pairs(1, seed=31, n_points=16000, scale=0.9, max_shift=0.3)
     return s[0][s[0][:, 0] < np.median(s[0][:, 0])], d[0], t[0]
+
+
+# ---- inputs that reach what the surfaces above never do: both max_nn cuts, the candidate spill, isolated points, tied matches, a grid that
+# ---- has to grow, the voxel-span limit and a frame far from the origin (measured figures: tests/test_global_reg_cpu.py) ------------------
+VOLUME_ITERATIONS, VOLUME_VALIDATIONS = 20000, 20
+WIDE_ITERATIONS, WIDE_VALIDATIONS = 20000, 5
+CAND_LDS = 320                  # kCandLds of csrc/alignnet_globalreg.hip: a wave's candidates beyond these are ranked from HBM
+MAX_GRID_CELLS = 32768          # kMaxCells
+VOLUME_SEED = {True: 66, False: 62}
+CLUTTER_SEED, FAR_SEED, WIDE_SEED = 71, 81, 91
+FAR_OFFSET = (4000.0, -3000.0, 50.0)
+WIDE_X = 100000.0               # the accepted span ends at 2^21 * VOXEL = 104,857.6 m
+
+
+def _frozen(*arrays):
+    """The arrays, read-only: what a cached generator hands out is shared."""
+    for a in arrays:
+        a.setflags(write=False)
+    return arrays
+
+
+@functools.lru_cache(maxsize=None)
+def volume_pair(constrained=True):
+    """A filled box: 24,000 points uniform in 0.8 x 0.6 x 0.45 m, the source an exact 70 % subset under a yaw anywhere (small tilts too for
+    the full-rotation form) and up to 0.3 m of shift.  The 5 cm voxel means of a volume hold about 45 points within 0.10 m and 520 within
+    0.25 m: the normals are cut to their 30 nearest, the features to their 100 nearest, and more than kCandLds candidates are ranked.
+    The box is nearly symmetric: no motion recovery is claimed on it.  Returns (source, target, truth)."""
+    rng = np.random.default_rng(VOLUME_SEED[constrained])
+    n = 24000
+    x = rng.uniform(0, 1, (n, 3)) * np.array([0.8, 0.6, 0.45]) + rng.uniform(-15, 15, 3)
+    R, t = _planted_motion(rng, x.mean(0), 0.3, constrained, 0.05)
+    keep = rng.permutation(n)[: int(n * 0.7)]
+    T = np.eye(4); T[:3, :3] = R; T[:3, 3] = t
+    return _frozen(((x[keep] - t) @ R).astype(np.float32), x.astype(np.float32), T)
+
+
+@functools.lru_cache(maxsize=None)
+def clutter_pair():
+    """The object of gpu_test_pairs among 48 stray returns.  The sites lie within +-8 m of the object's centre, at least 2 m from it and 1 m
+    from each other; a third are single points (no neighbour: default normal, all-zero feature rows), a third carry a second point 0.064 m
+    away (one neighbour within both radii), a third one 0.173 m away (none within 0.10, one within 0.25).  All clutter is in both clouds, the
+    object's points are subsampled to 70 % in the source.  The zero rows and the one-neighbour rows (nothing but 0 and 100) repeat, so the
+    matches hold exact ties; the cloud spans some 15 m, so the validation grid's cell has to grow.  Returns (source, target, truth)."""
+    rng = np.random.default_rng(CLUTTER_SEED)
+    n = 1800
+    obj = _surface(rng, n) * 0.3 + rng.uniform(-15, 15, 3)
+    obj = obj + np.clip(rng.normal(0, 0.01, obj.shape), -0.02, 0.02)
+    ctr = obj.mean(0)
+    sites = []
+    while len(sites) < 48:
+        c = ctr + rng.uniform(-8, 8, 3)
+        if np.linalg.norm(c - ctr) >= 2.0 and all(np.linalg.norm(c - o) >= 1.0 for o in sites):
+            sites.append(c)
+    clutter = []
+    for k, c in enumerate(sites):
+        clutter.append(c)
+        if k % 3:
+            u = rng.normal(size=3)
+            clutter.append(c + u / np.linalg.norm(u) * (0.064 if k % 3 == 1 else 0.173))
+    clutter = np.asarray(clutter)
+    R, t = _planted_motion(rng, ctr, 0.3, True, 0.0)
+    keep = rng.permutation(n)[: int(n * 0.7)]
+    x = np.concatenate([obj, clutter])
+    p = (np.concatenate([obj[keep], clutter]) - t) @ R
+    T = np.eye(4); T[:3, :3] = R; T[:3, 3] = t
+    return _frozen(p.astype(np.float32), x.astype(np.float32), T)
+
+
+def far_pair():
+    """The object of gpu_test_pairs in a frame (4000, -3000, 50) m from the origin, where float32 coordinates are 2.4e-4 m apart: raw points
+    then sit ON voxel edges in exact arithmetic (an offset of an odd multiple of 0.125 m from the cloud's minimum is representable, and
+    0.125 + 0.025 is three voxels), and the floor is decided by the rounding of 0.05 and 0.025 alone -- in fp64 by hundreds of times the
+    rounding of the one inexact operation, the division; in fp32 not at all."""
+    s, d, t = car_pairs(1, seed=FAR_SEED, n_points=1800, scale=0.3, max_shift=0.3, offset=FAR_OFFSET)
+    return s[0], d[0], t[0]
+
+
+def wide_pair():
+    """far_pair's recipe near the origin, plus one point WIDE_X m away in x, the same in both clouds: 2,000,000 voxels wide, inside the limit
+    of 2^21, and the validation grid's cell grows from 0.075 m to metres before its cells fit."""
+    s, d, t = car_pairs(1, seed=WIDE_SEED, n_points=1800, scale=0.3, max_shift=0.3)
+    far = (d[0].astype(np.float64).mean(0) + [WIDE_X, 0.0, 0.0]).astype(np.float32)[None]
+    return np.concatenate([s[0], far]), np.concatenate([d[0], far]), t[0]
+
+
+def too_wide_cloud():
+    """Two points 110,000 m apart: more than 2^21 voxels of 0.05 m."""
+    return np.array([[0.0, 0.0, 0.0], [110000.0, 0.0, 0.0]], np.float32)
+
+
+def radius_counts(points, radius):
+    """Points within `radius` of every point (itself included), before any max_nn cut."""
+    return neighbours(points, radius, len(points) + 1)[3]
+
+
+def grid_cells(points, tau=TAU):
+    """Cells of a uniform grid of edge 1.001 tau over the points: what the validation grid would need before its cell grows."""
+    e = np.floor((points.max(0) - points.min(0)) / (1.001 * tau)) + 1
+    return int(e[0]) * int(e[1]) * int(e[2])
+
+
+NEW_PAIRS = ("volume", "volume_full", "clutter", "far", "wide")
+
+
+def new_pair(name):
+    """(source, target, truth) of one of NEW_PAIRS."""
+    return {"volume": lambda: volume_pair(True), "volume_full": lambda: volume_pair(False), "clutter": clutter_pair, "far": far_pair,
+            "wide": wide_pair}[name]()
+
+
+@functools.lru_cache(maxsize=None)
+def new_pair_stages(name):
+    """The restatement's front end of both clouds of one of NEW_PAIRS, computed once per process: shared by the CPU tests, which only read it."""
+    s, d, _ = new_pair(name)
+    return [front_end(s), front_end(d)]
 
 
 def stage_shares(st, match_margin):

@@ -165,6 +165,26 @@ def test_gpu_single_pair_inputs_are_decided():
     assert margin >= G.UNDECIDED_RANSAC and r["correspondences"] < R.MIN_CORRESPONDENCES
 
 
+@pytest.mark.parametrize("name", ("volume", "volume_full", "clutter", "far"))
+def test_new_inputs_are_decided(name):
+    """global_reg_ref's NEW_PAIRS that the GPU test runs FGR on: the matches both ways under the tie rule of G.matches, the tuple test and the
+    score.  The clutter pair's zero rows and one-neighbour rows repeat in BOTH clouds, so its reverse matches hold ties too."""
+    st = G.new_pair_stages(name)
+    front = tuple((x["ds"]["points"], x["fpfh"]["fpfh"]) for x in st)
+    tally = {}
+    margin, r = _decided(front, name != "volume_full", 3, 0, tally)
+    tied = [int(G.matches(front[a][1], front[b][1], with_ties=True)[2].sum()) for a, b in ((0, 1), (1, 0))]
+    print("%s: smallest tuple / score margin %.3g, %d mutual matches, %d correspondences in %d trials, fitness %.3f; tied matches %d forward, %d reverse; %s"
+          % (name, margin, len(r["cross"]), r["correspondences"], r["trials"], r["fitness"], tied[0], tied[1], tally))
+    assert margin >= G.UNDECIDED_RANSAC and r["correspondences"] >= R.MIN_CORRESPONDENCES
+    for key, (s, n) in tally.items():
+        assert s <= G.SKIP_CAP / 10 * n, (key, s, n)
+    if name == "clutter":
+        assert min(tied) >= 30
+    else:
+        assert tied == [0, 0]
+
+
 def test_restatement_degenerate_inputs():
     empty = np.zeros((0, 3), np.float32)
     src, dst, _ = G.car_pairs(1, seed=5, n_points=600, scale=0.2)

@@ -6,7 +6,9 @@ Pinned-oracle method, as tests/test_global_reg_gpu.py: every step of the restate
 skipped, at most G.SKIP_CAP of them; a pair whose smallest tuple-test or score margin is below G.UNDECIDED_RANSAC is undecided, at most one of
 the 8 pairs per estimate form (tests/test_fgr_cpu.py asserts that on these inputs the restatement alone finds a tenth of the first cap and no
 undecided pair).  Transforms are held to 1e-9, the bar of tests/test_global_reg_gpu.py and tests/test_icp_gpu.py.  Stages 1-5 (downsample
-to the forward matches) are the kernels tests/test_global_reg_gpu.py checks; here the forward matches are compared like the reverse ones."""
+to the forward matches) are the kernels tests/test_global_reg_gpu.py checks; here the forward matches are compared like the reverse ones:
+a match between EQUAL rows is decided, the lowest index of the equal rows wins (global_reg_ref.matches).  The tests from test_new_pairs on
+run global_reg_ref's NEW_PAIRS (filled, cluttered and far clouds) and all kinds of clouds side by side in one batch."""
 import json
 import os
 import subprocess
@@ -33,16 +35,19 @@ def eng(gpu_required):
     e.close()
 
 
-def _check_pair(dev, constrained, decrease_mu, seed, stream, skipped, **opt):
+def _check_pair(dev, constrained, decrease_mu, seed, stream, skipped, ties=None, **opt):
     """One pair's stage outputs against the restatement's steps, each from the device's upstream outputs.  Adds (skipped, total) of the match
-    entries to `skipped`; returns False when the pair is undecided (a tuple-test or score margin below G.UNDECIDED_RANSAC)."""
+    entries to `skipped`, and to `ties` the number of matches checked as ties between equal rows; returns False when the pair is undecided (a
+    tuple-test or score margin below G.UNDECIDED_RANSAC)."""
     mcd, its = opt.get("maximum_correspondence_distance", R.MAX_CORR_DIST), opt.get("iteration_number", R.ITERATIONS)
     sp, tp = dev["points"]
     for name, key, (fa, fb) in (("matches", "matches", (0, 1)), ("reverse matches", "reverse_matches", (1, 0))):
-        m, mm = G.matches(dev["fpfh"][fa], dev["fpfh"][fb])
+        m, mm, tied = G.matches(dev["fpfh"][fa], dev["fpfh"][fb], with_ties=True)
         und = mm < G.UNDECIDED
         s = skipped.setdefault(name, [0, 0]); s[0] += int(und.sum()); s[1] += und.size
         assert np.array_equal(dev[key][~und], m[~und]), name
+        if ties is not None:
+            ties[name] = ties.get(name, 0) + int((tied & ~und).sum())
     cross = R.cross_check(dev["matches"], dev["reverse_matches"])
     assert np.array_equal(dev["cross"], cross)
     means, scale = R.normalise(sp, tp)
@@ -146,6 +151,51 @@ def test_defaults_large_and_degenerate(eng):
     np.testing.assert_allclose(dev["transform"][:3, 3], dev["means"][1] - dev["means"][0], rtol=0, atol=1e-12)
     dev = eng.debug_fgr_stages(empty, dst[0])
     assert dev["correspondences"] == 0 and len(dev["cross"]) == 0 and np.array_equal(dev["transform"], np.eye(4))
+
+
+@pytest.mark.parametrize("name", ["volume", "volume_full", "clutter", "far"])
+def test_new_pairs(eng, name):
+    """Filled boxes (both max_nn cuts, the candidate spill), the cluttered object (zero and one-neighbour feature rows: ties in the matches
+    BOTH ways, and a 15 m cloud under the 0.025 m score grid) and the far frame, step by step."""
+    s, d, truth = G.new_pair(name)
+    constrained = name != "volume_full"
+    dev = eng.debug_fgr_stages(s, d, constrained=constrained, seed=3, stream=0)
+    skipped, ties = {}, {}
+    assert _check_pair(dev, constrained, False, 3, 0, skipped, ties)
+    for stage, (sk, n) in skipped.items():
+        print("%s: %d of %d entries undecided, %d checked as ties" % (stage, sk, n, ties[stage]))
+        assert sk <= G.SKIP_CAP * n, stage
+    assert dev["correspondences"] >= R.MIN_CORRESPONDENCES
+    if name == "clutter":
+        assert min(ties.values()) >= 30
+        assert G.grid_cells(dev["points"][1], R.MAX_CORR_DIST) > G.MAX_GRID_CELLS
+    if name in ("clutter", "far"):
+        E = np.linalg.inv(truth) @ dev["transform"]
+        print("fitness %.3f, yaw error %.4f" % (dev["fitness"], abs(np.arctan2(E[1, 0], E[0, 0]))))
+        assert dev["fitness"] > 0.9 and abs(np.arctan2(E[1, 0], E[0, 0])) < 0.02
+
+
+def test_heterogeneous_batch(eng):
+    """A 24,000-point volume, three points, the cluttered object, an empty cloud and a plain object in one call: the stage arrays are strided
+    by the largest cloud while three pairs are tiny.  Every output of every pair is bit for bit what the pair gives alone and through the
+    stage hook."""
+    vs, vd, _ = G.volume_pair(True)
+    cs, cd, _ = G.clutter_pair()
+    src, dst, _ = G.gpu_test_pairs(True)
+    empty = np.zeros((0, 3), np.float32)
+    S, D = [vs, src[0][:3], cs, empty, src[1]], [vd, dst[0], cd, dst[1], dst[1]]
+    streams = [0, 12, 0, 14, 15]
+    batch = eng.fgr_register(S, D, streams=streams, seed=3)
+    print("correspondences", batch["correspondences"], "trials", batch["trials"], "fitness", batch["fitness"])
+    assert batch["correspondences"][0] >= R.MIN_CORRESPONDENCES and batch["correspondences"][2] == 3 * R.MAX_TUPLES
+    assert batch["correspondences"][3] == 0 and batch["fitness"][3] == 0.0
+    for i in range(5):
+        alone = eng.fgr_register([S[i]], [D[i]], streams=[streams[i]], seed=3)
+        dbg = eng.debug_fgr_stages(S[i], D[i], stream=streams[i], seed=3)
+        for k in KEYS:
+            assert np.array_equal(alone[k][0], batch[k][i]), (i, k)
+        for k, kd in zip(KEYS, ("transform", "fitness", "rmse", "correspondences", "trials")):
+            assert np.array_equal(dbg[kd], batch[k][i]), (i, k)
 
 
 def test_arguments(eng):

@@ -1,7 +1,11 @@
 """CPU: the restatement of the global registration (tests/global_reg_ref.py: FPFH + RANSAC, the reference's o3_gicp baseline) on its own --
 the generator's vectors, planted motions recovered, and the check that the skip caps of tests/test_global_reg_gpu.py hide nothing: on every
 input set the GPU tests use, the restatement alone finds at most a tenth of the cap of undecided entries per stage, and no undecided
-RANSAC pair.  Plus the new symbols' header / ctypes agreement and the icp_global.py command's refusal of configs it does not accept."""
+RANSAC pair.  The inputs that reach the max_nn cuts, the candidate spill, isolated points, tied matches, the growing grid and a far frame
+(global_reg_ref's NEW_PAIRS) are checked three ways: they reach those paths and the older inputs do not, the restatement alone decides them,
+and two wrong kernels restated here move their results by far more than the GPU tolerances.  Plus the new symbols' header / ctypes agreement
+and the icp_global.py command's refusal of configs it does not accept."""
+import functools
 import json
 import os
 import re
@@ -79,6 +83,10 @@ def test_gpu_test_inputs_are_decided(constrained):
     assert all(v <= G.SKIP_CAP / 10 for v in shares.values()), shares
     assert margin >= G.UNDECIDED_RANSAC           # no undecided pair among the 8
     assert all(r["fitness"] > 0.9 and r["validations"] == G.TEST_VALIDATIONS for r in runs)
+    # no two target rows are equal here: the tie rule of `matches` returns what the plain best / second-best rule did
+    for r in runs:
+        idx, margin = _matches_without_tie_rule(r["stages"][0]["fpfh"]["fpfh"], r["stages"][1]["fpfh"]["fpfh"])
+        assert np.array_equal(idx, r["matches"]) and np.array_equal(margin, r["match_margin"]) and not r["match_tied"].any()
 
 
 def test_gpu_single_pair_inputs_are_decided():
@@ -93,6 +101,169 @@ def test_gpu_single_pair_inputs_are_decided():
         shares, margin = _shares([r])
         assert all(v <= G.SKIP_CAP / 10 for v in shares.values()), shares
         assert margin >= G.UNDECIDED_RANSAC
+
+
+def _matches_without_tie_rule(fs, ft):
+    """`matches` as it was before equal target rows were grouped: nearest row, margin = gap between the best and the second-best distance."""
+    ms, mt = len(fs), len(ft)
+    idx, margin = np.zeros(ms, np.int64), np.full(ms, np.inf)
+    for s in range(0, ms, 64):
+        d = ((fs[s:s + 64, None, :] - ft[None, :, :]) ** 2).sum(-1)
+        idx[s:s + 64] = d.argmin(1)
+        part = np.partition(d, 1, axis=1)
+        margin[s:s + 64] = (part[:, 1] - part[:, 0]) / np.maximum(part[:, 1], 1e-300)
+    return idx, margin
+
+
+def test_matches_tie_rule():
+    ft = np.array([[3.0, 0.0], [1.0, 0.0], [0.0, 0.0], [1.0, 0.0], [0.0, 0.0], [1.0, 0.0]])
+    fs = np.array([[0.9, 0.0], [0.0, 0.0], [2.0, 0.0], [10.0, 0.0]])
+    idx, margin, tied = G.matches(fs, ft, with_ties=True)
+    # rows 1, 3, 5 are one candidate, rows 2, 4 another, row 0 stands alone; [2, 0] is as far from the group {1, 3, 5} as from row 0
+    assert idx.tolist() == [1, 2, 0, 0] and tied.tolist() == [True, True, False, False]
+    np.testing.assert_allclose(margin[[0, 1, 3]], [(0.81 - 0.01) / 0.81, 1.0, (81.0 - 49.0) / 81.0], rtol=1e-12)
+    assert margin[2] == 0.0                      # equal distances to rows that differ: still undecided
+    assert G.matches(fs, ft)[0].tolist() == idx.tolist() and np.array_equal(G.matches(fs, ft)[1], margin)
+    idx, margin, tied = G.matches(fs, ft[[1, 3, 5]], with_ties=True)     # every row in the group
+    assert idx.tolist() == [0, 0, 0, 0] and np.all(np.isinf(margin)) and tied.all()
+    idx, margin, tied = G.matches(fs, ft[:1], with_ties=True)
+    assert idx.tolist() == [0, 0, 0, 0] and np.all(np.isinf(margin)) and not tied.any()
+    assert G.matches(fs, ft[:0], with_ties=True)[0].tolist() == [0, 0, 0, 0] and len(G.matches(fs[:0], ft)[0]) == 0
+
+
+# ---- the inputs of NEW_PAIRS -------------------------------------------------------------------------------------------------------------
+# (constrained, seed, stream, max_iteration, max_validation) of the GPU tests' RANSAC on them
+NEW_RANSAC = {"volume": (True, 3, 0, G.VOLUME_ITERATIONS, G.VOLUME_VALIDATIONS), "volume_full": (False, 3, 0, G.VOLUME_ITERATIONS, G.VOLUME_VALIDATIONS),
+              "clutter": (True, 3, 0, G.TEST_ITERATIONS, G.TEST_VALIDATIONS), "far": (True, 3, 0, G.TEST_ITERATIONS, G.TEST_VALIDATIONS),
+              "wide": (True, 3, 0, G.WIDE_ITERATIONS, G.WIDE_VALIDATIONS)}
+
+
+@functools.lru_cache(maxsize=None)
+def _new_run(name):
+    s, d, _ = G.new_pair(name)
+    return G.global_register(s, d, *NEW_RANSAC[name], stages=G.new_pair_stages(name))
+
+
+def _counts(name):
+    """Per cloud (in-radius counts at 0.10, at 0.25) before any cut."""
+    return [(G.radius_counts(st["ds"]["points"], 2 * G.VOXEL), G.radius_counts(st["ds"]["points"], 5 * G.VOXEL)) for st in G.new_pair_stages(name)]
+
+
+def test_new_inputs_reach_the_paths_and_the_old_ones_do_not():
+    for name in ("volume", "volume_full"):
+        for c10, c25 in _counts(name):
+            print(name, len(c10), "points:", int((c10 > 30).sum()), "above 30 at 0.10 (max %d)," % c10.max(), int((c25 > G.CAND_LDS).sum()),
+                  "above %d at 0.25 (max %d, min %d)" % (G.CAND_LDS, c25.max(), c25.min()))
+            assert (c10 > 30).sum() >= 500 and (c25 > G.CAND_LDS).sum() >= 500 and c25.min() > 100
+    for side, (c10, c25) in enumerate(_counts("clutter")):
+        print("clutter", len(c10), "points: K < 3 at 0.10:", int((c10 < 3).sum()), " K < 2 at 0.25:", int((c25 < 2).sum()), " K == 2 at 0.25:", int((c25 == 2).sum()))
+        assert (c25 < 2).sum() >= 10 and (c25 == 2).sum() >= 10 and (c10 < 3).sum() >= 10
+    r = _new_run("clutter")
+    tp = r["stages"][1]["ds"]["points"]
+    print("clutter: %d of %d matches tied; %d cells at 1.001 tau over %s m" % (r["match_tied"].sum(), len(r["match_tied"]), G.grid_cells(tp), tp.max(0) - tp.min(0)))
+    assert r["match_tied"].sum() >= 30 and G.grid_cells(tp) > G.MAX_GRID_CELLS
+    assert np.array_equal(r["matches"][r["match_tied"]], _matches_without_tie_rule(r["stages"][0]["fpfh"]["fpfh"], r["stages"][1]["fpfh"]["fpfh"])[0][r["match_tied"]])
+    s, d, _ = G.far_pair()
+    mg = np.concatenate([st["ds"]["margin"] for st in G.new_pair_stages("far")])
+    print("far: %d of %d raw points within 1e-9 bin widths of a voxel edge, the nearest at %.3g" % ((mg < 1e-9).sum(), mg.size, mg.min()))
+    # decided in fp64: the pre-floor value is at most 30, its one rounding (the division; the subtraction is exact) at most 30 * 1.2e-16
+    assert (mg < 1e-9).sum() >= 1 and mg.min() > 1e-13
+    # in fp32 the same floor is not decided: its rounding is 30 * 6e-8, eight orders above these margins
+    assert mg.min() < 30 * 2.0 ** -24
+    s, d, _ = G.wide_pair()
+    span = (d.astype(np.float64).max(0) - d.astype(np.float64).min(0))[0]
+    assert G.grid_cells(G.new_pair_stages("wide")[1]["ds"]["points"]) > G.MAX_GRID_CELLS and 100000 < span + G.VOXEL < (1 << 21) * G.VOXEL
+    w = G.too_wide_cloud()
+    assert (w.max(0) - w.min(0))[0] + G.VOXEL / 2 > (1 << 21) * G.VOXEL
+    # why these inputs exist: on everything the GPU tests ran before, no neighbourhood is cut to the 30 nearest, none spills, and no point has
+    # fewer than three points (itself included) within 0.25; nor does any target cloud need more cells than the grid has
+    old = []
+    for constrained in (True, False):
+        src, dst, _ = G.gpu_test_pairs(constrained)
+        old += src + dst
+    old += list(G.default_pair()[:2]) + list(G.large_pair()[:2])
+    top10, top25, low25 = 0, 0, 1 << 30
+    for pc in old:
+        P = G.voxel_downsample(pc)["points"]
+        c10, c25 = G.radius_counts(P, 2 * G.VOXEL), G.radius_counts(P, 5 * G.VOXEL)
+        top10, top25, low25 = max(top10, c10.max()), max(top25, c25.max()), min(low25, c25.min())
+    print("older inputs: at most %d within 0.10, between %d and %d within 0.25" % (top10, low25, top25))
+    assert top10 <= 30 and top25 <= G.CAND_LDS and low25 >= 3
+
+
+@pytest.mark.parametrize("name", G.NEW_PAIRS)
+def test_new_inputs_are_decided(name):
+    r = _new_run(name)
+    shares = G.stage_shares(r["stages"], r["match_margin"])
+    print(name, [len(st["ds"]["points"]) for st in r["stages"]], shares, "RANSAC: validations %d iterations %d fitness %.4f margin %.3g"
+          % (r["validations"], r["iterations"], r["fitness"], r["margin"]))
+    if name == "far":
+        # its voxel edges are the point of it: the floor is compared exactly on the GPU, never skipped, and
+        # test_new_inputs_reach_the_paths_and_the_old_ones_do_not holds every margin above the fp64 rounding
+        assert 0 < shares.pop("voxel")
+    assert all(v <= G.SKIP_CAP / 10 for v in shares.values()), shares
+    assert r["margin"] >= G.UNDECIDED_RANSAC
+    assert r["validations"] >= 1
+    if name in ("clutter", "far"):
+        assert r["fitness"] > 0.9 and r["validations"] == G.TEST_VALIDATIONS
+    if name == "wide":
+        assert r["validations"] == G.WIDE_VALIDATIONS
+
+
+# ---- teeth: two wrong neighbour kernels, restated ------------------------------------------------------------------------------------------
+def _wrong_neighbours(mode):
+    """G.neighbours as a wrong kernel would compute it.  "first": the cut keeps the first max_nn candidates in index order instead of the
+    nearest.  "lost_spill": the nearest max_nn are taken among the first CAND_LDS candidates only -- what ranking the LDS copy alone, or a
+    spill that other lanes never see, amounts to.  Candidates come in ascending index, as the kernel's slab scan finds them."""
+    true = G.neighbours
+
+    def wrong(points, radius, max_nn):
+        I, J, D, count, margin = true(points, radius, len(points) + 1)
+        starts = np.r_[0, np.cumsum(count)]
+        keep = []
+        for i in range(len(points)):
+            sel = np.arange(starts[i], starts[i + 1])
+            if len(sel) > max_nn:
+                if mode == "first":
+                    sel = sel[:max_nn]
+                else:
+                    sel = sel[:G.CAND_LDS] if len(sel) > G.CAND_LDS else sel
+                    sel = sel[np.lexsort((J[sel], D[sel]))][:max_nn]
+            keep.append(sel)
+        keep = np.concatenate(keep)
+        return I[keep], J[keep], D[keep], np.minimum(count, max_nn), margin
+    return wrong
+
+
+# Measured on volume_pair(True) when the test was written, per cloud (source, target): the share of the AFFECTED points (more than max_nn
+# within the radius for "first", more than CAND_LDS for "lost_spill") whose result moves by more than ten times the GPU tolerance.
+#   "first", normals (max_nn 30, moved by more than 1e-7):       0.9488, 0.9668 of 860 / 843 points.  The rest are points with 31 or 32
+#       candidates whose farthest ones come last in index order too (the index ascends with x): the wrong cut then keeps the right set
+#   "first", FPFH rows (max_nn 100, moved by more than 1e-6):    1.0, 1.0 of 2140 / 2202
+#   "lost_spill", FPFH rows (max_nn 100, more than 1e-6):        1.0, 1.0 of 1036 / 1089
+# Asserted as floors; anything below one half would mean the input is too sparse to tell these kernels from the right one.
+TEETH = {("first", "normals"): 0.94, ("first", "fpfh"): 1.0, ("lost_spill", "fpfh"): 1.0}
+
+
+def test_wrong_cuts_would_be_caught(monkeypatch):
+    shares = {}
+    for side, st in enumerate(G.new_pair_stages("volume")):
+        P, N = st["ds"]["points"], st["normals"]["normals"]
+        c10, c25 = _counts("volume")[side]
+        for mode in ("first", "lost_spill"):
+            with monkeypatch.context() as mp:
+                mp.setattr(G, "neighbours", _wrong_neighbours(mode))
+                if mode == "first":
+                    moved = np.abs(G.normals(P)["normals"] - N).max(1) > 10 * 1e-8
+                    shares.setdefault((mode, "normals"), []).append(float(moved[c10 > 30].mean()))
+                sp = G.spfh(P, N)["spfh"]
+                moved = np.abs(G.fpfh(P, sp)["fpfh"] - st["fpfh"]["fpfh"]).max(1) > 10 * 1e-7
+            affected = c25 > (100 if mode == "first" else G.CAND_LDS)
+            print(mode, "side", side, "affected:", int((c10 > 30).sum()), "normals,", int(affected.sum()), "FPFH rows")
+            shares.setdefault((mode, "fpfh"), []).append(float(moved[affected].mean()))
+    print(shares)
+    for key, floor in TEETH.items():
+        assert min(shares[key]) >= floor >= 0.5, (key, shares[key])
 
 
 def test_restatement_edge_cases():

@@ -5,7 +5,12 @@ Pinned-oracle method: every stage of the restatement is FED THE DEVICE'S OWN UPS
 flipped decision cannot cascade.  An entry whose decision margin (global_reg_ref's docstring) is below 1e-9 (1e-6 for the normals'
 eigenvalue gap) is undecided and skipped; a stage may skip at most 1e-3 of its entries (tests/test_global_reg_cpu.py asserts that on these
 inputs the restatement alone finds at most a tenth of that).  A RANSAC pair whose smallest comparison margin is below 1e-10 is undecided;
-at most one of the 8 pairs per estimate form may be."""
+at most one of the 8 pairs per estimate form may be.  A match between EQUAL target rows is decided: the lowest index of the equal rows wins
+(global_reg_ref.matches).
+
+The thin surfaces of gpu_test_pairs / default_pair / large_pair never fill a neighbourhood; global_reg_ref's NEW_PAIRS do (the tests from
+test_volume_pair on): both max_nn cuts and the candidate spill to HBM, isolated points, tied matches, a validation grid whose cell has to
+grow, the voxel-span limit, a frame kilometres from the origin, and all of them side by side in one batch."""
 import json
 import os
 import subprocess
@@ -32,7 +37,8 @@ def eng(gpu_required):
 
 
 def _check_front_end(dev, src, dst, skipped):
-    """Stages 1-4 of one pair; adds (skipped, total) per stage to `skipped`."""
+    """Stages 1-5 of one pair; adds (skipped, total) per stage to `skipped`.  Returns which matches were checked as ties between equal target
+    rows (the lowest index of the equal rows is what they were compared with)."""
     def tally(stage, undecided):
         s = skipped.setdefault(stage, [0, 0])
         s[0] += int(undecided.sum()); s[1] += undecided.size
@@ -56,10 +62,11 @@ def _check_front_end(dev, src, dst, skipped):
         und = fp["nbr_margin"] < G.UNDECIDED
         tally("fpfh", und)
         np.testing.assert_allclose(dev["fpfh"][side][~und], fp["fpfh"][~und], rtol=0, atol=1e-7)
-    m, mm = G.matches(dev["fpfh"][0], dev["fpfh"][1])
+    m, mm, tied = G.matches(dev["fpfh"][0], dev["fpfh"][1], with_ties=True)
     und = mm < G.UNDECIDED
     tally("matches", und)
     assert np.array_equal(dev["matches"][~und], m[~und])
+    return tied & ~und
 
 
 def _check_ransac(dev, constrained, seed, stream, max_iteration, max_validation):
@@ -188,6 +195,136 @@ def test_edge_cases(eng):
                                       out.ctypes.data_as(C.POINTER(C.c_double)), None, None, None, None)   # NULL streams = stream 0
     assert rc == 0
     assert np.array_equal(out.reshape(4, 4), eng.global_register(src[:1], dst[:1], max_iteration=20000, max_validation=5)["transforms"][0])
+
+
+# ---- filled, cluttered, far and wide clouds (global_reg_ref.NEW_PAIRS; tests/test_global_reg_cpu.py holds what they reach and that the
+# ---- restatement alone decides them) ---------------------------------------------------------------------------------------------------
+def _report(skipped):
+    for stage, (s, n) in skipped.items():
+        print("stage %s: %d of %d entries undecided" % (stage, s, n))
+        assert s <= G.SKIP_CAP * n, stage
+
+
+@pytest.mark.parametrize("constrained", [True, False])
+def test_volume_pair(eng, constrained):
+    """Every neighbourhood of the features is cut to its 100 nearest, half of them after more than kCandLds candidates (ranked from HBM), and
+    40 % of the normals' to their 30 nearest."""
+    s, d, _ = G.volume_pair(constrained)
+    dev = eng.debug_global_stages(s, d, constrained=constrained, seed=3, stream=0, max_iteration=G.VOLUME_ITERATIONS, max_validation=G.VOLUME_VALIDATIONS)
+    for P in dev["points"]:
+        c10, c25 = G.radius_counts(P, 2 * G.VOXEL), G.radius_counts(P, 5 * G.VOXEL)
+        assert (c10 > 30).sum() >= 500 and (c25 > G.CAND_LDS).sum() >= 500 and c25.min() > 100
+    skipped = {}
+    _check_front_end(dev, s, d, skipped)
+    _report(skipped)
+    assert _check_ransac(dev, constrained, 3, 0, G.VOLUME_ITERATIONS, G.VOLUME_VALIDATIONS)
+    assert dev["validations"] >= 1
+
+
+def test_clutter_pair(eng):
+    """Stray points around the object: default normals and all-zero feature rows where nothing is near, the one-neighbour histogram, matches
+    tied between equal rows, and a 15 m cloud for the validation grid (9 million cells at the threshold's size; it holds 32,768)."""
+    s, d, truth = G.clutter_pair()
+    dev = eng.debug_global_stages(s, d, seed=3, stream=0, max_iteration=G.TEST_ITERATIONS, max_validation=G.TEST_VALIDATIONS)
+    skipped = {}
+    tied = _check_front_end(dev, s, d, skipped)
+    _report(skipped)
+    print("tied matches checked: %d of %d" % (tied.sum(), tied.size))
+    assert tied.sum() >= 30
+    for side in range(2):
+        P = dev["points"][side]
+        for radius, name in ((2 * G.VOXEL, "normals"), (5 * G.VOXEL, "fpfh")):
+            assert (G.neighbours(P, radius, len(P) + 1)[4] >= G.UNDECIDED).all()      # every count below is decided
+        c10, c25 = G.radius_counts(P, 2 * G.VOXEL), G.radius_counts(P, 5 * G.VOXEL)
+        print("side %d: %d points with K < 3 at 0.10, %d with K < 2 and %d with K == 2 at 0.25" % (side, (c10 < 3).sum(), (c25 < 2).sum(), (c25 == 2).sum()))
+        assert (c10 < 3).sum() >= 10 and (c25 < 2).sum() >= 10 and (c25 == 2).sum() >= 10
+        assert np.array_equal(dev["normals"][side][c10 < 3], np.tile([0.0, 0.0, 1.0], ((c10 < 3).sum(), 1)))
+        for key in ("spfh", "fpfh"):
+            F = dev[key][side]
+            assert not F[c25 < 2].any() and (np.abs(F[c25 >= 2]).sum(1) > 0).all(), key
+        # one neighbour: three bins of exactly 100 / (K - 1) = 100
+        assert np.array_equal(np.sort(dev["spfh"][side][c25 == 2], 1)[:, -4:], np.tile([0.0, 100.0, 100.0, 100.0], ((c25 == 2).sum(), 1)))
+    assert G.grid_cells(dev["points"][1]) > G.MAX_GRID_CELLS
+    assert _check_ransac(dev, True, 3, 0, G.TEST_ITERATIONS, G.TEST_VALIDATIONS)
+    E = np.linalg.inv(truth) @ dev["transform"]
+    assert dev["fitness"] > 0.9 and abs(np.arctan2(E[1, 0], E[0, 0])) < 0.02
+
+
+def test_far_pair(eng):
+    """4 km from the origin float32 coordinates are 2.4e-4 m apart and raw points sit on voxel edges up to the rounding of 0.05 and 0.025: the
+    voxels and their counts are compared exactly (an fp32 floor, or a reciprocal in place of the division, puts those points elsewhere)."""
+    s, d, truth = G.far_pair()
+    dev = eng.debug_global_stages(s, d, seed=3, stream=0, max_iteration=G.TEST_ITERATIONS, max_validation=G.TEST_VALIDATIONS)
+    edge = 0
+    for side, raw in enumerate((s, d)):
+        ds = G.voxel_downsample(raw)
+        edge += int((ds["margin"] < 1e-9).sum())
+        assert ds["margin"].min() > 1e-13
+        assert dev["counts"][side] == len(ds["points"])
+        assert np.array_equal(dev["voxels"][side], ds["voxels"]) and np.array_equal(dev["voxel_points"][side], ds["counts"])
+    print("raw points within 1e-9 bin widths of a voxel edge: %d" % edge)
+    assert edge >= 1
+    skipped = {}
+    _check_front_end(dev, s, d, skipped)
+    _report(skipped)
+    assert _check_ransac(dev, True, 3, 0, G.TEST_ITERATIONS, G.TEST_VALIDATIONS)
+    E = np.linalg.inv(truth) @ dev["transform"]
+    assert dev["fitness"] > 0.9 and abs(np.arctan2(E[1, 0], E[0, 0])) < 0.02
+
+
+def test_wide_pair_and_span_limit(eng):
+    """One point 100,000 m away: 2,000,000 voxels, inside the limit, and a validation grid whose cell grows from 0.075 m to metres.  Two
+    points 110,000 m apart are more than 2^21 voxels: refused, and the engine computes afterwards what it computed before."""
+    s, d, _ = G.wide_pair()
+    kw = dict(seed=3, stream=0, max_iteration=G.WIDE_ITERATIONS, max_validation=G.WIDE_VALIDATIONS)
+    dev = eng.debug_global_stages(s, d, **kw)
+    assert dev["voxels"][1][:, 0].max() >= 2000000 and G.grid_cells(dev["points"][1]) > G.MAX_GRID_CELLS
+    skipped = {}
+    _check_front_end(dev, s, d, skipped)
+    _report(skipped)
+    assert _check_ransac(dev, True, 3, 0, G.WIDE_ITERATIONS, G.WIDE_VALIDATIONS)
+    assert dev["validations"] == G.WIDE_VALIDATIONS
+    src, dst, _ = G.gpu_test_pairs(True)
+    batch = dict(seed=3, streams=[0, 7], max_iteration=G.WIDE_ITERATIONS, max_validation=G.WIDE_VALIDATIONS)
+    before = eng.global_register([s, src[0]], [d, dst[0]], **batch)
+    wide = G.too_wide_cloud()
+    for a, b in ((wide, dst[0]), (src[0], wide)):
+        with pytest.raises(RuntimeError, match=r"2\^21 voxels"):
+            eng.global_register([src[1], a], [dst[1], b], **batch)
+        with pytest.raises(RuntimeError, match=r"2\^21 voxels"):
+            eng.debug_global_stages(a, b, **kw)
+    after = eng.global_register([s, src[0]], [d, dst[0]], **batch)
+    for k in KEYS:
+        assert np.array_equal(before[k], after[k]), k
+    again = eng.debug_global_stages(s, d, **kw)
+    for k in ("transform", "matches"):
+        assert np.array_equal(again[k], dev[k]), k
+    for k in ("points", "normals", "spfh", "fpfh"):
+        assert all(np.array_equal(x, y) for x, y in zip(again[k], dev[k])), k
+
+
+def test_heterogeneous_batch(eng):
+    """A 24,000-point volume, three points, the cluttered object, an empty cloud and a plain object in one call: the stage arrays are strided
+    by the largest cloud while three pairs are tiny.  Every output of every pair is bit for bit what the pair gives alone and through the
+    stage hook."""
+    vs, vd, _ = G.volume_pair(True)
+    cs, cd, _ = G.clutter_pair()
+    src, dst, _ = G.gpu_test_pairs(True)
+    empty = np.zeros((0, 3), np.float32)
+    S, D = [vs, src[0][:3], cs, empty, src[1]], [vd, dst[0], cd, dst[1], dst[1]]
+    streams = [0, 12, 0, 14, 15]            # the volume and the clutter pair as their own tests draw them: validations are known to be reached
+    kw = dict(seed=3, max_iteration=G.VOLUME_ITERATIONS, max_validation=G.VOLUME_VALIDATIONS)
+    batch = eng.global_register(S, D, streams=streams, **kw)
+    print("validations", batch["validations"], "fitness", batch["fitness"])
+    assert batch["validations"][0] >= 1 and batch["validations"][2] == G.VOLUME_VALIDATIONS
+    assert batch["fitness"][1] == 0.0 and batch["fitness"][3] == 0.0
+    for i in range(5):
+        alone = eng.global_register([S[i]], [D[i]], streams=[streams[i]], **kw)
+        dbg = eng.debug_global_stages(S[i], D[i], stream=streams[i], **kw)
+        for k in KEYS:
+            assert np.array_equal(alone[k][0], batch[k][i]), (i, k)
+        for k, kd in zip(KEYS, ("transform", "fitness", "rmse", "iterations", "validations")):
+            assert np.array_equal(dbg[kd], batch[k][i]), (i, k)
 
 
 # ---- the command, then train.py's refine step from its files ------------------------------------------------------------------------
