@@ -623,17 +623,27 @@ class Engine:
         assert hasattr(self, "_scene_offsets") and lab.shape[0] == self._scene_offsets.shape[0] - 1, "one label row per generated scene"
         self._check(self._lib.alignnet_scene_install_dataset(self._h, _fp(lab)))
 
-    def debug_scene_cast(self, mesh, scale, pose, lds_triangles=0):
+    def debug_scene_cast(self, mesh, scale, pose, lds_triangles=0, binned=False):
         """Test hook: ONE cloud by the shipped cast kernel, no noise.  Returns dict(t [64, 4500] float64 (inf = miss), triangle [64, 4500] (-1), window =
-        (first column, columns), lds_triangles as used).  lds_triangles in 1 .. 512 forces several LDS chunks on small meshes."""
+        (first column, columns), lds_triangles as used).  lds_triangles in 1 .. 512 forces several LDS chunks on small meshes.  binned=False: the scan;
+        True: the binned cast (set_option("scene_cast", 1) selects it for scene_generate; this read-back takes it whatever the option says), and the
+        dict also holds tile_counts [tiles of the window] (the length of every tile's triangle list) and entries (their sum)."""
         pose = np.ascontiguousarray(pose, np.float64).reshape(4)
         t, tri = np.empty(64 * 4500, np.float64), np.empty(64 * 4500, np.int32)
         win, used = np.zeros(2, np.int32), np.zeros(1, np.int32)
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        self._check(self._lib.alignnet_debug_scene_cast(self._h, int(mesh), float(scale), pose.ctypes.data_as(C.POINTER(C.c_double)), int(lds_triangles),
-                                                        t.ctypes.data_as(C.POINTER(C.c_double)), ip(tri), ip(win), ip(used)))
+        args = (self._h, int(mesh), float(scale), pose.ctypes.data_as(C.POINTER(C.c_double)), int(lds_triangles),
+                t.ctypes.data_as(C.POINTER(C.c_double)), ip(tri), ip(win), ip(used))
+        if binned:
+            counts, entries = np.zeros(563, np.int32), C.c_int64(0)
+            self._check(self._lib.alignnet_debug_scene_cast_binned(*args, ip(counts), C.byref(entries)))
+        else:
+            self._check(self._lib.alignnet_debug_scene_cast(*args))
         self.__dict__.pop("_scene_offsets", None)
-        return dict(t=t.reshape(64, 4500), triangle=tri.reshape(64, 4500), window=(int(win[0]), int(win[1])), lds_triangles=int(used[0]))
+        out = dict(t=t.reshape(64, 4500), triangle=tri.reshape(64, 4500), window=(int(win[0]), int(win[1])), lds_triangles=int(used[0]))
+        if binned:
+            out.update(tile_counts=counts[:(int(win[1]) + 7) // 8].copy(), entries=int(entries.value))
+        return out
 
     @staticmethod
     def read_device(ptr, count, dtype=np.float32):
@@ -821,7 +831,7 @@ class Engine:
 
     PROFILED_KERNELS = ("backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1",
                         "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact",
-                        "icp_grid_build", "icp_grid")
+                        "icp_grid_build", "icp_grid", "scene_bin")
 
     def profile_kernels(self):
         """{kernel: (ms, launches)} accumulated since the last profile_read(reset=True); call BEFORE that reset."""

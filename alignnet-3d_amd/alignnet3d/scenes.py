@@ -285,10 +285,26 @@ class MeshLibrary:
         return self.index[key]
 
 
-def generate(engine, scenes, seed=0, meshes="builtin", noise=True, sigma=0.05, clip=0.05, install=False):
+CASTS = {"scan": 0, "binned": 1, "auto": 2}   # engine option scene_cast (include/alignnet_hip.h)
+
+
+def cast_option(cast):
+    """The value of the engine option "scene_cast" for a cast name; ValueError for an unknown one."""
+    if cast not in CASTS:
+        raise ValueError("cast = %r: expected one of %s" % (cast, ", ".join(sorted(CASTS))))
+    return CASTS[cast]
+
+
+def generate(engine, scenes, seed=0, meshes="builtin", noise=True, sigma=0.05, clip=0.05, install=False, cast="scan"):
     """Cast `scenes` (draw_scene results) on the GPU.  The noise key of a scene is (seed, scene.seed): a scene's clouds do not depend on
     what else is in the list.  Returns the offsets table [B + 1, 2]; the clouds stay on the device -- engine.scene_read() copies them
-    out, install=True makes them the HBM-resident dataset (engine.sample_batch, train_step_rows, icp_refine_rows, ... work on it)."""
+    out, install=True makes them the HBM-resident dataset (engine.sample_batch, train_step_rows, icp_refine_rows, ... work on it).
+    cast: "scan" (every tile of a cloud's window goes through the whole mesh), "binned" (the triangles are binned to the tiles first) or
+    "auto" (binned for meshes of more than 512 triangles); it sets the engine option "scene_cast", which stays set.  The clouds are the same
+    bit for bit whichever is chosen; "binned" and "auto" are exact alternatives that were slower than "scan" at every mesh size measured
+    (516 to 100,002 triangles: profiles/scene_cast_rate.json)."""
+    option = cast_option(cast)
+    engine.set_option("scene_cast", option)
     lib = meshes if isinstance(meshes, MeshLibrary) else MeshLibrary(meshes)
     first = len(lib.meshes)
     ids = [lib.add(s.cat, s.mesh_id) for s in scenes]

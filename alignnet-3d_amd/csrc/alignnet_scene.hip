@@ -18,14 +18,39 @@
 //     difference array (integer atomics: order-free); a triangle whose xy projection holds the z axis covers all 4500.  The window is the complement of the
 //     largest uncovered gap of the circle of columns, so it may wrap 4499 -> 0.  The windows come back to the host (one small copy), which deals
 //     (cloud, tile of 8 window columns) work items: a batch of small far objects and one near object both become hundreds of workgroups.
-//  2. scene_cast_kernel, one workgroup (four waves) per tile; lane = elevation row, a wave takes two of the tile's columns.  The cloud's triangles go
-//     through LDS in chunks of 512: each is posed (Rz(angle) (scale v) + position, fp64), culled against the tile's azimuth sector by two exact side tests
+//  2. scene_cast_kernel (the SCAN, alignnet_set_option "scene_cast" = 0, the default), one workgroup (four waves) per tile; lane = elevation row, a wave
+//     takes two of the tile's columns.  The cloud's triangles go through LDS in chunks of 512: each is posed (Rz(angle) (scale v) + position, fp64), culled against the tile's azimuth sector by two exact side tests
 //     with a relative margin (all three vertices strictly before the first column's half plane, or strictly behind the last one's: conservative, so what is
-//     left is decided in fp64 as above), and the survivors' ten numbers are compacted into LDS (ballot prefix: deterministic order).  The inner loop reads
-//     one triangle as a broadcast and tests it against the wave's two columns.  Cost model: every tile poses and side-tests all T triangles of its cloud
+//     left is decided in fp64 as above), and the survivors' ten numbers are compacted into LDS (ballot prefix: deterministic order).  The inner loop
+//     (cast_triangle per staged triangle, shared with the binned cast) reads one triangle as a broadcast and tests it against the wave's two columns.  Cost model: every tile poses and side-tests all T triangles of its cloud
 //     (T / 256 per thread, latency-bound on the vertex gathers) and intersects 64 x 8 rays with the few that overlap its 0.64 deg sector; a car of some
-//     hundred triangles is one chunk, a 10^5-triangle model is 200 chunks per tile -- a per-cloud binning of triangles to tiles would remove the T / 256 term
-//     and is the next step if such models matter.  t per ray goes to a [row][window column] table (inf = miss).
+//     hundred triangles is one chunk, a 10^5-triangle model is 200 chunks per tile.  t per ray goes to a [row][window column] table (inf = miss).
+//  2b. the BINNED cast ("scene_cast" = 1: every cloud; 2: clouds of more than kSceneBinAuto triangles) removes the T / 256 term: per cloud the triangles
+//     are binned to the window's tiles once, and a tile poses only the triangles of its own list.
+//       scene_bin_tally_kernel    grid (cloud, slice of the mesh): every triangle is posed once, its tile range found (tri_reach: the WINDOW kernel's rule --
+//                                 the atan2 interval of its three vertices widened by kColMargin columns; every tile when its xy projection holds the z axis
+//                                 or it spans half the circle; a zero-area triangle reaches nothing and is dropped) and counted in an LDS histogram of the
+//                                 window's tiles, which is added onto the (cloud, tile) counters (integer atomics: order-free);
+//       scene_bin_offsets_kernel  one workgroup: exclusive scan of the counters into the 64-bit (cloud, tile) offset table, counters cleared; the total
+//                                 goes to the host (the one extra copy of a call), which grows the list buffer (4 bytes per entry);
+//       scene_bin_fill_kernel     the tally's grid and the tally's ranges again (the same function on the same numbers), a global atomic cursor per tile
+//                                 (the cleared counters) hands out the slots: the ORDER inside a list depends on the run, the SET does not;
+//       scene_bincast_kernel      one workgroup per (cloud, tile) as in the scan; walks the tile's list in chunks of lds_triangles, poses each listed
+//                                 triangle with the same pose() and tri_setup() (re-posing per entry: a table of posed triangles would be 88 B x T x
+//                                 clouds), stages the ten numbers in LDS and runs cast_triangle over them.  Equal t goes to the lower triangle index whatever the
+//                                 order, so the result does not depend on the fill order, and it is bit for bit the scan's.
+//     Why the lists are conservative: a ray of column c can only hit a triangle when its xy direction lies in the angular span of the triangle's xy
+//     projection as seen from the z axis.  When the projection does not hold the axis and spans less than half the circle, that span is the interval
+//     between the extreme vertex azimuths (the projection is convex); column c sits at column coordinate c to 1e-13, the interval is widened by 1e-6 column
+//     and rounded outwards to whole columns: the margin is seven orders of magnitude above atan2's error, and that alone makes the range conservative,
+//     whatever scene_window_kernel computed.  (It is also the rule by which the window is chosen -- a column outside every interval is cast by neither
+//     path -- but the scan culls inside the window by exact side tests, not by these intervals.)  A range that leaves the window (possible only if the
+//     two kernels rounded an interval's end differently) is clamped to it.
+//     Measured (tools/scene_cast_rate.py, profiles/scene_cast_rate.json; 512 clouds, whole calls): the binned cast is NOT ahead of the scan at 516, 5,001,
+//     20,001 or 100,002 triangles (0.79 - 0.95 x).  Both casts are bound by the inner loop -- every staged triangle against all 64 x 8 rays of the tile, about
+//     0.6 - 0.8 ns of chip time per (tile, triangle) entry -- and the scan's side tests leave it the same entries; the T / 256 term that binning removes is
+//     the small one (cast kernel 13.6 -> 12.8 ms at 20,001 triangles) and the binning costs more (1.6 ms there).  Fewer rays per entry -- binning by
+//     elevation row inside a tile, for which these lists are the input -- is the step that would pay.  The default stays the scan.
 //  3. scene_count_kernel (hits per (cloud, row)), scene_scan_kernel (exclusive scan in (scene, row) order per cloud index: the offsets table),
 //     scene_scatter_kernel (per (cloud, row): columns in ascending COLUMN order -- a wrapped window starts at column 0 -- ballot prefix, location = t d in
 //     fp64 rounded to float, + noise).  Counts, a scan, a scatter: no atomics that could reorder points.
@@ -48,6 +73,10 @@ int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1;
 constexpr int kRows = 64, kCols = 4500, kRays = kRows * kCols;
 constexpr int kTileCols = 8, kCastThreads = 256, kColsPerWave = kTileCols / (kCastThreads / 64);
 constexpr int kLdsTriangles = 512;        // triangles per LDS chunk as shipped (88 bytes each: three workgroups per CU)
+constexpr int kSceneBinAuto = kLdsTriangles;   // "scene_cast" = 2: clouds whose mesh has more triangles take the binned cast: where the scan leaves one LDS chunk,
+                                               // NOT a measured crossover (none exists up to 100,002 triangles: the header above)
+constexpr int kMaxTiles = (kCols + kTileCols - 1) / kTileCols;   // 563 tiles in the all-column window
+constexpr int kBinSlices = 32;            // most workgroups per cloud of the tally / fill kernels (256 triangles per pass each)
 constexpr double kColMargin = 1e-6;       // columns of margin around a triangle's azimuth interval (fp64 atan2 is good to 1e-13 column)
 constexpr double kSideMargin = 1e-12;     // relative margin of the side tests (their rounding error is 4e-16 of the same scale)
 
@@ -60,7 +89,8 @@ struct SceneCloud {
   long long tbase;                    // first entry of this cloud's [64][count] table of t
   unsigned long long scene_id;
   int nf, first, count, which;        // faces; window (first column, columns); cloud index 0 / 1
-  float strength; int pad;
+  float strength;
+  int bt0;                            // binned cast: the cloud's first entry in the (cloud, tile) offset table; -1: the cloud takes the scan
 };
 
 struct V3 { double x, y, z; };
@@ -192,6 +222,29 @@ __global__ __launch_bounds__(256) void scene_window_kernel(const SceneCloud* __r
   }
 }
 
+// the arithmetic of both casts: one staged triangle against the wave's columns of one elevation row (lane)
+__device__ __forceinline__ void cast_triangle(const SceneTri& t, const double (&dx)[kColsPerWave], const double (&dy)[kColsPerWave], double dz,
+                                              double (&best)[kColsPerWave], int (&bid)[kColsPerWave])
+{
+#pragma clang fp contract(off)
+  const double N0 = t.N[0], N1 = t.N[1], N2 = t.N[2], A0 = t.A[0], A1 = t.A[1], A2 = t.A[2], B0 = t.Bv[0], B1 = t.Bv[1], B2 = t.Bv[2], cc = t.c;
+  const int id = t.id;
+  const double nz = dz * N2, az = dz * A2, bz = dz * B2;
+#pragma unroll
+  for (int q = 0; q < kColsPerWave; ++q) {
+    const double den = (dx[q] * N0 + dy[q] * N1) + nz;
+    const double un = (dx[q] * A0 + dy[q] * A1) + az;
+    const double vn = (dx[q] * B0 + dy[q] * B1) + bz;
+    const double sum = un + vn;
+    const bool hit = den > 0.0 ? (un >= 0.0 && vn >= 0.0 && sum <= den && cc > 0.0)
+                               : (den < 0.0 && un <= 0.0 && vn <= 0.0 && sum >= den && cc < 0.0);
+    if (hit) {
+      const double tt = cc / den;
+      if (tt > 0.0 && (tt < best[q] || (tt == best[q] && id < bid[q]))) { best[q] = tt; bid[q] = id; }
+    }
+  }
+}
+
 // ---- stage 2: the cast ---------------------------------------------------------------------------------------------------------------------
 struct SceneCastArgs {
   const SceneCloud* clouds; const int* tiles /*[tiles][2] = cloud, tile of the window*/;
@@ -251,28 +304,186 @@ __global__ __launch_bounds__(kCastThreads) void scene_cast_kernel(const SceneCas
       n += total;
       __syncthreads();
     }
-    {
-#pragma clang fp contract(off)
-      for (int k = 0; k < n; ++k) {
-        const SceneTri& t = tris[k];   // every lane reads the same address: a broadcast
-        const double N0 = t.N[0], N1 = t.N[1], N2 = t.N[2], A0 = t.A[0], A1 = t.A[1], A2 = t.A[2], B0 = t.Bv[0], B1 = t.Bv[1], B2 = t.Bv[2], cc = t.c;
-        const int id = t.id;
-        const double nz = dz * N2, az = dz * A2, bz = dz * B2;
+    for (int k = 0; k < n; ++k) cast_triangle(tris[k], dx, dy, dz, best, bid);   // every lane reads the same address: a broadcast
+    __syncthreads();   // the stage is rewritten by the next chunk
+  }
 #pragma unroll
-        for (int q = 0; q < kColsPerWave; ++q) {
-          const double den = (dx[q] * N0 + dy[q] * N1) + nz;
-          const double un = (dx[q] * A0 + dy[q] * A1) + az;
-          const double vn = (dx[q] * B0 + dy[q] * B1) + bz;
-          const double sum = un + vn;
-          const bool hit = den > 0.0 ? (un >= 0.0 && vn >= 0.0 && sum <= den && cc > 0.0)
-                                     : (den < 0.0 && un <= 0.0 && vn <= 0.0 && sum >= den && cc < 0.0);
-          if (hit) {
-            const double tt = cc / den;
-            if (tt > 0.0 && (tt < best[q] || (tt == best[q] && id < bid[q]))) { best[q] = tt; bid[q] = id; }
-          }
-        }
-      }
+  for (int q = 0; q < kColsPerWave; ++q) {
+    const int j = j0 + wave * kColsPerWave + q;
+    if (j < j0 + ncol) {
+      const long long o = c.tbase + (long long)lane * c.count + j;
+      a.t[o] = best[q];
+      if constexpr (kTrace) a.tri[o] = bid[q];
     }
+  }
+}
+
+// ---- stage 2b: the binned cast -------------------------------------------------------------------------------------------------------------
+// Which columns a triangle can reach, by the window kernel's rule: 0 = none (zero area), 1 = the n columns from column *s on (they may wrap
+// 4499 -> 0), 2 = every column.  The tally and the fill both call it on the same numbers, so they see the same ranges (contraction off and one
+// shared atan2 body: the two inlined copies round alike; the fill is bounded by the tallied lengths regardless).  scene_window_kernel evaluates
+// the same expressions without the pragma, so its interval ends may round differently from these; nothing here depends on their agreeing: the
+// range is conservative on its own, because the 1e-6 column margin is far larger than the error of fp64 atan2 (1e-13 column), and a range that
+// leaves the window is clamped to it.
+// col_coord as a call: one body of fp64 atan2 for the tally and the fill instead of three inlined copies each (which spilled scalar registers)
+__device__ __attribute__((noinline)) double col_coord_call(double x, double y) { return col_coord(x, y); }
+
+__device__ __forceinline__ int tri_reach(const SceneCloud& c, const double* __restrict__ verts, const int* __restrict__ fi, int* s, int* n)
+{
+#pragma clang fp contract(off)
+  const V3 a = pose(c, verts + (c.v0 + fi[0]) * 3), b = pose(c, verts + (c.v0 + fi[1]) * 3), d = pose(c, verts + (c.v0 + fi[2]) * 3);
+  SceneTri t;
+  tri_setup(a, b, d, t);
+  if (t.N[0] == 0.0 && t.N[1] == 0.0 && t.N[2] == 0.0) return 0;
+  const double o1 = a.x * b.y - a.y * b.x, o2 = b.x * d.y - b.y * d.x, o3 = d.x * a.y - d.y * a.x;
+  const double ext = fmax(fmax(fabs(a.x) + fabs(a.y), fabs(b.x) + fabs(b.y)), fabs(d.x) + fabs(d.y));
+  const double m = kSideMargin * ext * ext;
+  bool full;
+  if (fabs(o1 + o2 + o3) > m)
+    full = (o1 >= -m && o2 >= -m && o3 >= -m) || (o1 <= m && o2 <= m && o3 <= m);
+  else
+    full = fmin(fmin(a.x * b.x + a.y * b.y, b.x * d.x + b.y * d.y), d.x * a.x + d.y * a.y) <= m;
+  if (full) return 2;
+  const double c0 = col_coord_call(a.x, a.y);
+  double d1 = col_coord_call(b.x, b.y) - c0, d2 = col_coord_call(d.x, d.y) - c0;
+  d1 -= kCols * rint(d1 / kCols); d2 -= kCols * rint(d2 / kCols);
+  const double lo = c0 + fmin(0.0, fmin(d1, d2)), hi = c0 + fmax(0.0, fmax(d1, d2));
+  if (hi - lo >= kCols / 2 - 1.0) return 2;
+  const long long ca = (long long)floor(lo - kColMargin), cb = (long long)ceil(hi + kColMargin);
+  int first = (int)(ca % kCols); if (first < 0) first += kCols;
+  *s = first; *n = (int)(cb - ca + 1);
+  return 1;
+}
+
+// the tiles of the cloud's window that the n columns from column s on touch: at most two runs [k0, k1] (the second when the columns pass the
+// window's column 4500, which only the all-column window allows); columns outside the window are dropped.  Returns the number of runs.
+__device__ __forceinline__ int reach_tiles(const SceneCloud& c, int s, int n, int (&k0)[2], int (&k1)[2])
+{
+  int js = s - c.first; if (js < 0) js += kCols;   // window column of the first one
+  const int je = js + n - 1;
+  int runs = 0;
+  if (js < c.count) { k0[runs] = js / kTileCols; k1[runs] = min(je, c.count - 1) / kTileCols; ++runs; }
+  if (je >= kCols) { k0[runs] = 0; k1[runs] = min(je - kCols, c.count - 1) / kTileCols; ++runs; }
+  return runs;
+}
+
+// grid (clouds, slices): lengths of the tile lists of the clouds on the binned path
+__global__ __launch_bounds__(256) void scene_bin_tally_kernel(const SceneCloud* __restrict__ clouds, const double* __restrict__ verts,
+                                                              const int* __restrict__ faces, int* __restrict__ cnt)
+{
+  __shared__ int hist[kMaxTiles];
+  __shared__ int s_all;
+  const SceneCloud c = clouds[blockIdx.x];
+  if (c.bt0 < 0 || c.count <= 0) return;   // (uniform: the whole workgroup leaves)
+  const int tid = threadIdx.x, ntile = (c.count + kTileCols - 1) / kTileCols;
+  for (int k = tid; k < ntile; k += 256) hist[k] = 0;
+  if (tid == 0) s_all = 0;
+  __syncthreads();
+  for (int f = blockIdx.y * 256 + tid; f < c.nf; f += gridDim.y * 256) {
+    int s = 0, n = 0, k0[2], k1[2];
+    const int kind = tri_reach(c, verts, faces + (c.f0 + f) * 3, &s, &n);
+    if (kind == 2) atomicAdd(&s_all, 1);
+    else if (kind == 1) {
+      const int runs = reach_tiles(c, s, n, k0, k1);
+      for (int r = 0; r < runs; ++r)
+        for (int k = k0[r]; k <= k1[r]; ++k) atomicAdd(&hist[k], 1);
+    }
+  }
+  __syncthreads();
+  const int all = s_all;
+  for (int k = tid; k < ntile; k += 256) {
+    const int v = hist[k] + all;
+    if (v) atomicAdd(&cnt[c.bt0 + k], v);
+  }
+}
+
+// one workgroup of 1024: exclusive scan of the n list lengths -> off [n + 1] (64-bit); the lengths are cleared (the fill's cursors)
+__global__ __launch_bounds__(1024) void scene_bin_offsets_kernel(int* __restrict__ cnt, long long* __restrict__ off, int n)
+{
+  __shared__ long long part[1024];
+  const int tid = threadIdx.x;
+  const long long per = ((long long)n + 1023) / 1024, lo = min((long long)n, tid * per), hi = min((long long)n, lo + per);
+  long long s = 0;
+  for (long long e = lo; e < hi; ++e) s += cnt[e];
+  part[tid] = s;
+  __syncthreads();
+  if (tid == 0) {
+    long long run = 0;
+    for (int i = 0; i < 1024; ++i) { const long long v = part[i]; part[i] = run; run += v; }
+    off[n] = run;
+  }
+  __syncthreads();
+  long long run = part[tid];
+  for (long long e = lo; e < hi; ++e) { off[e] = run; run += cnt[e]; cnt[e] = 0; }
+}
+
+// grid (clouds, slices) as the tally: the triangle indices into their tiles' lists
+__global__ __launch_bounds__(256) void scene_bin_fill_kernel(const SceneCloud* __restrict__ clouds, const double* __restrict__ verts,
+                                                             const int* __restrict__ faces, int* __restrict__ cur, const long long* __restrict__ off,
+                                                             int* __restrict__ list)
+{
+  const SceneCloud c = clouds[blockIdx.x];
+  if (c.bt0 < 0 || c.count <= 0) return;
+  const int ntile = (c.count + kTileCols - 1) / kTileCols;
+  for (int f = blockIdx.y * 256 + threadIdx.x; f < c.nf; f += gridDim.y * 256) {
+    int s = 0, n = 0, k0[2], k1[2], runs = 0;
+    const int kind = tri_reach(c, verts, faces + (c.f0 + f) * 3, &s, &n);
+    if (kind == 2) { runs = 1; k0[0] = 0; k1[0] = ntile - 1; }
+    else if (kind == 1) runs = reach_tiles(c, s, n, k0, k1);
+    for (int r = 0; r < runs; ++r)
+      for (int k = k0[r]; k <= k1[r]; ++k) {
+        const long long b = off[c.bt0 + k], len = off[c.bt0 + k + 1] - b;
+        const int slot = atomicAdd(&cur[c.bt0 + k], 1);
+        if (slot < len) list[b + slot] = f;   // (never beyond the tallied length)
+      }
+  }
+}
+
+struct SceneBinCastArgs {
+  SceneCastArgs c;               // tiles: the binned clouds' (cloud, tile) items, in the order of the offset table
+  const long long* off;          // [items + 1]
+  const int* list;
+};
+
+template <bool kTrace>
+__global__ __launch_bounds__(kCastThreads) void scene_bincast_kernel(const SceneBinCastArgs b)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  SceneTri* tris = reinterpret_cast<SceneTri*>(lds_raw);
+  const SceneCastArgs& a = b.c;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ci = a.tiles[blockIdx.x * 2], j0 = a.tiles[blockIdx.x * 2 + 1] * kTileCols;
+  const SceneCloud c = a.clouds[ci];
+  const int ncol = min(kTileCols, c.count - j0);
+  const double dz = a.dir[2 * kCols + lane];
+  double dx[kColsPerWave], dy[kColsPerWave], best[kColsPerWave];
+  int bid[kColsPerWave];
+#pragma unroll
+  for (int q = 0; q < kColsPerWave; ++q) {
+    const int j = j0 + wave * kColsPerWave + q;
+    const int col = (c.first + min(j, c.count - 1)) % kCols;   // (a column past the tile's end runs along on the last one; never stored)
+    dx[q] = a.dir[col]; dy[q] = a.dir[kCols + col];
+    best[q] = INFINITY; bid[q] = -1;
+  }
+  const long long e0 = b.off[blockIdx.x], e1 = b.off[(long long)blockIdx.x + 1];
+  const int L = a.lds_triangles;
+  for (long long s0 = e0; s0 < e1; s0 += L) {
+    const int n = (int)min((long long)L, e1 - s0);
+    for (int k = tid; k < n; k += kCastThreads) {
+      const int f = b.list[s0 + k];
+      SceneTri tr;
+      if ((unsigned)f < (unsigned)c.nf) {
+        const int* fi = a.faces + (c.f0 + f) * 3;
+        const V3 p = pose(c, a.verts + (c.v0 + fi[0]) * 3), q = pose(c, a.verts + (c.v0 + fi[1]) * 3), r = pose(c, a.verts + (c.v0 + fi[2]) * 3);
+        tri_setup(p, q, r, tr);
+      } else {   // (not a face of this mesh: a triangle that no ray hits)
+        tr.N[0] = tr.N[1] = tr.N[2] = tr.A[0] = tr.A[1] = tr.A[2] = tr.Bv[0] = tr.Bv[1] = tr.Bv[2] = tr.c = 0.0;
+      }
+      tr.id = f; tr.pad = 0;
+      tris[k] = tr;
+    }
+    __syncthreads();
+    for (int k = 0; k < n; ++k) cast_triangle(tris[k], dx, dy, dz, best, bid);   // every lane reads the same address: a broadcast
     __syncthreads();   // the stage is rewritten by the next chunk
   }
 #pragma unroll
@@ -405,6 +616,9 @@ struct SceneWS {
   SceneCloud* d_clouds = nullptr; int* d_win = nullptr; int* d_rowcount = nullptr; long long* d_rowoff = nullptr; size_t cap_clouds = 0;
   int* d_tiles = nullptr; size_t cap_tiles = 0;
   double* d_t = nullptr; int* d_tri = nullptr; size_t cap_t = 0, cap_tri = 0;
+  // binned cast: list lengths / fill cursors and offsets per (cloud, tile) of the binned clouds, the triangle lists
+  int* d_bincnt = nullptr; long long* d_binoff = nullptr; size_t cap_bincnt = 0, cap_binoff = 0;
+  int* d_binlist = nullptr; size_t cap_binlist = 0;
   // the last result (alignnet_scene_generate)
   int B = -1;
   std::vector<long long> offsets;           // [B + 1][2]
@@ -449,7 +663,10 @@ int ensure_ws(alignnet_handle* h)
   return 0;
 }
 
-struct SceneTrace { int lds_triangles; double* t; int32_t* triangle; int32_t* window; int32_t* lds_triangles_used; };
+struct SceneTrace {
+  int lds_triangles; double* t; int32_t* triangle; int32_t* window; int32_t* lds_triangles_used;
+  bool binned; int32_t* tile_counts /*[kMaxTiles]*/; int64_t* entries;   // the binned read-back
+};
 
 // B scenes x 2 clouds (or, traced: ONE cloud, pose [4]); results stay on the device
 int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const double* scale, const double* poses, const int64_t* scene_ids, int nclouds,
@@ -506,7 +723,11 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
     HIP_TRY(h, hipMemcpyAsync(win.data(), w->d_win, win.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
   }
-  // deal the work: (cloud, tile of the window); the t tables and the point blobs are sized by the windows
+  // deal the work: (cloud, tile of the window); the t tables and the point blobs are sized by the windows.  Which cast a cloud takes ("scene_cast";
+  // the read-backs choose their own) depends on its mesh alone, never on what else is in the call; the binned clouds' tiles come behind the scan's.
+  const int mode = trace ? (trace->binned ? 1 : 0) : h->scene_cast;
+  std::vector<int> btiles;
+  int nbinned = 0, max_nf = 0;
   size_t nt = 0, npts[2] = {0, 0};
   for (int i = 0; i < nclouds; ++i) {
     SceneCloud& c = cl[i];
@@ -515,33 +736,74 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
     c.tbase = (long long)nt;
     nt += (size_t)c.count * kRows;
     npts[c.which] += (size_t)c.count * kRows;
-    for (int k = 0; k * kTileCols < c.count; ++k) { tiles.push_back(i); tiles.push_back(k); }
+    const bool binned = mode == 1 || (mode == 2 && c.nf > kSceneBinAuto);
+    c.bt0 = binned ? (int)(btiles.size() / 2) : -1;
+    if (binned) { ++nbinned; max_nf = std::max(max_nf, c.nf); }
+    std::vector<int>& dst = binned ? btiles : tiles;
+    for (int k = 0; k * kTileCols < c.count; ++k) { dst.push_back(i); dst.push_back(k); }
   }
+  const size_t nscan = tiles.size() / 2, nbt = btiles.size() / 2;
+  if (nscan + nbt > 0x7fffffffu) return fail(h, name + ": too many tiles in one call");
+  tiles.insert(tiles.end(), btiles.begin(), btiles.end());
   if (grow(h, &w->d_t, &w->cap_t, nt)) return 1;
   if (trace && grow(h, &w->d_tri, &w->cap_tri, nt)) return 1;
   if (grow(h, &w->d_tiles, &w->cap_tiles, tiles.size())) return 1;
   for (int k = 0; k < 2; ++k) if (grow(h, &w->d_pts[k], &w->cap_pts[k], npts[k] * 3)) return 1;
   int L = kLdsTriangles;
   if (trace && trace->lds_triangles > 0) L = trace->lds_triangles;
+  long long bin_entries = 0;   // entries of all tile lists of this call
   if (nclouds > 0) {
     HIP_TRY(h, hipMemcpyAsync(w->d_clouds, cl.data(), cl.size() * sizeof(SceneCloud), hipMemcpyHostToDevice, h->stream));
+    if (!tiles.empty()) HIP_TRY(h, hipMemcpyAsync(w->d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (nbt > 0) {
+      // bin the triangles of the binned clouds to their tiles: lengths, offsets (the total comes back: the lists are sized by it), lists
+      if (grow(h, &w->d_bincnt, &w->cap_bincnt, nbt) || grow(h, &w->d_binoff, &w->cap_binoff, nbt + 1)) return 1;
+      const dim3 bgrid((unsigned)nclouds, (unsigned)std::min(kBinSlices, std::max(1, (max_nf + 255) / 256)));
+      HIP_TRY(h, hipMemsetAsync(w->d_bincnt, 0, nbt * sizeof(int), h->stream));
+      {
+        alignnet::ProfScope prof_scope(h, alignnet::PK_SCENE_BIN);
+        hipLaunchKernelGGL(scene_bin_tally_kernel, bgrid, dim3(256), 0, h->stream, w->d_clouds, w->d_verts, w->d_faces, w->d_bincnt);
+        hipLaunchKernelGGL(scene_bin_offsets_kernel, dim3(1), dim3(1024), 0, h->stream, w->d_bincnt, w->d_binoff, (int)nbt);
+      }
+      HIP_TRY(h, hipGetLastError());
+      HIP_TRY(h, hipMemcpyAsync(&bin_entries, w->d_binoff + nbt, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+      if (bin_entries < 0) return fail(h, name + ": tile lists out of range (internal)");
+      if (grow(h, &w->d_binlist, &w->cap_binlist, (size_t)bin_entries)) return 1;
+      if (bin_entries > 0) {
+        alignnet::ProfScope prof_scope(h, alignnet::PK_SCENE_BIN);
+        hipLaunchKernelGGL(scene_bin_fill_kernel, bgrid, dim3(256), 0, h->stream, w->d_clouds, w->d_verts, w->d_faces, w->d_bincnt, w->d_binoff, w->d_binlist);
+      }
+      HIP_TRY(h, hipGetLastError());
+    }
     if (!tiles.empty()) {
-      HIP_TRY(h, hipMemcpyAsync(w->d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
       SceneCastArgs a;
       a.clouds = w->d_clouds; a.tiles = w->d_tiles; a.verts = w->d_verts; a.faces = w->d_faces; a.dir = w->d_dir; a.t = w->d_t; a.tri = w->d_tri;
       a.lds_triangles = L;
       const size_t lds = (size_t)L * sizeof(SceneTri);
       alignnet::ProfScope prof_scope(h, alignnet::PK_SCENE_CAST);
-      if (trace)
-        hipLaunchKernelGGL(scene_cast_kernel<true>, dim3((unsigned)(tiles.size() / 2)), dim3(kCastThreads), lds, h->stream, a);
-      else
-        hipLaunchKernelGGL(scene_cast_kernel<false>, dim3((unsigned)(tiles.size() / 2)), dim3(kCastThreads), lds, h->stream, a);
+      if (nscan > 0) {
+        if (trace)
+          hipLaunchKernelGGL(scene_cast_kernel<true>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, a);
+        else
+          hipLaunchKernelGGL(scene_cast_kernel<false>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, a);
+      }
+      if (nbt > 0) {
+        SceneBinCastArgs b;
+        b.c = a; b.c.tiles = w->d_tiles + nscan * 2; b.off = w->d_binoff; b.list = w->d_binlist;
+        if (trace)
+          hipLaunchKernelGGL(scene_bincast_kernel<true>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, b);
+        else
+          hipLaunchKernelGGL(scene_bincast_kernel<false>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, b);
+      }
     }
     HIP_TRY(h, hipGetLastError());
   }
   if (trace) {
     // the record: t and triangle per ray of the window, laid out by ray index on the host
     std::vector<double> t(nt); std::vector<int> tri(nt);
+    std::vector<long long> boff(nbt + 1, 0);
+    if (trace->binned && nbt) HIP_TRY(h, hipMemcpyAsync(boff.data(), w->d_binoff, boff.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
     if (nt) {
       HIP_TRY(h, hipMemcpyAsync(t.data(), w->d_t, nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(h, hipMemcpyAsync(tri.data(), w->d_tri, nt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -556,6 +818,10 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
       }
     trace->window[0] = c.first; trace->window[1] = c.count;
     *trace->lds_triangles_used = L;
+    if (trace->binned) {
+      for (int k = 0; k < kMaxTiles; ++k) trace->tile_counts[k] = (size_t)k < nbt ? (int32_t)(boff[k + 1] - boff[k]) : 0;
+      *trace->entries = bin_entries;
+    }
     return 0;
   }
   if (nclouds > 0) {
@@ -570,6 +836,7 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
     HIP_TRY(h, hipMemcpyAsync(w->offsets.data(), w->d_offsets, w->offsets.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   w->B = B;
+  h->scene_binned_clouds = nbinned; h->scene_bin_entries = bin_entries;
   return 0;
 }
 
@@ -581,7 +848,7 @@ extern "C" void alignnet_scene_free(alignnet_handle* h)
   SceneWS* w = sws(h);
   if (h->stream) hipStreamSynchronize(h->stream);
   void* const ptrs[] = {w->d_verts, w->d_faces, w->d_dir, w->d_clouds, w->d_win, w->d_rowcount, w->d_rowoff, w->d_tiles, w->d_t, w->d_tri, w->d_offsets,
-                        w->d_pts[0], w->d_pts[1]};
+                        w->d_pts[0], w->d_pts[1], w->d_bincnt, w->d_binoff, w->d_binlist};
   for (void* p : ptrs) if (p) hipFree(p);
   delete w;
   h->scene_ws = nullptr;
@@ -702,6 +969,19 @@ extern "C" int alignnet_debug_scene_cast(alignnet_handle* h, int32_t mesh, doubl
   if (!pose || !t || !triangle || !window || !lds_triangles_used) return fail(h, name + ": null argument");
   if (lds_triangles < 0 || lds_triangles > kLdsTriangles)
     return fail(h, name + ": lds_triangles must be in [0, " + std::to_string(kLdsTriangles) + "] (0 = as shipped)");
-  const SceneTrace tr = {lds_triangles, t, triangle, window, lds_triangles_used};
+  const SceneTrace tr = {lds_triangles, t, triangle, window, lds_triangles_used, false, nullptr, nullptr};
+  return run_scene(h, name.c_str(), &mesh, &scale, pose, nullptr, 1, 0, 0.0, 0.0, &tr);
+}
+
+extern "C" int alignnet_debug_scene_cast_binned(alignnet_handle* h, int32_t mesh, double scale, const double* pose, int32_t lds_triangles, double* t,
+                                                int32_t* triangle, int32_t* window, int32_t* lds_triangles_used, int32_t* tile_counts, int64_t* entries)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_debug_scene_cast_binned");
+  if (!h->scene_ws || sws(h)->M < 0) return fail(h, name + ": no meshes uploaded");
+  if (!pose || !t || !triangle || !window || !lds_triangles_used || !tile_counts || !entries) return fail(h, name + ": null argument");
+  if (lds_triangles < 0 || lds_triangles > kLdsTriangles)
+    return fail(h, name + ": lds_triangles must be in [0, " + std::to_string(kLdsTriangles) + "] (0 = as shipped)");
+  const SceneTrace tr = {lds_triangles, t, triangle, window, lds_triangles_used, true, tile_counts, entries};
   return run_scene(h, name.c_str(), &mesh, &scale, pose, nullptr, 1, 0, 0.0, 0.0, &tr);
 }

@@ -454,7 +454,11 @@ int alignnet_debug_fgr_stages(alignnet_handle* h, const float* points1, int64_t 
  *   with a record behind it, no noise: t [288000] per ray index (inf = miss), triangle [288000] the face hit (-1),
  *   window [2] = first column and number of columns of the azimuth window that was cast (it may wrap 4499 -> 0),
  *   lds_triangles: triangles per LDS chunk, 0 = as shipped (512), 1 .. 512 forces several chunks on small meshes;
- *   lds_triangles_used [1].  It discards the result of an earlier alignnet_scene_generate. */
+ *   lds_triangles_used [1].  It discards the result of an earlier alignnet_scene_generate.  It always runs the scan.
+ * alignnet_debug_scene_cast_binned (test hook, outside the stable surface): the same read-back through the BINNED cast
+ *   (alignnet_set_option "scene_cast"), whatever the option says; the same arguments and lds_triangles range, and
+ *   tile_counts [563] the length of the triangle list of every 8-column tile of the window (0 beyond the window's
+ *   tiles), entries [1] their sum. */
 int alignnet_scene_set_sensor(alignnet_handle* h, const double* dir_x, const double* dir_y, const double* dir_z);
 int alignnet_scene_upload_meshes(alignnet_handle* h, const double* vertices, const int32_t* faces, const int64_t* offsets,
                                  const double* centroids, int32_t M);
@@ -465,6 +469,9 @@ int alignnet_scene_read(alignnet_handle* h, float* points1, float* points2);
 int alignnet_scene_install_dataset(alignnet_handle* h, const float* labels);
 int alignnet_debug_scene_cast(alignnet_handle* h, int32_t mesh, double scale, const double* pose, int32_t lds_triangles,
                               double* t, int32_t* triangle, int32_t* window, int32_t* lds_triangles_used);
+int alignnet_debug_scene_cast_binned(alignnet_handle* h, int32_t mesh, double scale, const double* pose,
+                                     int32_t lds_triangles, double* t, int32_t* triangle, int32_t* window,
+                                     int32_t* lds_triangles_used, int32_t* tile_counts, int64_t* entries);
 
 /* ---- run-time options with no counterpart in the reference's config surface --------
  * "train_matmul_bf16" (0/1, default 0): training only -- the two MFMA convs of every backbone (the hidden 1x1 conv
@@ -518,6 +525,16 @@ int alignnet_debug_scene_cast(alignnet_handle* h, int32_t mesh, double scale, co
  *   over another assignment of points to threads, so transforms agree with the scan's to rounding (1e-9), not bit for bit.  2 = automatic:
  *   a pair takes the grid when its target has more than 4266 points (where the scan leaves its LDS stage), else the scan; each pair's
  *   result is bit-identical to what 0 (scan pairs) or 1 (grid pairs) gives it.  Other values are an error.
+ * "scene_cast" (0/1/2, default 0): how alignnet_scene_generate casts a cloud.  0 = the scan: every 8-column tile of the cloud's azimuth
+ *   window poses and side-tests all triangles of the mesh (built for meshes of some hundred triangles; every result bit for bit what it
+ *   was before the key existed).  1 = binned, for every cloud: the triangles are first binned to the tiles their azimuth interval
+ *   reaches (conservative: the rule that chooses the window), and a tile poses and intersects only its own list (4 bytes per list entry,
+ *   freed with the handle) -- exact: offsets and points are bit for bit the scan's.  2 = automatic: a cloud is binned when its mesh has
+ *   more than 512 triangles (where the scan stops fitting the mesh in one LDS chunk), else scanned.  A cloud's result does not depend on
+ *   the option or on what else is in the call.  Other values are an error.  Measured on an MI355X the scan is the faster one at every mesh
+ *   size tried, 516 to 100,002 triangles (profiles/scene_cast_rate.json): 1 and 2 are exact alternatives, not accelerations, today.
+ *   "scene_binned_clouds" (read-only): how many clouds of the last alignnet_scene_generate took the binned cast;
+ *   "scene_bin_entries" (read-only): the entries of their tile lists together.
  *   "icp_grid_ws_bytes" (read-only): the workspace the last call with grid pairs carved (per chunk of pairs, at most 1 GiB unless one pair
  *   needs more; freed with the handle).
  * "ab_*" (0/1, default 0): A/B dispatch overrides -- each selects an earlier kernel variant of the SAME arithmetic for same-box comparisons

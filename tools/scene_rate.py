@@ -78,7 +78,8 @@ def main():
         if r.returncode != 0 or not line:
             sys.exit("scene_rate: %s failed (exit %d)\n%s" % (config, r.returncode, r.stderr[-3000:]))
         res[config] = json.loads(line[-1][len("SCENE_RATE "):])
-    print(json.dumps(dict(tool="scene_rate", **res)))
+    stamp = os.path.join(ROOT, ".build_commit")   # tools/gpu.sh writes it: the tree the numbers were taken at
+    print(json.dumps(dict(tool="scene_rate", commit=open(stamp).read().strip() if os.path.exists(stamp) else None, **res)))
 
 
 if __name__ == "__main__":
