@@ -118,6 +118,13 @@ SYMBOLS = {
     "alignnet_debug_icp_grid": (C.c_int, [H, FP, C.c_int64, FP, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_int32, C.POINTER(C.c_int32),
                                           C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "alignnet_icp_plane_register": (C.c_int, [H, FP, FP, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "alignnet_icp_plane_register_dataset": (C.c_int, [H, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "alignnet_debug_icp_plane": (C.c_int, [H, FP, C.c_int64, FP, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "alignnet_global_register": (C.c_int, [H, FP, FP, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "alignnet_global_register_dataset": (C.c_int, [H, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,

@@ -430,6 +430,53 @@ class Engine:
         return dict(index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1, candidates=cand[:n1].copy(), cell_edge=float(edge[0]),
                     buckets_occupied=int(occ[0]), largest_bucket=int(big[0]), fitness=float(fit[0]), rmse=float(rmse[0]))
 
+    # ---- point-to-plane ICP (csrc/alignnet_icp.hip: icp_plane_*; semantics: tests/icp_plane_ref.py) ----
+    def icp_plane_refine(self, sources, targets, inits, radius=0.1, normal_radius=0.3, its=30, constrained=True):
+        """Point-to-plane ICP: icp_refine's loop (nearest target within `radius`, same stop rule, same return dict) with the estimate that
+        minimises the distances to the targets' tangent planes.  The target normals are computed once per call from ALL target points within
+        `normal_radius` (fewer than 3: (0, 0, 1); orientation n_z >= 0).  constrained=True: rotation about z + translation; False: six unknowns.
+        A singular system (a single plane) leaves the transform as it is.  Why 0.3 and not the search radius: the 64-ring sensor's ring spacing
+        is 0.0075 x range, so at 20 m a radius of 0.1 sees only one ring and every neighbourhood is a line."""
+        B = len(sources)
+        off = np.zeros((B + 1, 2), np.int64)
+        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
+        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
+        p1, p2 = cat(sources), cat(targets)
+        init, out, fit, rmse, it, dp = self._icp_bufs(inits, B)
+        offp, itp = off.ctypes.data_as(C.POINTER(C.c_int64)), it.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.alignnet_icp_plane_register(self._h, _fp(p1), _fp(p2), offp, B, dp(init), float(radius), float(normal_radius), int(its),
+                                                          0 if constrained else ICP_FULL_ROTATION, dp(out), dp(fit), dp(rmse), itp))
+        return dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+
+    def icp_plane_refine_rows(self, rows, inits, radius=0.1, normal_radius=0.3, its=30, constrained=True):
+        """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows."""
+        r, rp = self._rows(rows)
+        init, out, fit, rmse, it, dp = self._icp_bufs(inits, r.size)
+        itp = it.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.alignnet_icp_plane_register_dataset(self._h, rp, r.size, dp(init), float(radius), float(normal_radius), int(its),
+                                                                  0 if constrained else ICP_FULL_ROTATION, dp(out), dp(fit), dp(rmse), itp))
+        return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+
+    def debug_icp_plane(self, source, target, T, radius=0.1, normal_radius=0.3, constrained=True):
+        """Test hook: one pair through the point-to-plane kernels' own source -- the target's normals and neighbour counts, ONE evaluation at the
+        4x4 `T` and the estimate that follows.  Returns dict(normals [n2, 3], neighbours [n2], index [n1] (-1 without a candidate), dist2 [n1]
+        (inf without), inlier [n1] bool, residual [n1] (0 for outliers), sums [29] (count, sum dist2, upper triangle of J^T J, J^T r; 16 used
+        by the z-constrained estimate), update [4, 4], fitness, rmse)."""
+        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+        Tm = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+        n, m = max(len(p1), 1), max(len(p2), 1)
+        nrm, nbr = np.zeros((m, 3), np.float64), np.zeros(m, np.int32)
+        idx, d2, inl, res = np.full(n, -1, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        sums, upd, fit, rmse = np.zeros(29, np.float64), np.zeros(16, np.float64), np.zeros(1, np.float64), np.zeros(1, np.float64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.alignnet_debug_icp_plane(self._h, _fp(p1), len(p1), _fp(p2), len(p2), dp(Tm), float(radius), float(normal_radius),
+                                                       0 if constrained else ICP_FULL_ROTATION, dp(nrm), ip(nbr), ip(idx), dp(d2), ip(inl), dp(res),
+                                                       dp(sums), dp(upd), dp(fit), dp(rmse)))
+        n1, n2 = len(p1), len(p2)
+        return dict(normals=nrm[:n2].copy(), neighbours=nbr[:n2].copy(), index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1,
+                    residual=res[:n1].copy(), sums=sums, update=upd.reshape(4, 4), fitness=float(fit[0]), rmse=float(rmse[0]))
+
     # ---- global registration: RANSAC on FPFH feature matches (csrc/alignnet_globalreg.hip) ----
     @staticmethod
     def _global_bufs(B, streams, default_streams):
@@ -831,7 +878,7 @@ class Engine:
 
     PROFILED_KERNELS = ("backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1",
                         "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact",
-                        "icp_grid_build", "icp_grid", "scene_bin")
+                        "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane")
 
     def profile_kernels(self):
         """{kernel: (ms, launches)} accumulated since the last profile_read(reset=True); call BEFORE that reset."""

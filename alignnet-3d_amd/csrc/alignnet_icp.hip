@@ -661,6 +661,526 @@ int icp_rows(alignnet_handle* h, const char* fn, const int32_t* rows, int32_t B,
   return rc;
 }
 
+// ---- point-to-plane ICP (alignnet_icp_plane_register*): target normals once per call, a 6x6 / 4x4 normal-equation estimate in the loop -------------
+// Semantics: tests/icp_plane_ref.py (the reference names the method and leaves it `assert False`, icp.py:81-82).  Per pair, once per call: grid A
+// (cells of `radius`) for the correspondence search and grid B (cells of `normal_radius`) for the normals, both by icp_grid_build_kernel; grid B's
+// records are then put in original-index order inside every bucket (icp_plane_sort_kernel: the build's scatter orders them by its atomics, and the
+// normals' fp64 moments would differ in their last bits from run to run); icp_plane_normals_kernel, one lane per target point over several workgroups
+// per pair, takes count, first and second moments of the differences q_j - q_i over all targets with fp64 squared distance <= fl(normal_radius^2) (the
+// point itself included, no cap on their number) and writes the unit eigenvector of the smallest eigenvalue of S2 / K - m m^T with n_z >= 0, or
+// (0, 0, 1) for K < 3.  A bucket reached through two of the 27 cells is walked once: sums, unlike the minimum of the search, would count it twice.
+// The cell claim of the grid search (file header) holds for a target as the query and normal_radius as the radius: same arithmetic, same bound.
+// Loop (icp_plane_kernel, one workgroup per pair, always the grid search): evaluate, stop test, estimate, T <- U T exactly as icp_kernel.  Estimate over
+// the inlier correspondences (p, q, n): r = (p - q) . n, a = p - c (c = the pivot, the pair's first target), J = [a x n, n] (full) or [(a x n)_z, n]
+// (z-constrained); J^T J x = -J^T r by Cholesky without pivoting on the diagonally scaled matrix; U = Tr(c) [Rz(g) Ry(b) Rx(a) | t] Tr(-c).  A diagonal
+// entry <= 0, a pivot <= kIcpPlanePivot or no correspondence determines no update: U = I.
+// The transformed point and the residual are evaluated WITHOUT fused multiply-adds, in the order the restatement states, so that both are the
+// restatement's to the last bit at any distance from the origin (a cloud 5 km out: one fused product moves p by 1e-12 m and a residual of a millimetre
+// by 1e-9 of itself); the squared distance is the grid search's expression.
+constexpr int kIcpPlaneSums = 16, kIcpPlaneSumsFull = 29;   // count, sum d^2, upper triangle of J^T J (10 / 21), J^T r (4 / 6)
+constexpr double kIcpPlanePivot = 1e-10;                    // on the scaled matrix (unit diagonal): a design constant
+constexpr int kIcpPlaneLanes = 256, kIcpPlaneMaxBlocks = 1024;   // normals / sort: threads per workgroup, workgroups per pair at most
+
+__host__ __device__ inline size_t icp_r256(size_t v) { return (v + 255) & ~(size_t)255; }
+// a pair's workspace: grid A | grid B | grid B's records, index-ordered per bucket [n2] float4 | normals [n2][3] doubles | neighbour counts [n2] ints
+__host__ __device__ inline size_t icp_plane_sorted_off(long long n2) { return 2 * icp_grid_pair_bytes(n2); }
+__host__ __device__ inline size_t icp_plane_normals_off(long long n2) { return icp_plane_sorted_off(n2) + icp_r256((size_t)n2 * 16); }
+__host__ __device__ inline size_t icp_plane_counts_off(long long n2) { return icp_plane_normals_off(n2) + icp_r256((size_t)n2 * 24); }
+__host__ __device__ inline size_t icp_plane_pair_bytes(long long n2) { return icp_plane_counts_off(n2) + icp_r256((size_t)n2 * 4); }
+
+struct IcpPlaneArgs : IcpGridArgs {   // ws_off: pair b's part (grid A at its head)
+  int parts;                    // sort / normals: workgroups per pair (blockIdx.x = pair * parts + part)
+  const long long* ws_off_b;    // [B] byte offset of pair b's grid B (= ws_off[b] + icp_grid_pair_bytes(n2))
+  double normal_radius;
+  // read only by the traced instantiations (alignnet_debug_icp_plane: one pair): residual per source point of the first evaluation, its sums, the update
+  double* tr_resid; double* tr_sums; double* tr_update;
+};
+
+__device__ __forceinline__ double icp_dot3_unfused(double a0, double b0, double a1, double b1, double a2, double b2)
+{
+#pragma clang fp contract(off)
+  return (a0 * b0 + a1 * b1) + a2 * b2;
+}
+__device__ __forceinline__ double icp_affine_unfused(double t0, double t1, double t2, double t3, double x, double y, double z)
+{
+#pragma clang fp contract(off)
+  return ((t0 * x + t1 * y) + t2 * z) + t3;
+}
+
+// eigenvector of the smallest eigenvalue of a symmetric 3x3 matrix: cyclic Jacobi in fp64 (the routine of the global registration's normals,
+// alignnet_globalreg.hip gr_smallest_eigenvector, restated here: the two translation units share no device code)
+__device__ __forceinline__ void icp_smallest_eigenvector(double a00, double a01, double a02, double a11, double a12, double a22, double* n)
+{
+  double A[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}};
+  double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+#pragma unroll 1
+  for (int sweep = 0; sweep < 32; ++sweep) {
+    bool rotated = false;
+#pragma unroll
+    for (int pr = 0; pr < 3; ++pr) {
+      const int p = pr == 2 ? 1 : 0, q = pr == 0 ? 1 : 2;
+      const double apq = A[p][q];
+      if (!(fabs(apq) > 1e-18 * (fabs(A[p][p]) + fabs(A[q][q])))) continue;
+      const double th = (A[q][q] - A[p][p]) / (2.0 * apq);
+      const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(1.0 + th * th));
+      const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+      const int r = 3 - p - q;
+      const double arp = A[r][p], arq = A[r][q];
+      A[p][p] -= t * apq; A[q][q] += t * apq; A[p][q] = 0.0; A[q][p] = 0.0;
+      A[r][p] = cs * arp - sn * arq; A[p][r] = A[r][p];
+      A[r][q] = sn * arp + cs * arq; A[q][r] = A[r][q];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double vp = V[i][p], vq = V[i][q];
+        V[i][p] = cs * vp - sn * vq; V[i][q] = sn * vp + cs * vq;
+      }
+      rotated = true;
+    }
+    if (!rotated) break;
+  }
+  const double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
+  if (e0 <= e1 && e0 <= e2) { n[0] = V[0][0]; n[1] = V[1][0]; n[2] = V[2][0]; }
+  else if (e1 <= e2) { n[0] = V[0][1]; n[1] = V[1][1]; n[2] = V[2][1]; }
+  else { n[0] = V[0][2]; n[1] = V[1][2]; n[2] = V[2][2]; }
+}
+
+// grid B's records in original-index order inside every bucket: one lane per record finds its bucket again (the build's hash of the build's edge),
+// counts the bucket's records of lower index and writes itself there in the second array.  blockIdx.x = pair * parts + part (the pair in x: no
+// 65,535 limit on the pairs of a chunk); the parts of a pair stride over its records
+__global__ __launch_bounds__(kIcpPlaneLanes) void icp_plane_sort_kernel(const IcpPlaneArgs a)
+{
+  const int b = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
+  const long long row = a.rows ? a.rows[b] : b;
+  const long long n2 = a.off[(row + 1) * 2 + 1] - a.off[row * 2 + 1];
+  const char* const w = a.ws + a.ws_off_b[b];
+  const int H = icp_grid_buckets(n2);
+  const int* const st = reinterpret_cast<const int*>(w + 256);
+  const float4* const rec = reinterpret_cast<const float4*>(w + 256 + icp_grid_table_bytes(n2));
+  float4* const srt = reinterpret_cast<float4*>(a.ws + a.ws_off[b] + icp_plane_sorted_off(n2));
+  const double e = reinterpret_cast<const IcpGridInfo*>(w)->edge;
+  const unsigned mask = (unsigned)H - 1u;
+  for (long long j = (long long)part * kIcpPlaneLanes + threadIdx.x; j < n2; j += (long long)a.parts * kIcpPlaneLanes) {
+    const float4 q = rec[j];
+    const int mine = __float_as_int(q.w);
+    const unsigned hb = icp_grid_hash(icp_grid_cell((double)q.x, e), icp_grid_cell((double)q.y, e), icp_grid_cell((double)q.z, e)) & mask;
+    const int lo = st[hb], hi = st[hb + 1];
+    int rank = 0;
+    for (int k = lo; k < hi; ++k) rank += __float_as_int(rec[k].w) < mine ? 1 : 0;
+    if (j >= lo && j < hi) srt[lo + rank] = q;   // (always: the record sits in the bucket its coordinates hash to)
+  }
+}
+
+__global__ __launch_bounds__(kIcpPlaneLanes) void icp_plane_normals_kernel(const IcpPlaneArgs a)
+{
+  const int b = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
+  const long long row = a.rows ? a.rows[b] : b;
+  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
+  const float* dst = a.pts[1] + t_lo * 3;
+  const char* const w = a.ws + a.ws_off_b[b];
+  char* const base = a.ws + a.ws_off[b];
+  const int H = icp_grid_buckets(n2);
+  const int* const st = reinterpret_cast<const int*>(w + 256);
+  const float4* const srt = reinterpret_cast<const float4*>(base + icp_plane_sorted_off(n2));
+  double* const nrm = reinterpret_cast<double*>(base + icp_plane_normals_off(n2));
+  int* const cnt = reinterpret_cast<int*>(base + icp_plane_counts_off(n2));
+  const double e = reinterpret_cast<const IcpGridInfo*>(w)->edge;
+  const unsigned mask = (unsigned)H - 1u;
+  const double r2 = a.normal_radius * a.normal_radius;
+  for (long long i = (long long)part * kIcpPlaneLanes + threadIdx.x; i < n2; i += (long long)a.parts * kIcpPlaneLanes) {
+    const double qx = (double)dst[i * 3], qy = (double)dst[i * 3 + 1], qz = (double)dst[i * 3 + 2];
+    const int gx = icp_grid_cell(qx, e), gy = icp_grid_cell(qy, e), gz = icp_grid_cell(qz, e);
+    int K = 0;
+    double s1x = 0.0, s1y = 0.0, s1z = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+#pragma unroll 1
+    for (int c = 0; c < 27; ++c) {
+      const unsigned hb = icp_grid_hash(gx + c % 3 - 1, gy + (c / 3) % 3 - 1, gz + c / 9 - 1) & mask;
+      bool seen = false;   // an earlier cell in the same bucket: walked already
+#pragma unroll 1
+      for (int c0 = 0; c0 < c; ++c0) seen = seen || (icp_grid_hash(gx + c0 % 3 - 1, gy + (c0 / 3) % 3 - 1, gz + c0 / 9 - 1) & mask) == hb;
+      if (seen) continue;
+      const int lo = st[hb], hi = st[hb + 1];
+#pragma unroll 1
+      for (int j = lo; j < hi; ++j) {
+        const float4 q = srt[j];
+        const double dx = (double)q.x - qx, dy = (double)q.y - qy, dz = (double)q.z - qz;
+        const double d = dx * dx + dy * dy + dz * dz;
+        if (d <= r2) {
+          ++K;
+          s1x += dx; s1y += dy; s1z += dz;
+          sxx += dx * dx; sxy += dx * dy; sxz += dx * dz; syy += dy * dy; syz += dy * dz; szz += dz * dz;
+        }
+      }
+    }
+    double n[3] = {0.0, 0.0, 1.0};
+    if (K >= 3) {
+      const double k = (double)K, mx = s1x / k, my = s1y / k, mz = s1z / k;
+      icp_smallest_eigenvector(sxx / k - mx * mx, sxy / k - mx * my, sxz / k - mx * mz, syy / k - my * my, syz / k - my * mz, szz / k - mz * mz, n);
+      const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+      if (!(nn > 0.0)) { n[0] = 0.0; n[1] = 0.0; n[2] = 1.0; }
+      else { n[0] /= nn; n[1] /= nn; n[2] /= nn; }
+      if (n[2] < 0.0) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; }
+    }
+    nrm[i * 3] = n[0]; nrm[i * 3 + 1] = n[1]; nrm[i * 3 + 2] = n[2];
+    cnt[i] = K;
+  }
+}
+
+// the update U (rows 0..2 of the 4x4) from the reduced sums; false (U = I): nothing determined
+template <bool kFull>
+__device__ __forceinline__ bool icp_plane_update(const double* tot, double cx, double cy, double cz, double* U)
+{
+  constexpr int N = kFull ? 6 : 4, TRI = N * (N + 1) / 2;
+#pragma unroll
+  for (int q = 0; q < 12; ++q) U[q] = q % 5 == 0 ? 1.0 : 0.0;
+  if (!(tot[0] > 0.0)) return false;
+  double L[N][N], s[N], y[N];
+  {
+    int q = 2;
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+      for (int j = i; j < N; ++j) L[j][i] = tot[q++];   // the lower triangle holds A
+  }
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < N; ++i) { ok = ok && L[i][i] > 0.0; s[i] = 1.0 / sqrt(L[i][i]); }
+  if (!ok) return false;
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j <= i; ++j) L[i][j] = L[i][j] * s[i] * s[j];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    double d = L[k][k];
+#pragma unroll
+    for (int j = 0; j < k; ++j) d -= L[k][j] * L[k][j];
+    if (!(d > kIcpPlanePivot)) return false;
+    d = sqrt(d);
+    L[k][k] = d;
+#pragma unroll
+    for (int i = k + 1; i < N; ++i) {
+      double v = L[i][k];
+#pragma unroll
+      for (int j = 0; j < k; ++j) v -= L[i][j] * L[k][j];
+      L[i][k] = v / d;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double v = -(s[i] * tot[2 + TRI + i]);
+#pragma unroll
+    for (int j = 0; j < i; ++j) v -= L[i][j] * y[j];
+    y[i] = v / L[i][i];
+  }
+#pragma unroll
+  for (int i = N - 1; i >= 0; --i) {
+    double v = y[i];
+#pragma unroll
+    for (int j = i + 1; j < N; ++j) v -= L[j][i] * y[j];
+    y[i] = v / L[i][i];
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) y[i] *= s[i];
+  double R[9], t[3];
+  if constexpr (kFull) {
+    const double ca = cos(y[0]), sa = sin(y[0]), cb = cos(y[1]), sb = sin(y[1]), cg = cos(y[2]), sg = sin(y[2]);   // Rz(g) Ry(b) Rx(a)
+    R[0] = cg * cb; R[1] = cg * sb * sa - sg * ca; R[2] = cg * sb * ca + sg * sa;
+    R[3] = sg * cb; R[4] = sg * sb * sa + cg * ca; R[5] = sg * sb * ca - cg * sa;
+    R[6] = -sb;     R[7] = cb * sa;                R[8] = cb * ca;
+    t[0] = y[3]; t[1] = y[4]; t[2] = y[5];
+  } else {
+    const double cg = cos(y[0]), sg = sin(y[0]);
+    R[0] = cg; R[1] = -sg; R[2] = 0.0; R[3] = sg; R[4] = cg; R[5] = 0.0; R[6] = 0.0; R[7] = 0.0; R[8] = 1.0;
+    t[0] = y[1]; t[1] = y[2]; t[2] = y[3];
+  }
+  const double c[3] = {cx, cy, cz};
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    U[r * 4] = R[r * 3]; U[r * 4 + 1] = R[r * 3 + 1]; U[r * 4 + 2] = R[r * 3 + 2];
+    U[r * 4 + 3] = (c[r] + t[r]) - (R[r * 3] * c[0] + R[r * 3 + 1] * c[1] + R[r * 3 + 2] * c[2]);   // Tr(c) [R | t] Tr(-c)
+  }
+  return true;
+}
+
+// kTrace (alignnet_debug_icp_plane, one pair): the same evaluation with one record per source point behind it, then the sums and the update of the
+// estimate that follows, and no further iteration
+template <bool kFull, bool kTrace = false>
+__global__ __launch_bounds__(kIcpThreads) void icp_plane_kernel(const IcpPlaneArgs a)
+{
+  constexpr int kSums = kFull ? kIcpPlaneSumsFull : kIcpPlaneSums;
+  extern __shared__ __attribute__((aligned(16))) int gstart[];   // [H + 1] bucket starts of grid A
+  __shared__ double T[12];
+  __shared__ double red[(kIcpThreads / 64) * kSums], tot[kSums];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const long long row = a.rows ? a.rows[b] : b;
+  const long long s_lo = a.off[row * 2], n1 = a.off[(row + 1) * 2] - s_lo;
+  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
+  const float* src = a.pts[0] + s_lo * 3;
+  const float* dst = a.pts[1] + t_lo * 3;
+  if (tid < 12) T[tid] = a.init[(size_t)b * 16 + tid];
+  const char* const w = a.ws + a.ws_off[b];
+  const int H = icp_grid_buckets(n2);
+  {
+    const int* const st = reinterpret_cast<const int*>(w + 256);
+    for (int j = tid; j <= H; j += kIcpThreads) gstart[j] = st[j];
+  }
+  const float4* const grec = reinterpret_cast<const float4*>(w + 256 + icp_grid_table_bytes(n2));
+  const double* const nrm = reinterpret_cast<const double*>(w + icp_plane_normals_off(n2));
+  const unsigned gmask = (unsigned)H - 1u;
+  const double gedge = reinterpret_cast<const IcpGridInfo*>(w)->edge;
+  __syncthreads();
+  const double r2 = a.radius * a.radius;
+  const double cx = n2 > 0 ? (double)dst[0] : 0.0, cy = n2 > 0 ? (double)dst[1] : 0.0, cz = n2 > 0 ? (double)dst[2] : 0.0;   // the pivot of icp_kernel
+  double fit_prev = 0.0, rmse_prev = 0.0, fit = 0.0, rmse = 0.0;
+  int k = 0;
+  if (n1 > 0 && n2 > 0)
+    for (k = 0;; ++k) {
+      double v[kSums];
+#pragma unroll
+      for (int q = 0; q < kSums; ++q) v[q] = 0.0;
+      for (long long i = tid; i < n1; i += kIcpThreads) {
+        const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
+        const double px = icp_affine_unfused(T[0], T[1], T[2], T[3], sx, sy, sz);
+        const double py = icp_affine_unfused(T[4], T[5], T[6], T[7], sx, sy, sz);
+        const double pz = icp_affine_unfused(T[8], T[9], T[10], T[11], sx, sy, sz);
+        double best = 1e300; int bj = 0x7fffffff;
+        float4 brec = {0.f, 0.f, 0.f, 0.f};
+        const int gx = icp_grid_cell(px, gedge), gy = icp_grid_cell(py, gedge), gz = icp_grid_cell(pz, gedge);
+#pragma unroll 1
+        for (int c = 0; c < 27; ++c) {
+          const unsigned hb = icp_grid_hash(gx + c % 3 - 1, gy + (c / 3) % 3 - 1, gz + c / 9 - 1) & gmask;
+          const int lo = gstart[hb], hi = gstart[hb + 1];
+#pragma unroll 1
+          for (int j = lo; j < hi; ++j) {
+            const float4 q = grec[j];
+            const int oj = __float_as_int(q.w);
+            const double ddx = px - (double)q.x, ddy = py - (double)q.y, ddz = pz - (double)q.z;
+            const double d = ddx * ddx + ddy * ddy + ddz * ddz;
+            if (d < best || (d == best && oj < bj)) { best = d; bj = oj; brec = q; }   // equal distances: the lower original index
+          }
+        }
+        const bool inlier = best <= r2;
+        double res = 0.0;
+        if (inlier) {
+          const double nx = nrm[(size_t)bj * 3], ny = nrm[(size_t)bj * 3 + 1], nz = nrm[(size_t)bj * 3 + 2];
+          res = icp_dot3_unfused(px - (double)brec.x, nx, py - (double)brec.y, ny, pz - (double)brec.z, nz);
+          const double ax = px - cx, ay = py - cy, az = pz - cz;
+          v[0] += 1.0; v[1] += best;
+          if constexpr (kFull) {
+            const double J[6] = {ay * nz - az * ny, az * nx - ax * nz, ax * ny - ay * nx, nx, ny, nz};
+            int q = 2;
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+              for (int j = i; j < 6; ++j) v[q++] += J[i] * J[j];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) v[23 + i] += J[i] * res;
+          } else {
+            const double J[4] = {ax * ny - ay * nx, nx, ny, nz};
+            int q = 2;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+              for (int j = i; j < 4; ++j) v[q++] += J[i] * J[j];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[12 + i] += J[i] * res;
+          }
+        }
+        if constexpr (kTrace) {
+          if (k == 0) {
+            const bool found = bj != 0x7fffffff;
+            a.tr_index[i] = found ? bj : -1; a.tr_dist[i] = found ? best : __builtin_huge_val(); a.tr_inlier[i] = inlier; a.tr_resid[i] = res;
+          }
+        }
+      }
+      block_reduce(v, red, tot);
+      const double cnt = tot[0];
+      fit = cnt / (double)n1;
+      rmse = cnt > 0.0 ? sqrt(tot[1] / cnt) : 0.0;
+      if constexpr (kTrace) {
+        if (tid == 0) {
+          double U[12];
+          icp_plane_update<kFull>(tot, cx, cy, cz, U);
+          for (int q = 0; q < kIcpPlaneSumsFull; ++q) a.tr_sums[q] = q < kSums ? tot[q] : 0.0;
+          for (int q = 0; q < 12; ++q) a.tr_update[q] = U[q];
+        }
+        break;
+      }
+      if (k > 0 && fabs(fit - fit_prev) < 1e-6 && fabs(rmse - rmse_prev) < 1e-6) break;
+      if (k == a.its) break;
+      fit_prev = fit; rmse_prev = rmse;
+      if (tid == 0) {
+        double U[12], n[12];
+        if (icp_plane_update<kFull>(tot, cx, cy, cz, U)) {   // T <- U T
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int col = 0; col < 4; ++col) n[r * 4 + col] = U[r * 4] * T[col] + U[r * 4 + 1] * T[4 + col] + U[r * 4 + 2] * T[8 + col];
+            n[r * 4 + 3] += U[r * 4 + 3];
+          }
+          for (int q = 0; q < 12; ++q) T[q] = n[q];
+        }
+      }
+      __syncthreads();
+    }
+  __syncthreads();
+  if (tid < 12) a.out[(size_t)b * 16 + tid] = T[tid];
+  if (tid >= 12 && tid < 16) a.out[(size_t)b * 16 + tid] = tid == 15 ? 1.0 : 0.0;
+  if (tid == 0) {
+    if (a.fitness) a.fitness[b] = fit;
+    if (a.rmse) a.rmse[b] = rmse;
+    if (a.iters) a.iters[b] = k;
+  }
+}
+
+// alignnet_debug_icp_plane: host arrays of the one pair
+struct IcpPlaneTrace { long long n1, n2; double* normals; int* neighbours; int* index; double* dist; int* inlier; double* resid; double* sums; double* update; };
+
+// shared driver of the point-to-plane entry points: tables already on the device; n2 = the target sizes as the host knows them
+int run_icp_plane(alignnet_handle* h, const float* d_p0, const float* d_p1, const long long* d_off, const int* d_rows, const std::vector<long long>& n2,
+                  int B, const double* init, double radius, double normal_radius, int its, bool full, double* out, double* fitness, double* rmse,
+                  int* iters, const IcpPlaneTrace* trace = nullptr)
+{
+  if (!init || !out) return fail(h, "icp_plane: null init / out");
+  if (!(radius > 0.0) || !(normal_radius > 0.0) || its < 0) return fail(h, "icp_plane: radius and normal_radius must be > 0 and its >= 0");
+  // consecutive pairs form chunks of at most kIcpGridWsBudget of workspace (two grids, the ordered records, normals and counts per pair; one pair may
+  // exceed it alone); every chunk reuses the handle's workspace -- the grid search's -- in stream order
+  std::vector<long long> ws_off(2 * (size_t)B, 0);
+  std::vector<int> first;   // the chunks' first pairs
+  const size_t budget = h->icp_plane_ws_budget ? h->icp_plane_ws_budget : kIcpGridWsBudget;
+  constexpr int kChunkPairs = 1 << 20;   // pairs x parts (<= 1024) of a chunk stay a valid gridDim.x
+  size_t need = 0, cur = 0;
+  for (int b = 0; b < B; ++b) {
+    if (n2[b] > 0x7fffffff) return fail(h, "icp_plane: more than 2^31 - 1 target points in a pair");
+    const size_t bytes = icp_plane_pair_bytes(n2[b]);
+    if (b == 0 || cur + bytes > budget || b - first.back() >= kChunkPairs) { first.push_back(b); cur = 0; }
+    ws_off[b] = (long long)cur; ws_off[(size_t)B + b] = (long long)(cur + icp_grid_pair_bytes(n2[b]));
+    cur += bytes;
+    need = std::max(need, cur);
+  }
+  first.push_back(B);
+  h->icp_plane_chunks = (int)first.size() - 1;
+  if (h->icp_grid_ws_bytes < need) {
+    if (h->icp_grid_ws) { HIP_TRY(h, hipStreamSynchronize(h->stream)); hipFree(h->icp_grid_ws); h->icp_grid_ws = nullptr; h->icp_grid_ws_bytes = 0; }
+    HIP_TRY(h, hipMalloc(&h->icp_grid_ws, need));
+    h->icp_grid_ws_bytes = need;
+  }
+  h->icp_grid_ws_used = need;
+  double *d_init = nullptr, *d_out = nullptr, *d_fr = nullptr, *d_trd = nullptr; int *d_it = nullptr, *d_tri = nullptr; long long* d_wsoff = nullptr;
+  HIP_TRY(h, hipMalloc(&d_init, (size_t)B * 16 * sizeof(double)));
+  HIP_TRY(h, hipMalloc(&d_out, (size_t)B * 16 * sizeof(double)));
+  HIP_TRY(h, hipMalloc(&d_fr, (size_t)B * 2 * sizeof(double)));
+  HIP_TRY(h, hipMalloc(&d_it, (size_t)B * sizeof(int)));
+  HIP_TRY(h, hipMalloc(&d_wsoff, (size_t)B * 2 * sizeof(long long)));
+  HIP_TRY(h, hipMemcpyAsync(d_init, init, (size_t)B * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d_wsoff, ws_off.data(), (size_t)B * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  IcpPlaneArgs a;
+  a.pts[0] = d_p0; a.pts[1] = d_p1; a.off = d_off; a.rows = d_rows; a.init = d_init; a.radius = radius; a.its = its; a.lds_points = 0;
+  a.out = d_out; a.fitness = d_fr; a.rmse = d_fr + B; a.iters = d_it;
+  a.tr_index = a.tr_inlier = a.tr_paths = nullptr; a.tr_dist = a.tr_resid = a.tr_sums = a.tr_update = nullptr;
+  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = d_wsoff; a.ws_off_b = d_wsoff + B; a.normal_radius = normal_radius; a.parts = 1;
+  const size_t tn = trace ? (size_t)std::max<long long>(trace->n1, 1) : 0;
+  if (trace) {   // doubles: dist [n1] | residual [n1] | sums [29] | update [12]; ints: index [n1] | inlier [n1]
+    HIP_TRY(h, hipMalloc(&d_trd, (2 * tn + kIcpPlaneSumsFull + 12) * sizeof(double)));
+    HIP_TRY(h, hipMalloc(&d_tri, 2 * tn * sizeof(int)));
+    HIP_TRY(h, hipMemsetAsync(d_trd, 0, (2 * tn + kIcpPlaneSumsFull + 12) * sizeof(double), h->stream));
+    HIP_TRY(h, hipMemsetAsync(d_tri, 0xff, tn * sizeof(int), h->stream));   // (index -1 where the kernel wrote nothing: an empty target)
+    HIP_TRY(h, hipMemsetAsync(d_tri + tn, 0, tn * sizeof(int), h->stream));
+    a.tr_dist = d_trd; a.tr_resid = d_trd + tn; a.tr_sums = d_trd + 2 * tn; a.tr_update = a.tr_sums + kIcpPlaneSumsFull;
+    a.tr_index = d_tri; a.tr_inlier = d_tri + tn;
+  }
+  static alignnet::PerDeviceOnce attr[4];
+  const int which = (full ? 1 : 0) + (trace ? 2 : 0);
+  const void* const kernels[4] = {reinterpret_cast<const void*>(icp_plane_kernel<false>), reinterpret_cast<const void*>(icp_plane_kernel<true>),
+                                  reinterpret_cast<const void*>(icp_plane_kernel<false, true>), reinterpret_cast<const void*>(icp_plane_kernel<true, true>)};
+  if (attr[which].need(h->cfg.device)) {
+    HIP_TRY(h, hipFuncSetAttribute(kernels[which], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(icp_grid_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+    attr[which].mark(h->cfg.device);
+  }
+  for (size_t c = 0; c + 1 < first.size(); ++c) {
+    const int lo = first[c], hi = first[c + 1];
+    const long long big = *std::max_element(n2.begin() + lo, n2.begin() + hi);
+    IcpPlaneArgs r = icp_args_from<IcpPlaneArgs>(a, lo);
+    r.ws_off += lo; r.ws_off_b += lo;
+    const size_t lds = ((size_t)icp_grid_buckets(big) + 1) * 4;
+    IcpGridArgs ga = r, gb = r;
+    gb.radius = normal_radius; gb.ws_off = r.ws_off_b;
+    {
+      alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID_BUILD);
+      hipLaunchKernelGGL(icp_grid_build_kernel, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, ga);
+      hipLaunchKernelGGL(icp_grid_build_kernel, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, gb);
+    }
+    if (big > 0) {
+      // the parts per pair are sized by the chunk's largest target: a small pair beside a large one launches workgroups that find nothing to do
+      alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_PLANE_NORMALS);
+      r.parts = (int)std::min<long long>((big + kIcpPlaneLanes - 1) / kIcpPlaneLanes, kIcpPlaneMaxBlocks);
+      const dim3 blocks((unsigned)r.parts * (unsigned)(hi - lo));
+      hipLaunchKernelGGL(icp_plane_sort_kernel, blocks, dim3(kIcpPlaneLanes), 0, h->stream, r);
+      hipLaunchKernelGGL(icp_plane_normals_kernel, blocks, dim3(kIcpPlaneLanes), 0, h->stream, r);
+    }
+    alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_PLANE);
+    if (which == 3)
+      hipLaunchKernelGGL((icp_plane_kernel<true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+    else if (which == 2)
+      hipLaunchKernelGGL((icp_plane_kernel<false, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+    else if (full)
+      hipLaunchKernelGGL(icp_plane_kernel<true>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+    else
+      hipLaunchKernelGGL(icp_plane_kernel<false>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+    HIP_TRY(h, hipGetLastError());
+  }
+  if (trace) {
+    const size_t m = (size_t)trace->n1, t2 = (size_t)trace->n2;
+    const char* const base = static_cast<const char*>(h->icp_grid_ws);
+    if (t2) {
+      HIP_TRY(h, hipMemcpyAsync(trace->normals, base + icp_plane_normals_off(trace->n2), t2 * 24, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->neighbours, base + icp_plane_counts_off(trace->n2), t2 * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (m) {
+      HIP_TRY(h, hipMemcpyAsync(trace->dist, d_trd, m * 8, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->resid, d_trd + tn, m * 8, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->index, d_tri, m * 4, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->inlier, d_tri + tn, m * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipMemcpyAsync(trace->sums, d_trd + 2 * tn, kIcpPlaneSumsFull * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(trace->update, d_trd + 2 * tn + kIcpPlaneSumsFull, 12 * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_TRY(h, hipMemcpyAsync(out, d_out, (size_t)B * 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (fitness) HIP_TRY(h, hipMemcpyAsync(fitness, d_fr, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (rmse) HIP_TRY(h, hipMemcpyAsync(rmse, d_fr + B, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (iters) HIP_TRY(h, hipMemcpyAsync(iters, d_it, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  hipFree(d_init); hipFree(d_out); hipFree(d_fr); hipFree(d_it); hipFree(d_wsoff); hipFree(d_trd); hipFree(d_tri);
+  return 0;
+}
+
+int icp_plane_host(alignnet_handle* h, const char* fn, const float* points1, const float* points2, const int64_t* offsets, int32_t B, const double* init,
+                   double radius, double normal_radius, int32_t its, bool full, double* out, double* fitness, double* rmse, int32_t* iterations,
+                   const IcpPlaneTrace* trace = nullptr)
+{
+  const std::string name(fn);
+  if (!offsets || B < 1) return fail(h, name + ": null offsets or B < 1");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  std::vector<long long> n2(B);
+  for (int i = 0; i < B; ++i) {
+    if (offsets[(i + 1) * 2] < offsets[i * 2] || offsets[(i + 1) * 2 + 1] < offsets[i * 2 + 1]) return fail(h, name + ": offsets must be non-decreasing");
+    n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1];
+  }
+  const size_t n0 = (size_t)offsets[B * 2], n1 = (size_t)offsets[B * 2 + 1];
+  if ((n0 && !points1) || (n1 && !points2)) return fail(h, name + ": null point blob");
+  float *d0 = nullptr, *d1 = nullptr; long long* doff = nullptr;
+  HIP_TRY(h, hipMalloc(&d0, std::max<size_t>(n0, 1) * 3 * sizeof(float)));
+  HIP_TRY(h, hipMalloc(&d1, std::max<size_t>(n1, 1) * 3 * sizeof(float)));
+  HIP_TRY(h, hipMalloc(&doff, (size_t)(B + 1) * 2 * sizeof(long long)));
+  if (n0) HIP_TRY(h, hipMemcpyAsync(d0, points1, n0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (n1) HIP_TRY(h, hipMemcpyAsync(d1, points2, n1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(doff, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  const int rc = run_icp_plane(h, d0, d1, doff, nullptr, n2, B, init, radius, normal_radius, its, full, out, fitness, rmse, iterations, trace);
+  hipFree(d0); hipFree(d1); hipFree(doff);
+  return rc;
+}
+
 // flags of alignnet_icp_register*: bit 0 = full rotation; no other bit is defined
 int icp_flags(alignnet_handle* h, const char* fn, int32_t flags, bool* full)
 {
@@ -736,6 +1256,60 @@ extern "C" int alignnet_debug_icp_grid(alignnet_handle* h, const float* points1,
   double out[16];
   if (icp_host(h, name.c_str(), points1, points2, off, 1, T, radius, 0, full, out, fitness, rmse, nullptr, &tr)) return 1;
   *cell_edge = info.edge; *buckets_occupied = info.occupied; *largest_bucket = info.largest;
+  return 0;
+}
+
+extern "C" int alignnet_icp_plane_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
+                                           const double* init, double radius, double normal_radius, int32_t its, int32_t flags, double* out,
+                                           double* fitness, double* rmse, int32_t* iterations)
+{
+  if (!h) return 1;
+  bool full = false;
+  if (icp_flags(h, "alignnet_icp_plane_register", flags, &full)) return 1;
+  return icp_plane_host(h, "alignnet_icp_plane_register", points1, points2, offsets, B, init, radius, normal_radius, its, full, out, fitness, rmse, iterations);
+}
+
+extern "C" int alignnet_icp_plane_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
+                                                   double normal_radius, int32_t its, int32_t flags, double* out, double* fitness, double* rmse,
+                                                   int32_t* iterations)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_icp_plane_register_dataset");
+  bool full = false;
+  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
+  alignnet::DatasetTables t;
+  if (!alignnet_dataset_tables(h, &t)) return fail(h, name + ": no dataset uploaded");
+  if (!rows || B < 1) return fail(h, name + ": null rows or B < 1");
+  for (int i = 0; i < B; ++i)
+    if (rows[i] < 0 || rows[i] >= t.n) return fail(h, name + ": row " + std::to_string(rows[i]) + " out of range");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  int* d_rows = nullptr;
+  HIP_TRY(h, hipMalloc(&d_rows, (size_t)B * sizeof(int)));
+  HIP_TRY(h, hipMemcpyAsync(d_rows, rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  std::vector<long long> n2(B);
+  for (int i = 0; i < B; ++i) n2[i] = t.h_off[((size_t)rows[i] + 1) * 2 + 1] - t.h_off[(size_t)rows[i] * 2 + 1];
+  const int rc = run_icp_plane(h, t.pts[0], t.pts[1], t.off, d_rows, n2, B, init, radius, normal_radius, its, full, out, fitness, rmse, iterations);
+  hipFree(d_rows);
+  return rc;
+}
+
+extern "C" int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2, const double* T,
+                                        double radius, double normal_radius, int32_t flags, double* normals, int32_t* neighbours, int32_t* index,
+                                        double* dist2, int32_t* inlier, double* residual, double* sums, double* update, double* fitness, double* rmse)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_debug_icp_plane");
+  bool full = false;
+  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
+  if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(h, name + ": n1 / n2 out of range");
+  if (!normals || !neighbours || !index || !dist2 || !inlier || !residual || !sums || !update) return fail(h, name + ": null output");
+  const int64_t off[4] = {0, 0, n1, n2};
+  double up[12];
+  const IcpPlaneTrace tr = {n1, n2, normals, neighbours, index, dist2, inlier, residual, sums, up};
+  double out[16];
+  if (icp_plane_host(h, name.c_str(), points1, points2, off, 1, T, radius, normal_radius, 0, full, out, fitness, rmse, nullptr, &tr)) return 1;
+  const bool ran = n1 > 0 && n2 > 0;   // (an empty cloud: no evaluation, no update)
+  for (int q = 0; q < 16; ++q) update[q] = q < 12 && ran ? up[q] : (q % 5 == 0 ? 1.0 : 0.0);
   return 0;
 }
 

@@ -114,6 +114,7 @@ class Run:
             self.icp_data.upload(self.engine)
         if flags.refineICP:
             set_icp_search(self.engine)
+            log_icp_estimate()
         self.train_idx = provider.getDataFiles("%s/split/train.txt" % cfg.data.basepath)
         self.val_idx = provider.getDataFiles("%s/split/val.txt" % cfg.data.basepath)
         self.batches_per_epoch = len(self.train_idx) // cfg.training.batch_size
@@ -250,7 +251,7 @@ class Run:
                 pc = src["pred_s2_pc1centers"][s:e] if src else ep["pred_s2_pc1centers"]
                 inits = [evaluation.get_mat_angle(pt[i], pa[i], rotation_center=pc[i]) for i in range(n)]
                 t0 = time.time()
-                T = self.engine.icp_refine_rows(self.icp_data.rows_of(val[s:e]), inits, radius=0.1, its=int(flags.its))["transforms"]
+                T = icp_rows(self.engine, self.icp_data.rows_of(val[s:e]), inits, radius=0.1, its=int(flags.its))["transforms"]
                 cumulated += time.time() - t0
                 ep["pred_translations"] = T[:, :3, 3].astype(np.float32)
                 pred_angles = np.arctan2(T[:, 1, 0], T[:, 0, 0])
@@ -349,6 +350,40 @@ def set_icp_search(engine):
         logger.info("ICP correspondence search: %s" % name)
 
 
+ICP_ESTIMATE = ("point", "plane")
+
+
+def icp_estimate_option(config=None, environ=None):
+    """Optional, not a reference key: "evaluation": {"icp_estimate": "point" | "plane", "icp_normal_radius": 0.3} (or ALIGNNET_ICP_ESTIMATE, which
+    wins when set) selects the estimate of every ICP call -- point-to-point (default: every call as it was) or point-to-plane on target normals
+    taken within icp_normal_radius (Engine.icp_plane_refine_rows).  The reference's own spellings of point-to-plane (variant /
+    refine / --refineICPmethod p2plane) stay rejected: its function is `assert False`.  Returns (name, normal radius)."""
+    config = cfg if config is None else config
+    environ = os.environ if environ is None else environ
+    ev = getattr(config, "evaluation", None)
+    name = str(environ.get("ALIGNNET_ICP_ESTIMATE", "") or getattr(ev, "icp_estimate", "point")).lower()
+    if name not in ICP_ESTIMATE:
+        raise ValueError("evaluation.icp_estimate / ALIGNNET_ICP_ESTIMATE = %r: expected one of %s" % (name, ", ".join(ICP_ESTIMATE)))
+    radius = float(getattr(ev, "icp_normal_radius", 0.3))
+    if not radius > 0.0:
+        raise ValueError("evaluation.icp_normal_radius = %r: expected a radius > 0" % (radius,))
+    return name, radius
+
+
+def icp_rows(engine, rows, inits, radius, its, constrained=True):
+    """The ICP call of the --refineICP refinement and of the ICP mode: point-to-point, or point-to-plane when icp_estimate_option() says so."""
+    name, normal_radius = icp_estimate_option()
+    if name == "plane":
+        return engine.icp_plane_refine_rows(rows, inits, radius=radius, normal_radius=normal_radius, its=its, constrained=constrained)
+    return engine.icp_refine_rows(rows, inits, radius=radius, its=its, constrained=constrained)
+
+
+def log_icp_estimate():
+    name, normal_radius = icp_estimate_option()
+    if name == "plane":
+        logger.info("ICP estimate: point-to-plane (target normals within %g m)" % normal_radius)
+
+
 def icp_plan(icp):
     """What evaluation.special.icp asks for: "centroid" (p2point: icp.py:69-78 from get_centroid_init) or "precomputed" (o3_gicp /
     o3_gicp_fast with refine p2p: point-to-point ICP from the stored global-registration results, icp.py:157-169).  Anything else
@@ -410,6 +445,7 @@ def run_icp_mode(flags):
         import alignnet3d
         engine = alignnet3d.Engine(cfg, device=local_rank if world > 1 else None)
         set_icp_search(engine)
+        log_icp_estimate()
         packed.upload(engine)
         rows = packed.rows_of(val)
         pred_t, pred_a = np.empty((nval, 3), np.float32), np.empty((nval, 1), np.float32)
@@ -422,7 +458,7 @@ def run_icp_mode(flags):
                 inits = [evaluation.get_mat_angle(pre["pred_translations"][i], pre["pred_angles"][i], rotation_center=pre["pred_s1_pc1centers"][i])
                          for i in range(s, e)]
             t0 = time.time()
-            T = engine.icp_refine_rows(rows[s:e], inits, radius=0.10, its=30, constrained=constrained)["transforms"]
+            T = icp_rows(engine, rows[s:e], inits, radius=0.10, its=30, constrained=constrained)["transforms"]
             total_time += time.time() - t0
             pred_t[s:e] = T[:, :3, 3]
             pred_a[s:e, 0] = evaluation.rotvec_z(T[:, :3, :3])

@@ -349,6 +349,32 @@ int alignnet_debug_icp_grid(alignnet_handle* h, const float* points1, int64_t n1
                             int32_t* candidates, double* cell_edge, int32_t* buckets_occupied, int32_t* largest_bucket,
                             double* fitness, double* rmse);
 
+/* ---- point-to-plane ICP (the method icp.py:81-82 names and leaves `assert False`; semantics: tests/icp_plane_ref.py) --
+ * Same clouds, offsets, init / out and result arrays as alignnet_icp_register.  Per pair: normals of the TARGET, once --
+ * all target points within `normal_radius` (the point included, no cap), fewer than 3 give (0, 0, 1), else the unit
+ * eigenvector of the smallest eigenvalue of their covariance with n_z >= 0 -- then the loop of alignnet_icp_register
+ * (nearest target within `radius`, fitness / rmse of point distances, the same stop rule) with the estimate that
+ * minimises sum ((U p - q) . n)^2 linearised about the pair's first target point: six unknowns with
+ * ALIGNNET_ICP_FULL_ROTATION in `flags`, else rotation about z + translation (four).  A singular system (a pivot of the
+ * diagonally scaled normal matrix <= 1e-10: a single plane) or no correspondence leaves the transform as it is.  Any
+ * other bit of `flags` is an error.  Always the grid search: "icp_search" is not read.  The grids, normals and counts
+ * live in the workspace of the grid search (alignnet_icp_free releases it). */
+int alignnet_icp_plane_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets,
+                                int32_t B, const double* init, double radius, double normal_radius, int32_t its,
+                                int32_t flags, double* out, double* fitness, double* rmse, int32_t* iterations);
+int alignnet_icp_plane_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init,
+                                        double radius, double normal_radius, int32_t its, int32_t flags, double* out,
+                                        double* fitness, double* rmse, int32_t* iterations);
+/* Test hook: one pair through the shipped kernels' source (the loop kernel compiled with a record behind it): the normals
+ * [n2][3] and neighbour counts [n2] of the target, ONE evaluation at T [16] -- index [n1] (-1: no candidate), dist2 [n1]
+ * (+inf without), inlier [n1], residual [n1] = (p - q) . n of the inliers (0 otherwise) -- the reduced sums [29] (count,
+ * sum of dist2, the upper triangle of J^T J row by row, J^T r; the 16 of the z-constrained estimate first, zeros behind)
+ * and the update [16] (row-major 4x4) of the estimate that follows.  fitness / rmse [1] may be NULL. */
+int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2,
+                             const double* T, double radius, double normal_radius, int32_t flags, double* normals,
+                             int32_t* neighbours, int32_t* index, double* dist2, int32_t* inlier, double* residual,
+                             double* sums, double* update, double* fitness, double* rmse);
+
 /* ---- global registration: RANSAC on FPFH feature matches (the `o3_gicp` baseline, icp.py:85-143) --------------
  * Per pair: voxel downsample (0.05 m) of both clouds, normals (radius 0.10, 30 nearest), FPFH (radius 0.25, 100
  * nearest), nearest-feature matches, then RANSAC (4 correspondences, edge-length 0.9 and distance checks, threshold
@@ -537,6 +563,10 @@ int alignnet_debug_scene_cast_binned(alignnet_handle* h, int32_t mesh, double sc
  *   "scene_bin_entries" (read-only): the entries of their tile lists together.
  *   "icp_grid_ws_bytes" (read-only): the workspace the last call with grid pairs carved (per chunk of pairs, at most 1 GiB unless one pair
  *   needs more; freed with the handle).
+ * "icp_plane_ws_budget" (bytes, default 0 = 1 GiB): the workspace one chunk of pairs of alignnet_icp_plane_register* may take (two grids,
+ *   ordered records, normals and counts per pair; a pair that needs more forms a chunk alone).  Results do not depend on it: a smaller value
+ *   only cuts a call into more chunks (a test hook for the chunking, and a way to bound the allocation).
+ *   "icp_plane_chunks" (read-only): the chunks the last point-to-plane call ran.
  * "ab_*" (0/1, default 0): A/B dispatch overrides -- each selects an earlier kernel variant of the SAME arithmetic for same-box comparisons
  *   (results agree up to summation order; tests/test_train_gpu.py runs them against the default): "ab_no_ld_const", "ab_infer_tile64",
  *   "ab_phase2_legacy", "ab_b1_legacy", "ab_b1_fp32", "ab_p3_bf16_generic", "ab_p3_nogram", "ab_no_defer", "ab_dg_sparse",
@@ -581,7 +611,9 @@ int alignnet_profile_read(alignnet_handle* h, double* backbone_ms, int64_t* back
  * on the stream it is launched on while profiling is enabled.  name: "backbone" (eval-mode fused backbone), "knn",
  * "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge",
  * "allreduce" (what the compute stream waits for), "optimizer", and the stages of alignnet_scene_generate: "scene_window" (azimuth windows),
- * "scene_cast", "scene_compact" (counts, scan, scatter + noise), and of the ICP grid search: "icp_grid_build", "icp_grid" (the iterations). */
+ * "scene_cast", "scene_compact" (counts, scan, scatter + noise), and of the ICP grid search: "icp_grid_build", "icp_grid" (the iterations), and of
+ * point-to-plane ICP: "icp_plane_normals" (the ordering of the second grid's buckets + the normals), "icp_plane" (the iterations; its two grid builds
+ * count under "icp_grid_build"). */
 int alignnet_profile_read_kernel(alignnet_handle* h, const char* name, double* ms, int64_t* launches);
 
 #ifdef __cplusplus
