@@ -266,43 +266,7 @@ __global__ __launch_bounds__(kThreads) void gr_neighbours_kernel(const GrArgs a,
   }
 }
 
-// ---- 3. normals ----------------------------------------------------------------------------------------------------------------------
-// eigenvector of the smallest eigenvalue of the symmetric 3x3 matrix (a00, a01, a02, a11, a12, a22): cyclic Jacobi, fp64
-__device__ __forceinline__ void gr_smallest_eigenvector(double a00, double a01, double a02, double a11, double a12, double a22, double* n)
-{
-  double A[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}};
-  double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-#pragma unroll 1
-  for (int sweep = 0; sweep < 32; ++sweep) {
-    bool rotated = false;
-#pragma unroll
-    for (int pr = 0; pr < 3; ++pr) {
-      const int p = pr == 2 ? 1 : 0, q = pr == 0 ? 1 : 2;
-      const double apq = A[p][q];
-      if (!(fabs(apq) > 1e-18 * (fabs(A[p][p]) + fabs(A[q][q])))) continue;
-      const double th = (A[q][q] - A[p][p]) / (2.0 * apq);
-      const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(1.0 + th * th));
-      const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-      const int r = 3 - p - q;
-      const double arp = A[r][p], arq = A[r][q];
-      A[p][p] -= t * apq; A[q][q] += t * apq; A[p][q] = 0.0; A[q][p] = 0.0;
-      A[r][p] = cs * arp - sn * arq; A[p][r] = A[r][p];
-      A[r][q] = sn * arp + cs * arq; A[q][r] = A[r][q];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const double vp = V[i][p], vq = V[i][q];
-        V[i][p] = cs * vp - sn * vq; V[i][q] = sn * vp + cs * vq;
-      }
-      rotated = true;
-    }
-    if (!rotated) break;
-  }
-  const double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
-  if (e0 <= e1 && e0 <= e2) { n[0] = V[0][0]; n[1] = V[1][0]; n[2] = V[2][0]; }
-  else if (e1 <= e2) { n[0] = V[0][1]; n[1] = V[1][1]; n[2] = V[2][1]; }
-  else { n[0] = V[0][2]; n[1] = V[1][2]; n[2] = V[2][2]; }
-}
-
+// ---- 3. normals (icp_estimate.h: icp_smallest_eigenvector) ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gr_normals_kernel(const GrArgs a)
 {
   const int c = blockIdx.x;
@@ -326,7 +290,7 @@ __global__ __launch_bounds__(256) void gr_normals_kernel(const GrArgs a)
         c00 += x * x; c01 += x * y; c02 += x * z; c11 += y * y; c12 += y * z; c22 += z * z;
       }
       const double inv = (double)K;
-      gr_smallest_eigenvector(c00 / inv, c01 / inv, c02 / inv, c11 / inv, c12 / inv, c22 / inv, n);
+      icp_smallest_eigenvector(c00 / inv, c01 / inv, c02 / inv, c11 / inv, c12 / inv, c22 / inv, n);
       const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
       if (!(nn > 0.0)) { n[0] = 0.0; n[1] = 0.0; n[2] = 1.0; }
       else { n[0] /= nn; n[1] /= nn; n[2] /= nn; }

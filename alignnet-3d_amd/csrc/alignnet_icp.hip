@@ -128,6 +128,50 @@ __device__ __forceinline__ unsigned icp_grid_hash(int cx, int cy, int cz)
   v ^= v >> 15; v *= 0x2c1b3c6du; v ^= v >> 12;
   return v;
 }
+__device__ __forceinline__ unsigned icp_grid_bucket(double x, double y, double z, double e, unsigned mask)   // the bucket of a point
+{
+  return icp_grid_hash(icp_grid_cell(x, e), icp_grid_cell(y, e), icp_grid_cell(z, e)) & mask;
+}
+
+// one grid as the kernels address it, decoded from the pair's workspace `ws` (the layout above).  edge: the build's, read only from a built grid
+struct IcpGridView { char* ws; int* start; float4* rec; unsigned mask; double edge; int buckets; };
+__device__ __forceinline__ IcpGridView icp_grid_view(char* ws, long long n2, bool built = true)
+{
+  IcpGridView g;
+  g.ws = ws;
+  g.buckets = icp_grid_buckets(n2);
+  g.start = reinterpret_cast<int*>(ws + 256);
+  g.rec = reinterpret_cast<float4*>(ws + 256 + icp_grid_table_bytes(n2));
+  g.mask = (unsigned)g.buckets - 1u;
+  g.edge = built ? reinterpret_cast<const IcpGridInfo*>(ws)->edge : 0.0;
+  return g;
+}
+
+// The search of one query (px, py, pz): every record in the buckets of the 27 cells around it, in fp64, into the smallest (distance, original index)
+// pair seen so far (best, bj) and that record's coordinates (brec.x, .y, .z).  kCount (the traced instantiation): cand += the records evaluated.
+// The minimum runs in scalars of this function and not in the caller's float4: that is what the kernels compiled to when the walk stood in them (as
+// a 4-vector behind the reference the winner changed the schedule of the sums that follow the search, and which of their products were fused)
+template <bool kCount>
+__device__ __forceinline__ void icp_grid_nearest(double px, double py, double pz, const IcpGridView& g, double& best, int& bj, float4& brec, int& cand)
+{
+  double m = best; int mj = bj; float mx = brec.x, my = brec.y, mz = brec.z;
+  const int gx = icp_grid_cell(px, g.edge), gy = icp_grid_cell(py, g.edge), gz = icp_grid_cell(pz, g.edge);
+#pragma unroll 1
+  for (int c = 0; c < 27; ++c) {
+    const unsigned hb = icp_grid_hash(gx + c % 3 - 1, gy + (c / 3) % 3 - 1, gz + c / 9 - 1) & g.mask;
+    const int lo = g.start[hb], hi = g.start[hb + 1];
+#pragma unroll 1
+    for (int j = lo; j < hi; ++j) {
+      const float4 q = g.rec[j];
+      const int oj = __float_as_int(q.w);
+      const double ddx = px - (double)q.x, ddy = py - (double)q.y, ddz = pz - (double)q.z;
+      const double d = ddx * ddx + ddy * ddy + ddz * ddz;
+      if (d < m || (d == m && oj < mj)) { m = d; mj = oj; mx = q.x; my = q.y; mz = q.z; }   // equal distances: the lower original index
+    }
+    if constexpr (kCount) cand += hi - lo;   // candidates evaluated
+  }
+  best = m; bj = mj; brec.x = mx; brec.y = my; brec.z = mz;
+}
 
 struct IcpGridArgs : IcpArgs {
   char* ws;                     // the chunk's workspace
@@ -178,19 +222,13 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const std::conditional
   const double* tx = tgt; const double* ty = tgt + a.lds_points; const double* tz = tgt + 2 * a.lds_points;
   const int S4 = icp_slice_len(a.lds_points);
   float* t32 = reinterpret_cast<float*>(tgt + 3 * (size_t)a.lds_points);   // [coordinate][slice][S4]
-  // grid search: the pair's bucket starts (LDS), its records (L2) and its cell edge
-  [[maybe_unused]] int* const gstart = reinterpret_cast<int*>(tgt);
-  [[maybe_unused]] const float4* grec = nullptr;
-  [[maybe_unused]] unsigned gmask = 0;
-  [[maybe_unused]] double gedge = 1.0;
+  // grid search: the pair's grid, its bucket starts copied to LDS (the records stay in L2)
+  [[maybe_unused]] IcpGridView g = {};
   if constexpr (kGrid) {
-    const char* const w = a.ws + a.ws_off[b];
-    const int H = icp_grid_buckets(n2);
-    const int* const st = reinterpret_cast<const int*>(w + 256);
-    for (int j = tid; j <= H; j += kIcpThreads) gstart[j] = st[j];
-    grec = reinterpret_cast<const float4*>(w + 256 + icp_grid_table_bytes(n2));
-    gmask = (unsigned)H - 1u;
-    gedge = reinterpret_cast<const IcpGridInfo*>(w)->edge;
+    g = icp_grid_view(a.ws + a.ws_off[b], n2);
+    int* const lds = reinterpret_cast<int*>(tgt);
+    for (int j = tid; j <= g.buckets; j += kIcpThreads) lds[j] = g.start[j];
+    g.start = lds;   // the search reads the LDS copy
   } else {
   for (int j = tid; j < 3 * kIcpSplit * S4; j += kIcpThreads) t32[j] = kIcpFar;
   __syncthreads();
@@ -229,23 +267,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const std::conditional
         int path = kIcpPathNone;
         [[maybe_unused]] float4 brec = {0.f, 0.f, 0.f, 0.f};   // grid search: the winner's record
         if constexpr (kGrid) {
-          if (active) {
-            const int gx = icp_grid_cell(px, gedge), gy = icp_grid_cell(py, gedge), gz = icp_grid_cell(pz, gedge);
-#pragma unroll 1
-            for (int c = 0; c < 27; ++c) {
-              const unsigned hb = icp_grid_hash(gx + c % 3 - 1, gy + (c / 3) % 3 - 1, gz + c / 9 - 1) & gmask;
-              const int lo = gstart[hb], hi = gstart[hb + 1];
-#pragma unroll 1
-              for (int j = lo; j < hi; ++j) {
-                const float4 q = grec[j];
-                const int oj = __float_as_int(q.w);
-                const double ddx = px - (double)q.x, ddy = py - (double)q.y, ddz = pz - (double)q.z;
-                const double d = ddx * ddx + ddy * ddy + ddz * ddz;
-                if (d < best || (d == best && oj < bj)) { best = d; bj = oj; brec = q; }   // equal distances: the lower original index
-              }
-              if constexpr (kTrace) path += hi - lo;   // candidates evaluated
-            }
-          }
+          if (active) icp_grid_nearest<kTrace>(px, py, pz, g, best, bj, brec, path);
         } else {
         {
           // one fp32 pass over the slice: its smallest distance m1 with the position it sits at, and its second smallest m2 (v_med3 of the
@@ -415,10 +437,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_grid_build_kernel(const IcpGr
   const long long row = a.rows ? a.rows[b] : b;
   const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
   const float* dst = a.pts[1] + t_lo * 3;
-  char* const w = a.ws + a.ws_off[b];
-  const int H = icp_grid_buckets(n2);
-  int* const st = reinterpret_cast<int*>(w + 256);
-  float4* const rec = reinterpret_cast<float4*>(w + 256 + icp_grid_table_bytes(n2));
+  const IcpGridView g = icp_grid_view(a.ws + a.ws_off[b], n2, false);   // (its edge is found here)
+  const int H = g.buckets;
   double m = 0.0;
   for (long long j = tid; j < n2; j += kIcpThreads)
     m = fmax(m, (double)fmaxf(fmaxf(fabsf(dst[j * 3]), fabsf(dst[j * 3 + 1])), fabsf(dst[j * 3 + 2])));
@@ -429,11 +449,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_grid_build_kernel(const IcpGr
   __syncthreads();
   for (int q = 0; q < kIcpThreads / 64; ++q) m = fmax(m, wmax[q]);
   const double e = fmax(a.radius * (1.0 + kGridSpan), (m + a.radius) * kGridSpan);
-  const unsigned mask = (unsigned)H - 1u;
-  for (long long j = tid; j < n2; j += kIcpThreads) {
-    const unsigned hb = icp_grid_hash(icp_grid_cell((double)dst[j * 3], e), icp_grid_cell((double)dst[j * 3 + 1], e), icp_grid_cell((double)dst[j * 3 + 2], e)) & mask;
-    atomicAdd(&cnt[hb], 1);
-  }
+  for (long long j = tid; j < n2; j += kIcpThreads)
+    atomicAdd(&cnt[icp_grid_bucket((double)dst[j * 3], (double)dst[j * 3 + 1], (double)dst[j * 3 + 2], e, g.mask)], 1);
   __syncthreads();
   // exclusive scan: thread t owns buckets [t per, (t + 1) per)
   const int per = (H + kIcpThreads - 1) / kIcpThreads, lo = min(tid * per, H), hi = min(lo + per, H);
@@ -455,17 +472,16 @@ __global__ __launch_bounds__(kIcpThreads) void icp_grid_build_kernel(const IcpGr
     cnt[H] = (int)n2;
     int o2 = 0, b2 = 0;
     for (int q = 0; q < kIcpThreads / 64; ++q) { o2 += wocc[q]; b2 = max(b2, wbig[q]); }
-    IcpGridInfo* info = reinterpret_cast<IcpGridInfo*>(w);
+    IcpGridInfo* info = reinterpret_cast<IcpGridInfo*>(g.ws);
     info->edge = e; info->buckets = H; info->occupied = o2; info->largest = b2; info->pad = 0;
   }
   __syncthreads();
-  for (int j = tid; j <= H; j += kIcpThreads) st[j] = cnt[j];
+  for (int j = tid; j <= H; j += kIcpThreads) g.start[j] = cnt[j];
   __syncthreads();
   for (long long j = tid; j < n2; j += kIcpThreads) {
     const float x = dst[j * 3], y = dst[j * 3 + 1], z = dst[j * 3 + 2];
-    const unsigned hb = icp_grid_hash(icp_grid_cell((double)x, e), icp_grid_cell((double)y, e), icp_grid_cell((double)z, e)) & mask;
-    const int pos = atomicAdd(&cnt[hb], 1);
-    rec[pos] = make_float4(x, y, z, __int_as_float((int)j));
+    const int pos = atomicAdd(&cnt[icp_grid_bucket((double)x, (double)y, (double)z, e, g.mask)], 1);
+    g.rec[pos] = make_float4(x, y, z, __int_as_float((int)j));
   }
 }
 
@@ -486,11 +502,107 @@ Args icp_args_from(const Args& a, int lo)   // the arguments of pairs lo.. as a 
   return r;
 }
 
-// n2: the target sizes of the B pairs as the host knows them; stage_n2: what the scan's LDS stage is sized for
-int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long long* d_off, const int* d_rows, const std::vector<long long>& n2,
-            long long stage_n2, int B, const double* init, double radius, int its, bool full, double* out, double* fitness, double* rmse, int* iters,
-            const IcpTraceOut* trace = nullptr)
+// a device allocation of one call: freed on every way out of it
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) hipFree(p); }
+  hipError_t alloc(size_t n) { return hipMalloc(&p, n * sizeof(T)); }
+};
+
+// the clouds of a call as the kernels address them, with whatever this call uploaded of them (the dataset's tables stay the handle's)
+struct IcpClouds {
+  const float* pts[2] = {nullptr, nullptr}; const long long* off = nullptr; const int* rows = nullptr;
+  std::vector<long long> n2;   // the target sizes of the B pairs as the host knows them
+  DevBuf<float> up_pts[2]; DevBuf<long long> up_off; DevBuf<int> up_rows;
+};
+
+// clouds passed from the host (alignnet_icp_refine / _register / _plane_register and the read-backs); `name` is the entry point's in the messages
+int stage_host(alignnet_handle* h, const std::string& name, const float* points1, const float* points2, const int64_t* offsets, int32_t B, IcpClouds* c)
 {
+  if (!h) return 1;
+  if (!offsets || B < 1) return fail(h, name + ": null offsets or B < 1");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  c->n2.resize(B);
+  for (int i = 0; i < B; ++i) {
+    if (offsets[(i + 1) * 2] < offsets[i * 2] || offsets[(i + 1) * 2 + 1] < offsets[i * 2 + 1]) return fail(h, name + ": offsets must be non-decreasing");
+    c->n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1];
+  }
+  const size_t n0 = (size_t)offsets[B * 2], n1 = (size_t)offsets[B * 2 + 1];
+  if ((n0 && !points1) || (n1 && !points2)) return fail(h, name + ": null point blob");
+  HIP_TRY(h, c->up_pts[0].alloc(std::max<size_t>(n0, 1) * 3));
+  HIP_TRY(h, c->up_pts[1].alloc(std::max<size_t>(n1, 1) * 3));
+  HIP_TRY(h, c->up_off.alloc((size_t)(B + 1) * 2));
+  if (n0) HIP_TRY(h, hipMemcpyAsync(c->up_pts[0].p, points1, n0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (n1) HIP_TRY(h, hipMemcpyAsync(c->up_pts[1].p, points2, n1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(c->up_off.p, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  c->pts[0] = c->up_pts[0].p; c->pts[1] = c->up_pts[1].p; c->off = c->up_off.p;
+  return 0;
+}
+
+// clouds of the uploaded dataset addressed by rows (the _dataset entry points)
+int stage_rows(alignnet_handle* h, const std::string& name, const int32_t* rows, int32_t B, IcpClouds* c)
+{
+  if (!h) return 1;
+  alignnet::DatasetTables t;
+  if (!alignnet_dataset_tables(h, &t)) return fail(h, name + ": no dataset uploaded");
+  if (!rows || B < 1) return fail(h, name + ": null rows or B < 1");
+  for (int i = 0; i < B; ++i)
+    if (rows[i] < 0 || rows[i] >= t.n) return fail(h, name + ": row " + std::to_string(rows[i]) + " out of range");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  HIP_TRY(h, c->up_rows.alloc((size_t)B));
+  HIP_TRY(h, hipMemcpyAsync(c->up_rows.p, rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  // target sizes from the host's copy of the offsets (the grid search carves its workspace per pair)
+  c->n2.resize(B);
+  for (int i = 0; i < B; ++i) c->n2[i] = t.h_off[((size_t)rows[i] + 1) * 2 + 1] - t.h_off[(size_t)rows[i] * 2 + 1];
+  c->pts[0] = t.pts[0]; c->pts[1] = t.pts[1]; c->off = t.off; c->rows = c->up_rows.p;
+  return 0;
+}
+
+// the results of a call on the device: `init` goes up when the arguments are bound, what the caller asked for comes down at the end
+struct IcpResults {
+  DevBuf<double> init, out, fr; DevBuf<int> it;   // fr: fitness [B] | rmse [B]
+  int up(alignnet_handle* h, int B, const double* host_init, IcpArgs* a)
+  {
+    HIP_TRY(h, init.alloc((size_t)B * 16));
+    HIP_TRY(h, out.alloc((size_t)B * 16));
+    HIP_TRY(h, fr.alloc((size_t)B * 2));
+    HIP_TRY(h, it.alloc((size_t)B));
+    HIP_TRY(h, hipMemcpyAsync(init.p, host_init, (size_t)B * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    a->init = init.p; a->out = out.p; a->fitness = fr.p; a->rmse = fr.p + B; a->iters = it.p;
+    return 0;
+  }
+  int down(alignnet_handle* h, int B, double* host_out, double* fitness, double* rmse, int* iters)   // ends with the call's one synchronisation
+  {
+    HIP_TRY(h, hipMemcpyAsync(host_out, out.p, (size_t)B * 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (fitness) HIP_TRY(h, hipMemcpyAsync(fitness, fr.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (rmse) HIP_TRY(h, hipMemcpyAsync(rmse, fr.p + B, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (iters) HIP_TRY(h, hipMemcpyAsync(iters, it.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return 0;
+  }
+};
+
+// the handle's workspace, grown to `need` bytes (the chunks of a call carve it in stream order)
+int reserve_grid_ws(alignnet_handle* h, size_t need)
+{
+  if (h->icp_grid_ws_bytes < need) {
+    if (h->icp_grid_ws) { HIP_TRY(h, hipStreamSynchronize(h->stream)); hipFree(h->icp_grid_ws); h->icp_grid_ws = nullptr; h->icp_grid_ws_bytes = 0; }
+    HIP_TRY(h, hipMalloc(&h->icp_grid_ws, need));
+    h->icp_grid_ws_bytes = need;
+  }
+  h->icp_grid_ws_used = need;
+  return 0;
+}
+
+// stage_n2: what the scan's LDS stage is sized for
+int run_icp(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, const double* init, double radius, int its, bool full, double* out,
+            double* fitness, double* rmse, int* iters, const IcpTraceOut* trace = nullptr)
+{
+  const std::vector<long long>& n2 = c.n2;
   if (!init || !out) return fail(h, "icp: null init / out");
   if (!(radius > 0.0) || its < 0) return fail(h, "icp: radius must be > 0 and its >= 0");
   // which search each pair takes ("icp_search"; the read-backs choose their own), and the grid pairs' workspace: consecutive grid pairs form
@@ -508,38 +620,27 @@ int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long
     ws_off[b] = (long long)cur; cur += bytes;
     need = std::max(need, cur);
   }
-  if (need) {
-    if (h->icp_grid_ws_bytes < need) {
-      if (h->icp_grid_ws) { HIP_TRY(h, hipStreamSynchronize(h->stream)); hipFree(h->icp_grid_ws); h->icp_grid_ws = nullptr; h->icp_grid_ws_bytes = 0; }
-      HIP_TRY(h, hipMalloc(&h->icp_grid_ws, need));
-      h->icp_grid_ws_bytes = need;
-    }
-    h->icp_grid_ws_used = need;
-  }
-  double *d_init = nullptr, *d_out = nullptr, *d_fr = nullptr; int* d_it = nullptr; long long* d_wsoff = nullptr;
-  HIP_TRY(h, hipMalloc(&d_init, (size_t)B * 16 * sizeof(double)));
-  HIP_TRY(h, hipMalloc(&d_out, (size_t)B * 16 * sizeof(double)));
-  HIP_TRY(h, hipMalloc(&d_fr, (size_t)B * 2 * sizeof(double)));
-  HIP_TRY(h, hipMalloc(&d_it, (size_t)B * sizeof(int)));
-  HIP_TRY(h, hipMemcpyAsync(d_init, init, (size_t)B * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (need) {
-    HIP_TRY(h, hipMalloc(&d_wsoff, (size_t)B * sizeof(long long)));
-    HIP_TRY(h, hipMemcpyAsync(d_wsoff, ws_off.data(), (size_t)B * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  }
+  if (need && reserve_grid_ws(h, need)) return 1;
   IcpGridArgs a;
-  a.pts[0] = d_p0; a.pts[1] = d_p1; a.off = d_off; a.rows = d_rows; a.init = d_init; a.radius = radius; a.its = its;
+  IcpResults res;
+  DevBuf<long long> wsoff;
+  if (res.up(h, B, init, &a)) return 1;
+  if (need) {
+    HIP_TRY(h, wsoff.alloc((size_t)B));
+    HIP_TRY(h, hipMemcpyAsync(wsoff.p, ws_off.data(), (size_t)B * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  }
+  a.pts[0] = c.pts[0]; a.pts[1] = c.pts[1]; a.off = c.off; a.rows = c.rows; a.radius = radius; a.its = its;
   a.lds_points = (int)std::max<long long>(1, std::min(kIcpLdsBudget, stage_n2));
-  a.out = d_out; a.fitness = d_fr; a.rmse = d_fr + B; a.iters = d_it;
   a.tr_index = a.tr_inlier = a.tr_paths = nullptr; a.tr_dist = nullptr;
-  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = d_wsoff;
-  char* d_tr = nullptr;   // [n1] doubles | 3 x [n1] ints
+  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = wsoff.p;
+  DevBuf<char> tr;   // [n1] doubles | 3 x [n1] ints
   if (trace) {
     if (trace->lds_points > 0) a.lds_points = trace->lds_points;
     const size_t n = (size_t)std::max<long long>(trace->n1, 1);
-    HIP_TRY(h, hipMalloc(&d_tr, n * 20));
-    HIP_TRY(h, hipMemsetAsync(d_tr, 0xff, n * 20, h->stream));   // (index -1 where the kernel wrote nothing: an empty target)
-    a.tr_dist = reinterpret_cast<double*>(d_tr);
-    a.tr_index = reinterpret_cast<int*>(d_tr + n * 8); a.tr_inlier = a.tr_index + n; a.tr_paths = a.tr_inlier + n;
+    HIP_TRY(h, tr.alloc(n * 20));
+    HIP_TRY(h, hipMemsetAsync(tr.p, 0xff, n * 20, h->stream));   // (index -1 where the kernel wrote nothing: an empty target)
+    a.tr_dist = reinterpret_cast<double*>(tr.p);
+    a.tr_index = reinterpret_cast<int*>(tr.p + n * 8); a.tr_inlier = a.tr_index + n; a.tr_paths = a.tr_inlier + n;
   }
   static alignnet::PerDeviceOnce attr[9];
   const int which = (full ? 1 : 0) + (trace ? 2 : 0);
@@ -593,72 +694,33 @@ int run_icp(alignnet_handle* h, const float* d_p0, const float* d_p1, const long
   if (trace) {
     const size_t n = (size_t)std::max<long long>(trace->n1, 1), m = (size_t)trace->n1;
     if (m) {
-      HIP_TRY(h, hipMemcpyAsync(trace->dist, d_tr, m * 8, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(trace->index, d_tr + n * 8, m * 4, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(trace->inlier, d_tr + n * 12, m * 4, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(trace->paths, d_tr + n * 16, m * 4, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->dist, tr.p, m * 8, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->index, tr.p + n * 8, m * 4, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->inlier, tr.p + n * 12, m * 4, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->paths, tr.p + n * 16, m * 4, hipMemcpyDeviceToHost, h->stream));
     }
     if (trace->grid) HIP_TRY(h, hipMemcpyAsync(trace->info, h->icp_grid_ws, sizeof(IcpGridInfo), hipMemcpyDeviceToHost, h->stream));
     else *trace->lds_points_used = a.lds_points;
   }
-  HIP_TRY(h, hipMemcpyAsync(out, d_out, (size_t)B * 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (fitness) HIP_TRY(h, hipMemcpyAsync(fitness, d_fr, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (rmse) HIP_TRY(h, hipMemcpyAsync(rmse, d_fr + B, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (iters) HIP_TRY(h, hipMemcpyAsync(iters, d_it, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  hipFree(d_init); hipFree(d_out); hipFree(d_fr); hipFree(d_it); hipFree(d_tr); hipFree(d_wsoff);
-  return 0;
+  return res.down(h, B, out, fitness, rmse, iters);
 }
 
-// clouds passed from the host (alignnet_icp_refine / alignnet_icp_register); `fn` names the entry point in the messages
+// stage, then run: the point-to-point entry points on clouds from the host and on rows of the dataset; `fn` names the entry point in the messages
 int icp_host(alignnet_handle* h, const char* fn, const float* points1, const float* points2, const int64_t* offsets, int32_t B, const double* init,
              double radius, int32_t its, bool full, double* out, double* fitness, double* rmse, int32_t* iterations, const IcpTraceOut* trace = nullptr)
 {
-  if (!h) return 1;
-  const std::string name(fn);
-  if (!offsets || B < 1) return fail(h, name + ": null offsets or B < 1");
-  HIP_TRY(h, hipSetDevice(h->cfg.device));
-  std::vector<long long> n2(B);
-  for (int i = 0; i < B; ++i) {
-    if (offsets[(i + 1) * 2] < offsets[i * 2] || offsets[(i + 1) * 2 + 1] < offsets[i * 2 + 1]) return fail(h, name + ": offsets must be non-decreasing");
-    n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1];
-  }
-  const size_t n0 = (size_t)offsets[B * 2], n1 = (size_t)offsets[B * 2 + 1];
-  if ((n0 && !points1) || (n1 && !points2)) return fail(h, name + ": null point blob");
-  float *d0 = nullptr, *d1 = nullptr; long long* doff = nullptr;
-  HIP_TRY(h, hipMalloc(&d0, std::max<size_t>(n0, 1) * 3 * sizeof(float)));
-  HIP_TRY(h, hipMalloc(&d1, std::max<size_t>(n1, 1) * 3 * sizeof(float)));
-  HIP_TRY(h, hipMalloc(&doff, (size_t)(B + 1) * 2 * sizeof(long long)));
-  if (n0) HIP_TRY(h, hipMemcpyAsync(d0, points1, n0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (n1) HIP_TRY(h, hipMemcpyAsync(d1, points2, n1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(doff, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  const int rc = run_icp(h, d0, d1, doff, nullptr, n2, *std::max_element(n2.begin(), n2.end()), B, init, radius, its, full, out, fitness, rmse, iterations, trace);
-  hipFree(d0); hipFree(d1); hipFree(doff);
-  return rc;
+  IcpClouds c;
+  if (stage_host(h, fn, points1, points2, offsets, B, &c)) return 1;
+  return run_icp(h, c, *std::max_element(c.n2.begin(), c.n2.end()), B, init, radius, its, full, out, fitness, rmse, iterations, trace);
 }
 
-// clouds of the uploaded dataset addressed by rows (alignnet_icp_refine_dataset / alignnet_icp_register_dataset)
 int icp_rows(alignnet_handle* h, const char* fn, const int32_t* rows, int32_t B, const double* init, double radius, int32_t its, bool full,
              double* out, double* fitness, double* rmse, int32_t* iterations)
 {
-  if (!h) return 1;
-  const std::string name(fn);
-  alignnet::DatasetTables t;
-  if (!alignnet_dataset_tables(h, &t)) return fail(h, name + ": no dataset uploaded");
-  if (!rows || B < 1) return fail(h, name + ": null rows or B < 1");
-  for (int i = 0; i < B; ++i)
-    if (rows[i] < 0 || rows[i] >= t.n) return fail(h, name + ": row " + std::to_string(rows[i]) + " out of range");
-  HIP_TRY(h, hipSetDevice(h->cfg.device));
-  int* d_rows = nullptr;
-  HIP_TRY(h, hipMalloc(&d_rows, (size_t)B * sizeof(int)));
-  HIP_TRY(h, hipMemcpyAsync(d_rows, rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  // target sizes from the host's copy of the offsets (the grid search carves its workspace per pair).  The scan's LDS stage stays sized for
-  // the budget whatever the rows hold, as it was when the host did not know the sizes: the kernel clamps per pair
-  std::vector<long long> n2(B);
-  for (int i = 0; i < B; ++i) n2[i] = t.h_off[((size_t)rows[i] + 1) * 2 + 1] - t.h_off[(size_t)rows[i] * 2 + 1];
-  const int rc = run_icp(h, t.pts[0], t.pts[1], t.off, d_rows, n2, kIcpLdsBudget, B, init, radius, its, full, out, fitness, rmse, iterations);
-  hipFree(d_rows);
-  return rc;
+  IcpClouds c;
+  if (stage_rows(h, fn, rows, B, &c)) return 1;
+  // the scan's LDS stage stays sized for the budget whatever the rows hold, as it was when the host did not know the sizes: the kernel clamps per pair
+  return run_icp(h, c, kIcpLdsBudget, B, init, radius, its, full, out, fitness, rmse, iterations);
 }
 
 // ---- point-to-plane ICP (alignnet_icp_plane_register*): target normals once per call, a 6x6 / 4x4 normal-equation estimate in the loop -------------
@@ -687,6 +749,10 @@ __host__ __device__ inline size_t icp_plane_sorted_off(long long n2) { return 2 
 __host__ __device__ inline size_t icp_plane_normals_off(long long n2) { return icp_plane_sorted_off(n2) + icp_r256((size_t)n2 * 16); }
 __host__ __device__ inline size_t icp_plane_counts_off(long long n2) { return icp_plane_normals_off(n2) + icp_r256((size_t)n2 * 24); }
 __host__ __device__ inline size_t icp_plane_pair_bytes(long long n2) { return icp_plane_counts_off(n2) + icp_r256((size_t)n2 * 4); }
+// the three arrays behind the grids, from the view of the pair's grid A (the head of its part)
+__device__ __forceinline__ float4* icp_plane_sorted(const IcpGridView& ga, long long n2) { return reinterpret_cast<float4*>(ga.ws + icp_plane_sorted_off(n2)); }
+__device__ __forceinline__ double* icp_plane_normals(const IcpGridView& ga, long long n2) { return reinterpret_cast<double*>(ga.ws + icp_plane_normals_off(n2)); }
+__device__ __forceinline__ int* icp_plane_counts(const IcpGridView& ga, long long n2) { return reinterpret_cast<int*>(ga.ws + icp_plane_counts_off(n2)); }
 
 struct IcpPlaneArgs : IcpGridArgs {   // ws_off: pair b's part (grid A at its head)
   int parts;                    // sort / normals: workgroups per pair (blockIdx.x = pair * parts + part)
@@ -707,43 +773,6 @@ __device__ __forceinline__ double icp_affine_unfused(double t0, double t1, doubl
   return ((t0 * x + t1 * y) + t2 * z) + t3;
 }
 
-// eigenvector of the smallest eigenvalue of a symmetric 3x3 matrix: cyclic Jacobi in fp64 (the routine of the global registration's normals,
-// alignnet_globalreg.hip gr_smallest_eigenvector, restated here: the two translation units share no device code)
-__device__ __forceinline__ void icp_smallest_eigenvector(double a00, double a01, double a02, double a11, double a12, double a22, double* n)
-{
-  double A[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}};
-  double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-#pragma unroll 1
-  for (int sweep = 0; sweep < 32; ++sweep) {
-    bool rotated = false;
-#pragma unroll
-    for (int pr = 0; pr < 3; ++pr) {
-      const int p = pr == 2 ? 1 : 0, q = pr == 0 ? 1 : 2;
-      const double apq = A[p][q];
-      if (!(fabs(apq) > 1e-18 * (fabs(A[p][p]) + fabs(A[q][q])))) continue;
-      const double th = (A[q][q] - A[p][p]) / (2.0 * apq);
-      const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(1.0 + th * th));
-      const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-      const int r = 3 - p - q;
-      const double arp = A[r][p], arq = A[r][q];
-      A[p][p] -= t * apq; A[q][q] += t * apq; A[p][q] = 0.0; A[q][p] = 0.0;
-      A[r][p] = cs * arp - sn * arq; A[p][r] = A[r][p];
-      A[r][q] = sn * arp + cs * arq; A[q][r] = A[r][q];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const double vp = V[i][p], vq = V[i][q];
-        V[i][p] = cs * vp - sn * vq; V[i][q] = sn * vp + cs * vq;
-      }
-      rotated = true;
-    }
-    if (!rotated) break;
-  }
-  const double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
-  if (e0 <= e1 && e0 <= e2) { n[0] = V[0][0]; n[1] = V[1][0]; n[2] = V[2][0]; }
-  else if (e1 <= e2) { n[0] = V[0][1]; n[1] = V[1][1]; n[2] = V[2][1]; }
-  else { n[0] = V[0][2]; n[1] = V[1][2]; n[2] = V[2][2]; }
-}
-
 // grid B's records in original-index order inside every bucket: one lane per record finds its bucket again (the build's hash of the build's edge),
 // counts the bucket's records of lower index and writes itself there in the second array.  blockIdx.x = pair * parts + part (the pair in x: no
 // 65,535 limit on the pairs of a chunk); the parts of a pair stride over its records
@@ -752,20 +781,15 @@ __global__ __launch_bounds__(kIcpPlaneLanes) void icp_plane_sort_kernel(const Ic
   const int b = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
   const long long row = a.rows ? a.rows[b] : b;
   const long long n2 = a.off[(row + 1) * 2 + 1] - a.off[row * 2 + 1];
-  const char* const w = a.ws + a.ws_off_b[b];
-  const int H = icp_grid_buckets(n2);
-  const int* const st = reinterpret_cast<const int*>(w + 256);
-  const float4* const rec = reinterpret_cast<const float4*>(w + 256 + icp_grid_table_bytes(n2));
-  float4* const srt = reinterpret_cast<float4*>(a.ws + a.ws_off[b] + icp_plane_sorted_off(n2));
-  const double e = reinterpret_cast<const IcpGridInfo*>(w)->edge;
-  const unsigned mask = (unsigned)H - 1u;
+  const IcpGridView g = icp_grid_view(a.ws + a.ws_off_b[b], n2);   // grid B
+  float4* const srt = icp_plane_sorted(icp_grid_view(a.ws + a.ws_off[b], n2), n2);   // (behind the pair's grid A)
   for (long long j = (long long)part * kIcpPlaneLanes + threadIdx.x; j < n2; j += (long long)a.parts * kIcpPlaneLanes) {
-    const float4 q = rec[j];
+    const float4 q = g.rec[j];
     const int mine = __float_as_int(q.w);
-    const unsigned hb = icp_grid_hash(icp_grid_cell((double)q.x, e), icp_grid_cell((double)q.y, e), icp_grid_cell((double)q.z, e)) & mask;
-    const int lo = st[hb], hi = st[hb + 1];
+    const unsigned hb = icp_grid_bucket((double)q.x, (double)q.y, (double)q.z, g.edge, g.mask);
+    const int lo = g.start[hb], hi = g.start[hb + 1];
     int rank = 0;
-    for (int k = lo; k < hi; ++k) rank += __float_as_int(rec[k].w) < mine ? 1 : 0;
+    for (int k = lo; k < hi; ++k) rank += __float_as_int(g.rec[k].w) < mine ? 1 : 0;
     if (j >= lo && j < hi) srt[lo + rank] = q;   // (always: the record sits in the bucket its coordinates hash to)
   }
 }
@@ -776,29 +800,24 @@ __global__ __launch_bounds__(kIcpPlaneLanes) void icp_plane_normals_kernel(const
   const long long row = a.rows ? a.rows[b] : b;
   const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
   const float* dst = a.pts[1] + t_lo * 3;
-  const char* const w = a.ws + a.ws_off_b[b];
-  char* const base = a.ws + a.ws_off[b];
-  const int H = icp_grid_buckets(n2);
-  const int* const st = reinterpret_cast<const int*>(w + 256);
-  const float4* const srt = reinterpret_cast<const float4*>(base + icp_plane_sorted_off(n2));
-  double* const nrm = reinterpret_cast<double*>(base + icp_plane_normals_off(n2));
-  int* const cnt = reinterpret_cast<int*>(base + icp_plane_counts_off(n2));
-  const double e = reinterpret_cast<const IcpGridInfo*>(w)->edge;
-  const unsigned mask = (unsigned)H - 1u;
+  const IcpGridView g = icp_grid_view(a.ws + a.ws_off_b[b], n2), ga = icp_grid_view(a.ws + a.ws_off[b], n2);   // grid B; grid A for the arrays
+  const float4* const srt = icp_plane_sorted(ga, n2);
+  double* const nrm = icp_plane_normals(ga, n2);
+  int* const cnt = icp_plane_counts(ga, n2);
   const double r2 = a.normal_radius * a.normal_radius;
   for (long long i = (long long)part * kIcpPlaneLanes + threadIdx.x; i < n2; i += (long long)a.parts * kIcpPlaneLanes) {
     const double qx = (double)dst[i * 3], qy = (double)dst[i * 3 + 1], qz = (double)dst[i * 3 + 2];
-    const int gx = icp_grid_cell(qx, e), gy = icp_grid_cell(qy, e), gz = icp_grid_cell(qz, e);
+    const int gx = icp_grid_cell(qx, g.edge), gy = icp_grid_cell(qy, g.edge), gz = icp_grid_cell(qz, g.edge);
     int K = 0;
     double s1x = 0.0, s1y = 0.0, s1z = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
 #pragma unroll 1
     for (int c = 0; c < 27; ++c) {
-      const unsigned hb = icp_grid_hash(gx + c % 3 - 1, gy + (c / 3) % 3 - 1, gz + c / 9 - 1) & mask;
+      const unsigned hb = icp_grid_hash(gx + c % 3 - 1, gy + (c / 3) % 3 - 1, gz + c / 9 - 1) & g.mask;
       bool seen = false;   // an earlier cell in the same bucket: walked already
 #pragma unroll 1
-      for (int c0 = 0; c0 < c; ++c0) seen = seen || (icp_grid_hash(gx + c0 % 3 - 1, gy + (c0 / 3) % 3 - 1, gz + c0 / 9 - 1) & mask) == hb;
+      for (int c0 = 0; c0 < c; ++c0) seen = seen || (icp_grid_hash(gx + c0 % 3 - 1, gy + (c0 / 3) % 3 - 1, gz + c0 / 9 - 1) & g.mask) == hb;
       if (seen) continue;
-      const int lo = st[hb], hi = st[hb + 1];
+      const int lo = g.start[hb], hi = g.start[hb + 1];
 #pragma unroll 1
       for (int j = lo; j < hi; ++j) {
         const float4 q = srt[j];
@@ -918,16 +937,10 @@ __global__ __launch_bounds__(kIcpThreads) void icp_plane_kernel(const IcpPlaneAr
   const float* src = a.pts[0] + s_lo * 3;
   const float* dst = a.pts[1] + t_lo * 3;
   if (tid < 12) T[tid] = a.init[(size_t)b * 16 + tid];
-  const char* const w = a.ws + a.ws_off[b];
-  const int H = icp_grid_buckets(n2);
-  {
-    const int* const st = reinterpret_cast<const int*>(w + 256);
-    for (int j = tid; j <= H; j += kIcpThreads) gstart[j] = st[j];
-  }
-  const float4* const grec = reinterpret_cast<const float4*>(w + 256 + icp_grid_table_bytes(n2));
-  const double* const nrm = reinterpret_cast<const double*>(w + icp_plane_normals_off(n2));
-  const unsigned gmask = (unsigned)H - 1u;
-  const double gedge = reinterpret_cast<const IcpGridInfo*>(w)->edge;
+  IcpGridView g = icp_grid_view(a.ws + a.ws_off[b], n2);
+  const double* const nrm = icp_plane_normals(g, n2);
+  for (int j = tid; j <= g.buckets; j += kIcpThreads) gstart[j] = g.start[j];
+  g.start = gstart;   // the search reads the LDS copy
   __syncthreads();
   const double r2 = a.radius * a.radius;
   const double cx = n2 > 0 ? (double)dst[0] : 0.0, cy = n2 > 0 ? (double)dst[1] : 0.0, cz = n2 > 0 ? (double)dst[2] : 0.0;   // the pivot of icp_kernel
@@ -945,20 +958,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_plane_kernel(const IcpPlaneAr
         const double pz = icp_affine_unfused(T[8], T[9], T[10], T[11], sx, sy, sz);
         double best = 1e300; int bj = 0x7fffffff;
         float4 brec = {0.f, 0.f, 0.f, 0.f};
-        const int gx = icp_grid_cell(px, gedge), gy = icp_grid_cell(py, gedge), gz = icp_grid_cell(pz, gedge);
-#pragma unroll 1
-        for (int c = 0; c < 27; ++c) {
-          const unsigned hb = icp_grid_hash(gx + c % 3 - 1, gy + (c / 3) % 3 - 1, gz + c / 9 - 1) & gmask;
-          const int lo = gstart[hb], hi = gstart[hb + 1];
-#pragma unroll 1
-          for (int j = lo; j < hi; ++j) {
-            const float4 q = grec[j];
-            const int oj = __float_as_int(q.w);
-            const double ddx = px - (double)q.x, ddy = py - (double)q.y, ddz = pz - (double)q.z;
-            const double d = ddx * ddx + ddy * ddy + ddz * ddz;
-            if (d < best || (d == best && oj < bj)) { best = d; bj = oj; brec = q; }   // equal distances: the lower original index
-          }
-        }
+        int cand = 0;   // (counted by icp_kernel's traced instantiation alone)
+        icp_grid_nearest<false>(px, py, pz, g, best, bj, brec, cand);
         const bool inlier = best <= r2;
         double res = 0.0;
         if (inlier) {
@@ -1036,11 +1037,11 @@ __global__ __launch_bounds__(kIcpThreads) void icp_plane_kernel(const IcpPlaneAr
 // alignnet_debug_icp_plane: host arrays of the one pair
 struct IcpPlaneTrace { long long n1, n2; double* normals; int* neighbours; int* index; double* dist; int* inlier; double* resid; double* sums; double* update; };
 
-// shared driver of the point-to-plane entry points: tables already on the device; n2 = the target sizes as the host knows them
-int run_icp_plane(alignnet_handle* h, const float* d_p0, const float* d_p1, const long long* d_off, const int* d_rows, const std::vector<long long>& n2,
-                  int B, const double* init, double radius, double normal_radius, int its, bool full, double* out, double* fitness, double* rmse,
-                  int* iters, const IcpPlaneTrace* trace = nullptr)
+// shared driver of the point-to-plane entry points: clouds already on the device
+int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* init, double radius, double normal_radius, int its, bool full, double* out,
+                  double* fitness, double* rmse, int* iters, const IcpPlaneTrace* trace = nullptr)
 {
+  const std::vector<long long>& n2 = c.n2;
   if (!init || !out) return fail(h, "icp_plane: null init / out");
   if (!(radius > 0.0) || !(normal_radius > 0.0) || its < 0) return fail(h, "icp_plane: radius and normal_radius must be > 0 and its >= 0");
   // consecutive pairs form chunks of at most kIcpGridWsBudget of workspace (two grids, the ordered records, normals and counts per pair; one pair may
@@ -1060,34 +1061,26 @@ int run_icp_plane(alignnet_handle* h, const float* d_p0, const float* d_p1, cons
   }
   first.push_back(B);
   h->icp_plane_chunks = (int)first.size() - 1;
-  if (h->icp_grid_ws_bytes < need) {
-    if (h->icp_grid_ws) { HIP_TRY(h, hipStreamSynchronize(h->stream)); hipFree(h->icp_grid_ws); h->icp_grid_ws = nullptr; h->icp_grid_ws_bytes = 0; }
-    HIP_TRY(h, hipMalloc(&h->icp_grid_ws, need));
-    h->icp_grid_ws_bytes = need;
-  }
-  h->icp_grid_ws_used = need;
-  double *d_init = nullptr, *d_out = nullptr, *d_fr = nullptr, *d_trd = nullptr; int *d_it = nullptr, *d_tri = nullptr; long long* d_wsoff = nullptr;
-  HIP_TRY(h, hipMalloc(&d_init, (size_t)B * 16 * sizeof(double)));
-  HIP_TRY(h, hipMalloc(&d_out, (size_t)B * 16 * sizeof(double)));
-  HIP_TRY(h, hipMalloc(&d_fr, (size_t)B * 2 * sizeof(double)));
-  HIP_TRY(h, hipMalloc(&d_it, (size_t)B * sizeof(int)));
-  HIP_TRY(h, hipMalloc(&d_wsoff, (size_t)B * 2 * sizeof(long long)));
-  HIP_TRY(h, hipMemcpyAsync(d_init, init, (size_t)B * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(d_wsoff, ws_off.data(), (size_t)B * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  if (reserve_grid_ws(h, need)) return 1;
   IcpPlaneArgs a;
-  a.pts[0] = d_p0; a.pts[1] = d_p1; a.off = d_off; a.rows = d_rows; a.init = d_init; a.radius = radius; a.its = its; a.lds_points = 0;
-  a.out = d_out; a.fitness = d_fr; a.rmse = d_fr + B; a.iters = d_it;
+  IcpResults res;
+  DevBuf<long long> wsoff;
+  DevBuf<double> trd; DevBuf<int> tri;   // the read-back's records
+  if (res.up(h, B, init, &a)) return 1;
+  HIP_TRY(h, wsoff.alloc((size_t)B * 2));
+  HIP_TRY(h, hipMemcpyAsync(wsoff.p, ws_off.data(), (size_t)B * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  a.pts[0] = c.pts[0]; a.pts[1] = c.pts[1]; a.off = c.off; a.rows = c.rows; a.radius = radius; a.its = its; a.lds_points = 0;
   a.tr_index = a.tr_inlier = a.tr_paths = nullptr; a.tr_dist = a.tr_resid = a.tr_sums = a.tr_update = nullptr;
-  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = d_wsoff; a.ws_off_b = d_wsoff + B; a.normal_radius = normal_radius; a.parts = 1;
+  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = wsoff.p; a.ws_off_b = wsoff.p + B; a.normal_radius = normal_radius; a.parts = 1;
   const size_t tn = trace ? (size_t)std::max<long long>(trace->n1, 1) : 0;
   if (trace) {   // doubles: dist [n1] | residual [n1] | sums [29] | update [12]; ints: index [n1] | inlier [n1]
-    HIP_TRY(h, hipMalloc(&d_trd, (2 * tn + kIcpPlaneSumsFull + 12) * sizeof(double)));
-    HIP_TRY(h, hipMalloc(&d_tri, 2 * tn * sizeof(int)));
-    HIP_TRY(h, hipMemsetAsync(d_trd, 0, (2 * tn + kIcpPlaneSumsFull + 12) * sizeof(double), h->stream));
-    HIP_TRY(h, hipMemsetAsync(d_tri, 0xff, tn * sizeof(int), h->stream));   // (index -1 where the kernel wrote nothing: an empty target)
-    HIP_TRY(h, hipMemsetAsync(d_tri + tn, 0, tn * sizeof(int), h->stream));
-    a.tr_dist = d_trd; a.tr_resid = d_trd + tn; a.tr_sums = d_trd + 2 * tn; a.tr_update = a.tr_sums + kIcpPlaneSumsFull;
-    a.tr_index = d_tri; a.tr_inlier = d_tri + tn;
+    HIP_TRY(h, trd.alloc(2 * tn + kIcpPlaneSumsFull + 12));
+    HIP_TRY(h, tri.alloc(2 * tn));
+    HIP_TRY(h, hipMemsetAsync(trd.p, 0, (2 * tn + kIcpPlaneSumsFull + 12) * sizeof(double), h->stream));
+    HIP_TRY(h, hipMemsetAsync(tri.p, 0xff, tn * sizeof(int), h->stream));   // (index -1 where the kernel wrote nothing: an empty target)
+    HIP_TRY(h, hipMemsetAsync(tri.p + tn, 0, tn * sizeof(int), h->stream));
+    a.tr_dist = trd.p; a.tr_resid = trd.p + tn; a.tr_sums = trd.p + 2 * tn; a.tr_update = a.tr_sums + kIcpPlaneSumsFull;
+    a.tr_index = tri.p; a.tr_inlier = tri.p + tn;
   }
   static alignnet::PerDeviceOnce attr[4];
   const int which = (full ? 1 : 0) + (trace ? 2 : 0);
@@ -1138,47 +1131,24 @@ int run_icp_plane(alignnet_handle* h, const float* d_p0, const float* d_p1, cons
       HIP_TRY(h, hipMemcpyAsync(trace->neighbours, base + icp_plane_counts_off(trace->n2), t2 * 4, hipMemcpyDeviceToHost, h->stream));
     }
     if (m) {
-      HIP_TRY(h, hipMemcpyAsync(trace->dist, d_trd, m * 8, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(trace->resid, d_trd + tn, m * 8, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(trace->index, d_tri, m * 4, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(trace->inlier, d_tri + tn, m * 4, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->dist, trd.p, m * 8, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->resid, trd.p + tn, m * 8, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->index, tri.p, m * 4, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->inlier, tri.p + tn, m * 4, hipMemcpyDeviceToHost, h->stream));
     }
-    HIP_TRY(h, hipMemcpyAsync(trace->sums, d_trd + 2 * tn, kIcpPlaneSumsFull * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(trace->update, d_trd + 2 * tn + kIcpPlaneSumsFull, 12 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(trace->sums, trd.p + 2 * tn, kIcpPlaneSumsFull * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(trace->update, trd.p + 2 * tn + kIcpPlaneSumsFull, 12 * 8, hipMemcpyDeviceToHost, h->stream));
   }
-  HIP_TRY(h, hipMemcpyAsync(out, d_out, (size_t)B * 16 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (fitness) HIP_TRY(h, hipMemcpyAsync(fitness, d_fr, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (rmse) HIP_TRY(h, hipMemcpyAsync(rmse, d_fr + B, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (iters) HIP_TRY(h, hipMemcpyAsync(iters, d_it, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  hipFree(d_init); hipFree(d_out); hipFree(d_fr); hipFree(d_it); hipFree(d_wsoff); hipFree(d_trd); hipFree(d_tri);
-  return 0;
+  return res.down(h, B, out, fitness, rmse, iters);
 }
 
 int icp_plane_host(alignnet_handle* h, const char* fn, const float* points1, const float* points2, const int64_t* offsets, int32_t B, const double* init,
                    double radius, double normal_radius, int32_t its, bool full, double* out, double* fitness, double* rmse, int32_t* iterations,
                    const IcpPlaneTrace* trace = nullptr)
 {
-  const std::string name(fn);
-  if (!offsets || B < 1) return fail(h, name + ": null offsets or B < 1");
-  HIP_TRY(h, hipSetDevice(h->cfg.device));
-  std::vector<long long> n2(B);
-  for (int i = 0; i < B; ++i) {
-    if (offsets[(i + 1) * 2] < offsets[i * 2] || offsets[(i + 1) * 2 + 1] < offsets[i * 2 + 1]) return fail(h, name + ": offsets must be non-decreasing");
-    n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1];
-  }
-  const size_t n0 = (size_t)offsets[B * 2], n1 = (size_t)offsets[B * 2 + 1];
-  if ((n0 && !points1) || (n1 && !points2)) return fail(h, name + ": null point blob");
-  float *d0 = nullptr, *d1 = nullptr; long long* doff = nullptr;
-  HIP_TRY(h, hipMalloc(&d0, std::max<size_t>(n0, 1) * 3 * sizeof(float)));
-  HIP_TRY(h, hipMalloc(&d1, std::max<size_t>(n1, 1) * 3 * sizeof(float)));
-  HIP_TRY(h, hipMalloc(&doff, (size_t)(B + 1) * 2 * sizeof(long long)));
-  if (n0) HIP_TRY(h, hipMemcpyAsync(d0, points1, n0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (n1) HIP_TRY(h, hipMemcpyAsync(d1, points2, n1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(doff, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  const int rc = run_icp_plane(h, d0, d1, doff, nullptr, n2, B, init, radius, normal_radius, its, full, out, fitness, rmse, iterations, trace);
-  hipFree(d0); hipFree(d1); hipFree(doff);
-  return rc;
+  IcpClouds c;
+  if (stage_host(h, fn, points1, points2, offsets, B, &c)) return 1;
+  return run_icp_plane(h, c, B, init, radius, normal_radius, its, full, out, fitness, rmse, iterations, trace);
 }
 
 // flags of alignnet_icp_register*: bit 0 = full rotation; no other bit is defined
@@ -1277,20 +1247,9 @@ extern "C" int alignnet_icp_plane_register_dataset(alignnet_handle* h, const int
   const std::string name("alignnet_icp_plane_register_dataset");
   bool full = false;
   if (icp_flags(h, name.c_str(), flags, &full)) return 1;
-  alignnet::DatasetTables t;
-  if (!alignnet_dataset_tables(h, &t)) return fail(h, name + ": no dataset uploaded");
-  if (!rows || B < 1) return fail(h, name + ": null rows or B < 1");
-  for (int i = 0; i < B; ++i)
-    if (rows[i] < 0 || rows[i] >= t.n) return fail(h, name + ": row " + std::to_string(rows[i]) + " out of range");
-  HIP_TRY(h, hipSetDevice(h->cfg.device));
-  int* d_rows = nullptr;
-  HIP_TRY(h, hipMalloc(&d_rows, (size_t)B * sizeof(int)));
-  HIP_TRY(h, hipMemcpyAsync(d_rows, rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  std::vector<long long> n2(B);
-  for (int i = 0; i < B; ++i) n2[i] = t.h_off[((size_t)rows[i] + 1) * 2 + 1] - t.h_off[(size_t)rows[i] * 2 + 1];
-  const int rc = run_icp_plane(h, t.pts[0], t.pts[1], t.off, d_rows, n2, B, init, radius, normal_radius, its, full, out, fitness, rmse, iterations);
-  hipFree(d_rows);
-  return rc;
+  IcpClouds c;
+  if (stage_rows(h, name, rows, B, &c)) return 1;
+  return run_icp_plane(h, c, B, init, radius, normal_radius, its, full, out, fitness, rmse, iterations);
 }
 
 extern "C" int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2, const double* T,

@@ -1,4 +1,5 @@
-// The 3x3 rotation estimate shared by the ICP kernel (alignnet_icp.hip) and the global registration (alignnet_globalreg.hip).
+// The 3x3 fp64 routines shared by ICP (alignnet_icp.hip) and the global registration (alignnet_globalreg.hip): the Umeyama rotation of the
+// point-to-point estimates and the eigenvector behind both units' normals.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -76,4 +77,41 @@ __device__ __forceinline__ void icp_umeyama_rotation(double* work)
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) R[i * 3 + j] = u0[i] * v[j * 3] + u1[i] * v[j * 3 + 1] + d * u2[i] * v[j * 3 + 2];
+}
+
+// eigenvector of the smallest eigenvalue of the symmetric 3x3 matrix (a00, a01, a02, a11, a12, a22): cyclic Jacobi, fp64 (the normals of
+// point-to-plane ICP and of the global registration)
+__device__ __forceinline__ void icp_smallest_eigenvector(double a00, double a01, double a02, double a11, double a12, double a22, double* n)
+{
+  double A[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}};
+  double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+#pragma unroll 1
+  for (int sweep = 0; sweep < 32; ++sweep) {
+    bool rotated = false;
+#pragma unroll
+    for (int pr = 0; pr < 3; ++pr) {
+      const int p = pr == 2 ? 1 : 0, q = pr == 0 ? 1 : 2;
+      const double apq = A[p][q];
+      if (!(fabs(apq) > 1e-18 * (fabs(A[p][p]) + fabs(A[q][q])))) continue;
+      const double th = (A[q][q] - A[p][p]) / (2.0 * apq);
+      const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(1.0 + th * th));
+      const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+      const int r = 3 - p - q;
+      const double arp = A[r][p], arq = A[r][q];
+      A[p][p] -= t * apq; A[q][q] += t * apq; A[p][q] = 0.0; A[q][p] = 0.0;
+      A[r][p] = cs * arp - sn * arq; A[p][r] = A[r][p];
+      A[r][q] = sn * arp + cs * arq; A[q][r] = A[r][q];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double vp = V[i][p], vq = V[i][q];
+        V[i][p] = cs * vp - sn * vq; V[i][q] = sn * vp + cs * vq;
+      }
+      rotated = true;
+    }
+    if (!rotated) break;
+  }
+  const double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
+  if (e0 <= e1 && e0 <= e2) { n[0] = V[0][0]; n[1] = V[1][0]; n[2] = V[2][0]; }
+  else if (e1 <= e2) { n[0] = V[0][1]; n[1] = V[1][1]; n[2] = V[2][1]; }
+  else { n[0] = V[0][2]; n[1] = V[1][2]; n[2] = V[2][2]; }
 }
