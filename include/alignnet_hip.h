@@ -185,8 +185,10 @@ int alignnet_debug_dropout_uniforms(alignnet_handle* h, int32_t B, float* dst, s
 /* Test hook: the k-nearest-neighbour graph (k = 20, self included; the SET tf.nn.top_k selects, ties at the k-th distance to the
  * lower index; utils/tf_util_dgcnn.py:638-676) the last eval-mode forward of a dgcnn engine built: int32 [2B][num_points][20],
  * tower 1's B clouds first.  count = 2 * B * num_points * 20.  Order within a row: nearest first when the query's candidate list
- * has <= 64 survivors (the usual case); queries with more survivors (clustered / duplicated points) emit their k entries in
- * point-index order -- the max over the k neighbours is order-invariant, so compare rows as sets (sorted) where that can occur. */
+ * has <= 64 survivors (the usual case); queries with more survivors (clustered / duplicated points: every batch resampled with
+ * replacement from a cloud of fewer than about N / 64 points) emit two runs, each in point-index order: first the candidates strictly
+ * nearer than the k-th distance, then those AT the k-th distance, lowest indices first, until k are listed -- the max over the k
+ * neighbours is order-invariant, so compare rows as sets (sorted) where that can occur (tests/knn_select_ref.py check_rows). */
 int alignnet_debug_knn_graph(alignnet_handle* h, int32_t* dst, size_t count);
 /* Test hook: what the last TRAINING forward on this handle DECIDED -- the discontinuous choices of the graph.  A parity test pins
  * the oracle to them (after checking that each one is a maximum of the oracle's own values to within rounding), so that the rest of

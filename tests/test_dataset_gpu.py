@@ -105,12 +105,21 @@ def test_sampler_distribution(gpu_required):
 
 def test_rows_entry_points_match_host_path(gpu_required):
     """forward_rows / train_step_rows on the sampled batch == forward / train_step fed the same batch from the host."""
+    _rows_entry_points_match_host_path("pointnet")
+
+
+def test_rows_entry_points_match_host_path_dgcnn(gpu_required):
+    """The same on a dgcnn engine: the rows entry points build the kNN graph on the batch the device sampler wrote (copies of points in every cloud, one cloud empty)."""
+    _rows_entry_points_match_host_path("dgcnn")
+
+
+def _rows_entry_points_match_host_path(backbone):
     N, B = 128, 6
-    cfg = small_cfg(N=N, nb=12, s1=(32, 64, 96), s2=(32, 64, 128), emb=(32, 64, 160), fc=(64, 32))
+    cfg = small_cfg(N=N, nb=12, s1=(32, 64, 96), s2=(32, 64, 128), emb=(32, 64, 160), fc=(64, 32), backbone=backbone)
     cfg["training"]["batch_size"] = B
     spec, P32 = oracle_params(cfg, seed=5)
     pts, off, lab = _toy()
-    rows = [0, 1, 2, 3, 6, 7]
+    rows = [0, 1, 2, 3, 6, 7] if backbone == "pointnet" else [0, 1, 2, 4, 5, 7]   # (dgcnn: with the empty cloud of row 4 and the 7-point cloud of row 5)
     out = []
     for mode in ("rows", "host"):
         eng = alignnet3d.Engine(cfg)

@@ -1016,10 +1016,15 @@ def test_gradients_match_autograd_with_pinned_decisions(gpu_required, case):
       * the rest, held to the oracle's own floor on the batch: every tensor and the whole gradient within max(5e-4, 3 x the worst of
         four self-distances of the pinned fp64 oracle under one-ulp moves of its inputs) (bf16 convs: max(2e-2, 1.5 x))."""
     backbone, w, N, B, bf16, tail = PINNED_CASES[case]
+    pinned_check(case, PINNED_CASES[case], R.synth_pairs(B, N, seed=13, dtype=np.float32))
+
+
+def pinned_check(case, shape, d):
+    """Body of test_gradients_match_autograd_with_pinned_decisions on the batch `d` (tests/test_sampler_clouds_gpu.py runs it on batches as the sampler draws them)."""
+    backbone, w, N, B, bf16, tail = shape
     cfg = small_cfg(N=N, nb=12, fc=(64, 32), backbone=backbone, **w)
     cfg["training"]["batch_size"] = B
     spec, P32 = oracle_params(cfg, seed=13)
-    d = R.synth_pairs(B, N, seed=13, dtype=np.float32)
     rng = np.random.default_rng(13)
     du = {k: rng.uniform(size=(B, 32)).astype(np.float32) for k in ("s1_0", "s2_0", "s1_1", "s2_1", "rem")}
     eng = alignnet3d.Engine(cfg)
