@@ -57,6 +57,16 @@ class State(C.Structure):
     _fields_ = [("step", C.c_int64), ("learning_rate", C.c_float), ("bn_decay", C.c_float)]
 
 
+class RegisterOptions(C.Structure):
+    _fields_ = [("refine", C.c_int32), ("its", C.c_int32), ("flags", C.c_int32), ("radius", C.c_double), ("normal_radius", C.c_double)]
+
+
+class RegisterOutputs(C.Structure):
+    _fields_ = [("transforms", C.POINTER(C.c_double)), ("network_transforms", C.POINTER(C.c_double)), ("angles", C.POINTER(C.c_double)),
+                ("net", C.POINTER(Outputs)), ("fitness", C.POINTER(C.c_double)), ("rmse", C.POINTER(C.c_double)), ("iterations", C.POINTER(C.c_int32)),
+                ("loss", FP)]
+
+
 H = C.c_void_p
 
 # every symbol include/alignnet_hip.h declares: name -> (restype, argtypes)
@@ -125,6 +135,9 @@ SYMBOLS = {
     "alignnet_debug_icp_plane": (C.c_int, [H, FP, C.c_int64, FP, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_double),
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "alignnet_register": (C.c_int, [H, FP, FP, C.POINTER(C.c_int64), C.c_int32, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(RegisterOptions),
+                                    C.POINTER(RegisterOutputs)]),
+    "alignnet_register_dataset": (C.c_int, [H, C.POINTER(C.c_int32), C.c_int32, C.c_uint64, C.POINTER(RegisterOptions), C.POINTER(RegisterOutputs)]),
     "alignnet_global_register": (C.c_int, [H, FP, FP, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "alignnet_global_register_dataset": (C.c_int, [H, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
@@ -161,6 +174,9 @@ SYMBOLS = {
     "alignnet_profile_read": (C.c_int, [H, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32]),
 }
 
+# symbols added after ABI version 1 was fixed: an earlier build named by ALIGNNET_HIP_LIB loads without them
+LATE_SYMBOLS = ("alignnet_register", "alignnet_register_dataset")
+
 _lib = None
 
 
@@ -186,6 +202,9 @@ def load_library():
         except AttributeError:
             # an A/B build of an EARLIER revision (ALIGNNET_HIP_LIB, tools/ab_build.sh) may predate a test hook; the in-tree library must export everything
             if os.environ.get("ALIGNNET_HIP_LIB") and name.startswith("alignnet_debug_"):
+                continue
+            # likewise the one-call registration, added without moving ABI_VERSION: Engine.register* reports its absence (EngineError)
+            if os.environ.get("ALIGNNET_HIP_LIB") and name in LATE_SYMBOLS:
                 continue
             raise
         fn.restype = res

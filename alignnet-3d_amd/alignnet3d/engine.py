@@ -457,6 +457,80 @@ class Engine:
                                                                   0 if constrained else ICP_FULL_ROTATION, dp(out), dp(fit), dp(rmse), itp))
         return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
 
+    # ---- one-call registration: clouds to transforms on the device (csrc/alignnet_register.hip) ----
+    REFINE = {None: 0, "point": 1, "plane": 2}
+
+    def _register_fn(self, name):
+        try:
+            return getattr(self._lib, name)
+        except AttributeError:
+            raise EngineError("%s does not export %s: it was built from a revision before the one-call registration; rebuild it "
+                              "(make -C alignnet-3d_amd/csrc)" % (_capi.library_path(), name)) from None
+
+    def _register_bufs(self, B, refine, radius, normal_radius, its, constrained, want_net, want_loss):
+        if refine not in self.REFINE:
+            raise ValueError("refine = %r: expected None, 'point' or 'plane'" % (refine,))
+        opt = _capi.RegisterOptions(self.REFINE[refine], int(its) if refine else 0, 0 if constrained else ICP_FULL_ROTATION, float(radius),
+                                    float(normal_radius))
+        n = max(B, 0)
+        res = dict(transforms=np.empty((n, 4, 4), np.float64), network_transforms=np.empty((n, 4, 4), np.float64), angles=np.empty((n, 4), np.float64))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        out = _capi.RegisterOutputs()
+        out.transforms, out.network_transforms, out.angles = dp(res["transforms"]), dp(res["network_transforms"]), dp(res["angles"])
+        keep = []
+        if refine:
+            res.update(fitness=np.empty(n, np.float64), rmse=np.empty(n, np.float64), iterations=np.empty(n, np.int32))
+            out.fitness, out.rmse, out.iterations = dp(res["fitness"]), dp(res["rmse"]), res["iterations"].ctypes.data_as(C.POINTER(C.c_int32))
+        if want_net:
+            arrs, o = self._alloc_outputs(n)
+            res.update(arrs)
+            keep.append(o)
+            out.net = C.pointer(o)
+        loss = None
+        if want_loss:
+            loss = np.empty(17, np.float32)
+            out.loss = _fp(loss)
+        return opt, out, res, loss, keep
+
+    @staticmethod
+    def _register_finish(res, loss):
+        res["loss"] = None if loss is None else (float(loss[0]), dict(zip(SUMMARY_NAMES, [float(v) for v in loss[1:]])))
+        return res
+
+    def register(self, sources, targets, seed=0, streams=None, refine=None, radius=0.1, normal_radius=0.3, its=30, constrained=True, want_net=False):
+        """Two raw clouds per pair in, a 4x4 per pair out, in ONE engine call: the sampler's draw, the eval forward, the fp64 yaw decode, the
+        initial transform T_net and -- refine="point" | "plane" -- ICP on the full clouds from it, with no return to the host in between.
+        sources / targets: lists of [n, 3] arrays; streams: [B] ids of the pairs' random streams (None: the pair index) -- pair b is drawn as
+        register_rows would draw it were the pair example streams[b] of the dataset.  Returns dict(transforms [B, 4, 4] (refined, or T_net),
+        network_transforms [B, 4, 4], angles [B, 4] = a1, a2, a_rem, pred_angle, loss=None; fitness, rmse, iterations when refining; the
+        eight network arrays with want_net)."""
+        fn = self._register_fn("alignnet_register")
+        B = len(sources)
+        if len(targets) != B:
+            raise ValueError("register: %d sources and %d targets" % (B, len(targets)))
+        off = np.zeros((B + 1, 2), np.int64)
+        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
+        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
+        p1, p2 = cat(sources), cat(targets)
+        st = None
+        if streams is not None:
+            st = np.ascontiguousarray(streams, np.int64).ravel()
+            if st.size != B:
+                raise ValueError("register: %d streams for %d pairs" % (st.size, B))
+        opt, out, res, loss, keep = self._register_bufs(B, refine, radius, normal_radius, its, constrained, want_net, False)
+        self._check(fn(self._h, _fp(p1), _fp(p2), off.ctypes.data_as(C.POINTER(C.c_int64)), B, int(seed),
+                       st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, C.byref(opt), C.byref(out)))
+        return self._register_finish(res, loss)
+
+    def register_rows(self, rows, seed, refine=None, radius=0.1, normal_radius=0.3, its=30, constrained=True, want_net=False, want_loss=False):
+        """Same on rows of the uploaded dataset (upload_dataset): the batch forward_rows(rows, seed) draws.  want_loss: loss = (loss, summaries)
+        as eval_loss returns them for this batch against the dataset's labels."""
+        fn = self._register_fn("alignnet_register_dataset")
+        r, rp = self._rows(rows)
+        opt, out, res, loss, keep = self._register_bufs(r.size, refine, radius, normal_radius, its, constrained, want_net, want_loss)
+        self._check(fn(self._h, rp, r.size, int(seed), C.byref(opt), C.byref(out)))
+        return self._register_finish(res, loss)
+
     def debug_icp_plane(self, source, target, T, radius=0.1, normal_radius=0.3, constrained=True):
         """Test hook: one pair through the point-to-plane kernels' own source -- the target's normals and neighbour counts, ONE evaluation at the
         4x4 `T` and the estimate that follows.  Returns dict(normals [n2, 3], neighbours [n2], index [n1] (-1 without a candidate), dist2 [n1]

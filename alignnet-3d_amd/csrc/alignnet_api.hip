@@ -212,6 +212,7 @@ extern "C" void alignnet_destroy(alignnet_handle* h)
   alignnet_globalreg_free(h);
   alignnet_scene_free(h);
   alignnet_icp_free(h);
+  alignnet_register_free(h);
   pipe_free(h);
   free_ws(h);
   for (auto& pr : h->prof_pending) { hipEventDestroy(pr.a); hipEventDestroy(pr.b); }

@@ -57,15 +57,17 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x)
 }
 
 // grid (ceil(N / 256), B, 2 towers)
+// rows null: pair b is row b of the tables (clouds staged for one call, alignnet_register.hip).  streams non-null: the random stream of pair b is
+// keyed on streams[b] in place of its row -- the draw a dataset would give with the pair installed as that example.  labels null: none gathered.
 __global__ __launch_bounds__(256) void dataset_sample_kernel(const float* __restrict__ pts0, const float* __restrict__ pts1,
                                                              const long long* __restrict__ off, const float* __restrict__ labels,
-                                                             const int* __restrict__ rows, int B, int N, int cap, uint64_t seed,
-                                                             float sigma, float clip, float* __restrict__ out0,
+                                                             const int* __restrict__ rows, const long long* __restrict__ streams, int B, int N,
+                                                             int cap, uint64_t seed, float sigma, float clip, float* __restrict__ out0,
                                                              float* __restrict__ out1, float* __restrict__ lab)
 {
   const int b = blockIdx.y, t = blockIdx.z, n = blockIdx.x * 256 + threadIdx.x;
-  const long long row = rows[b];
-  if (t == 0 && blockIdx.x == 0 && threadIdx.x < 12) {   // the six label tensors of this pair
+  const long long row = rows ? rows[b] : b;
+  if (labels && t == 0 && blockIdx.x == 0 && threadIdx.x < 12) {   // the six label tensors of this pair
     const int c = threadIdx.x;
     int tt = 0;
     while (tt < 5 && c >= lab_col(tt + 1)) ++tt;
@@ -75,7 +77,8 @@ __global__ __launch_bounds__(256) void dataset_sample_kernel(const float* __rest
   const long long lo = off[row * 2 + t], cnt = off[(row + 1) * 2 + t] - lo;
   float* dst = (t ? out1 : out0) + ((size_t)b * N + n) * 3;
   if (cnt <= 0) { dst[0] = dst[1] = dst[2] = 0.f; return; }   // provider.py:97-98: empty cloud -> zeros
-  const uint64_t key = mix64(seed ^ ((uint64_t)row * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(2 * n + t) * 0xD1B54A32D192ED03ull));
+  const uint64_t stream = streams ? (uint64_t)streams[b] : (uint64_t)row;
+  const uint64_t key = mix64(seed ^ (stream * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)(2 * n + t) * 0xD1B54A32D192ED03ull));
   // uniform index in [0, cnt): high 64 bits of key32 * cnt
   const long long pick = (long long)(((key >> 32) * (uint64_t)cnt) >> 32);
   const float* src = (t ? pts1 : pts0) + (lo + pick) * 3;
@@ -122,8 +125,23 @@ bool alignnet_dataset_tables(alignnet_handle* h, alignnet::DatasetTables* out)
 {
   if (!h || !h->dataset_ws) return false;
   DatasetWS* w = dws(h);
-  out->pts[0] = w->pts[0]; out->pts[1] = w->pts[1]; out->off = w->off; out->n = w->n; out->h_off = w->h_off.data();
+  out->pts[0] = w->pts[0]; out->pts[1] = w->pts[1]; out->off = w->off; out->n = w->n; out->h_off = w->h_off.data(); out->labels = w->labels;
   return true;
+}
+
+int alignnet_dataset_sample_launch(alignnet_handle* h, const alignnet::SampleSource& s, int B, int cap, uint64_t seed, float* out0, float* out1,
+                                   float* lab, alignnet_labels* lab_ptrs)
+{
+  const int N = h->cfg.num_points;
+  hipLaunchKernelGGL(dataset_sample_kernel, dim3((N + 255) / 256, B, 2), dim3(256), 0, h->stream, s.pts[0], s.pts[1], s.off, s.labels, s.rows,
+                     s.streams, B, N, cap, seed, 0.f, 0.f, out0, out1, lab);
+  HIP_TRY(h, hipGetLastError());
+  if (lab_ptrs) {
+    lab_ptrs->translations = lab + lab_off(0, cap); lab_ptrs->rel_angles = lab + lab_off(1, cap);
+    lab_ptrs->pc1_centers = lab + lab_off(2, cap); lab_ptrs->pc2_centers = lab + lab_off(3, cap);
+    lab_ptrs->pc1_angles = lab + lab_off(4, cap); lab_ptrs->pc2_angles = lab + lab_off(5, cap);
+  }
+  return 0;
 }
 
 extern "C" int alignnet_dataset_free(alignnet_handle* h)
@@ -193,7 +211,7 @@ extern "C" int alignnet_dataset_sample(alignnet_handle* h, const int32_t* rows, 
   HIP_TRY(h, hipMemcpyAsync(w->d_rows, rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   const int N = h->cfg.num_points;
   hipLaunchKernelGGL(dataset_sample_kernel, dim3((N + 255) / 256, B, 2), dim3(256), 0, h->stream, w->pts[0], w->pts[1], w->off,
-                     w->labels, w->d_rows, B, N, w->cap, seed, jitter_sigma, jitter_clip, w->d_p[0], w->d_p[1], w->d_lab);
+                     w->labels, w->d_rows, static_cast<const long long*>(nullptr), B, N, w->cap, seed, jitter_sigma, jitter_clip, w->d_p[0], w->d_p[1], w->d_lab);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(h->stream));   // `rows` is the caller's (pageable) memory
   return 0;

@@ -600,8 +600,10 @@ int reserve_grid_ws(alignnet_handle* h, size_t need)
 
 // stage_n2: what the scan's LDS stage is sized for
 int run_icp(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, const double* init, double radius, int its, bool full, double* out,
-            double* fitness, double* rmse, int* iters, const IcpTraceOut* trace = nullptr)
+            double* fitness, double* rmse, int* iters, const IcpTraceOut* trace = nullptr, const alignnet::IcpDeviceIo* dev = nullptr)
 {
+  // dev: init / out / fitness / rmse / iters are device buffers of the caller (alignnet_icp_run_device): nothing is allocated, uploaded, downloaded
+  // or waited for here -- the launches are the same
   const std::vector<long long>& n2 = c.n2;
   if (!init || !out) return fail(h, "icp: null init / out");
   if (!(radius > 0.0) || its < 0) return fail(h, "icp: radius must be > 0 and its >= 0");
@@ -609,7 +611,9 @@ int run_icp(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, c
   // chunks of at most kIcpGridWsBudget (one pair may exceed it alone), every chunk reuses the handle's workspace in stream order
   const int mode = trace ? (trace->grid ? 1 : 0) : h->icp_search;
   std::vector<char> grid(B, 0);
-  std::vector<long long> ws_off(B, 0);
+  std::vector<long long> ws_off_own;
+  std::vector<long long>& ws_off = dev ? *dev->h_ws_off : ws_off_own;
+  ws_off.assign(B, 0);
   size_t need = 0, cur = 0; int open = -1;
   for (int b = 0; b < B; ++b) {
     grid[b] = mode == 1 || (mode == 2 && n2[b] > kIcpGridAuto);
@@ -624,15 +628,17 @@ int run_icp(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, c
   IcpGridArgs a;
   IcpResults res;
   DevBuf<long long> wsoff;
-  if (res.up(h, B, init, &a)) return 1;
+  if (dev) { a.init = init; a.out = out; a.fitness = fitness; a.rmse = rmse; a.iters = iters; }
+  else if (res.up(h, B, init, &a)) return 1;
+  long long* const d_ws_off = dev ? dev->ws_off : nullptr;
   if (need) {
-    HIP_TRY(h, wsoff.alloc((size_t)B));
-    HIP_TRY(h, hipMemcpyAsync(wsoff.p, ws_off.data(), (size_t)B * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    if (!dev) HIP_TRY(h, wsoff.alloc((size_t)B));
+    HIP_TRY(h, hipMemcpyAsync(dev ? d_ws_off : wsoff.p, ws_off.data(), (size_t)B * sizeof(long long), hipMemcpyHostToDevice, h->stream));
   }
   a.pts[0] = c.pts[0]; a.pts[1] = c.pts[1]; a.off = c.off; a.rows = c.rows; a.radius = radius; a.its = its;
   a.lds_points = (int)std::max<long long>(1, std::min(kIcpLdsBudget, stage_n2));
   a.tr_index = a.tr_inlier = a.tr_paths = nullptr; a.tr_dist = nullptr;
-  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = wsoff.p;
+  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = dev ? d_ws_off : wsoff.p;
   DevBuf<char> tr;   // [n1] doubles | 3 x [n1] ints
   if (trace) {
     if (trace->lds_points > 0) a.lds_points = trace->lds_points;
@@ -702,6 +708,7 @@ int run_icp(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, c
     if (trace->grid) HIP_TRY(h, hipMemcpyAsync(trace->info, h->icp_grid_ws, sizeof(IcpGridInfo), hipMemcpyDeviceToHost, h->stream));
     else *trace->lds_points_used = a.lds_points;
   }
+  if (dev) return 0;
   return res.down(h, B, out, fitness, rmse, iters);
 }
 
@@ -1039,14 +1046,17 @@ struct IcpPlaneTrace { long long n1, n2; double* normals; int* neighbours; int* 
 
 // shared driver of the point-to-plane entry points: clouds already on the device
 int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* init, double radius, double normal_radius, int its, bool full, double* out,
-                  double* fitness, double* rmse, int* iters, const IcpPlaneTrace* trace = nullptr)
+                  double* fitness, double* rmse, int* iters, const IcpPlaneTrace* trace = nullptr, const alignnet::IcpDeviceIo* dev = nullptr)
 {
+  // dev: as in run_icp
   const std::vector<long long>& n2 = c.n2;
   if (!init || !out) return fail(h, "icp_plane: null init / out");
   if (!(radius > 0.0) || !(normal_radius > 0.0) || its < 0) return fail(h, "icp_plane: radius and normal_radius must be > 0 and its >= 0");
   // consecutive pairs form chunks of at most kIcpGridWsBudget of workspace (two grids, the ordered records, normals and counts per pair; one pair may
   // exceed it alone); every chunk reuses the handle's workspace -- the grid search's -- in stream order
-  std::vector<long long> ws_off(2 * (size_t)B, 0);
+  std::vector<long long> ws_off_own;
+  std::vector<long long>& ws_off = dev ? *dev->h_ws_off : ws_off_own;
+  ws_off.assign(2 * (size_t)B, 0);
   std::vector<int> first;   // the chunks' first pairs
   const size_t budget = h->icp_plane_ws_budget ? h->icp_plane_ws_budget : kIcpGridWsBudget;
   constexpr int kChunkPairs = 1 << 20;   // pairs x parts (<= 1024) of a chunk stay a valid gridDim.x
@@ -1066,12 +1076,14 @@ int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* i
   IcpResults res;
   DevBuf<long long> wsoff;
   DevBuf<double> trd; DevBuf<int> tri;   // the read-back's records
-  if (res.up(h, B, init, &a)) return 1;
-  HIP_TRY(h, wsoff.alloc((size_t)B * 2));
-  HIP_TRY(h, hipMemcpyAsync(wsoff.p, ws_off.data(), (size_t)B * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  if (dev) { a.init = init; a.out = out; a.fitness = fitness; a.rmse = rmse; a.iters = iters; }
+  else if (res.up(h, B, init, &a)) return 1;
+  if (!dev) HIP_TRY(h, wsoff.alloc((size_t)B * 2));
+  long long* const d_ws_off = dev ? dev->ws_off : wsoff.p;
+  HIP_TRY(h, hipMemcpyAsync(d_ws_off, ws_off.data(), (size_t)B * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
   a.pts[0] = c.pts[0]; a.pts[1] = c.pts[1]; a.off = c.off; a.rows = c.rows; a.radius = radius; a.its = its; a.lds_points = 0;
   a.tr_index = a.tr_inlier = a.tr_paths = nullptr; a.tr_dist = a.tr_resid = a.tr_sums = a.tr_update = nullptr;
-  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = wsoff.p; a.ws_off_b = wsoff.p + B; a.normal_radius = normal_radius; a.parts = 1;
+  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = d_ws_off; a.ws_off_b = d_ws_off + B; a.normal_radius = normal_radius; a.parts = 1;
   const size_t tn = trace ? (size_t)std::max<long long>(trace->n1, 1) : 0;
   if (trace) {   // doubles: dist [n1] | residual [n1] | sums [29] | update [12]; ints: index [n1] | inlier [n1]
     HIP_TRY(h, trd.alloc(2 * tn + kIcpPlaneSumsFull + 12));
@@ -1139,6 +1151,7 @@ int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* i
     HIP_TRY(h, hipMemcpyAsync(trace->sums, trd.p + 2 * tn, kIcpPlaneSumsFull * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(trace->update, trd.p + 2 * tn + kIcpPlaneSumsFull, 12 * 8, hipMemcpyDeviceToHost, h->stream));
   }
+  if (dev) return 0;
   return res.down(h, B, out, fitness, rmse, iters);
 }
 
@@ -1160,6 +1173,18 @@ int icp_flags(alignnet_handle* h, const char* fn, int32_t flags, bool* full)
 }
 
 }  // namespace
+
+int alignnet_icp_run_device(alignnet_handle* h, const float* const pts[2], const long long* off, const int* rows, const long long* n2, long long stage_n2,
+                            int B, const alignnet::IcpDeviceIo& io, double radius, double normal_radius, int its, bool full, bool plane)
+{
+  if (!h) return 1;
+  if (!pts[0] || !pts[1] || !off || !n2 || B < 1 || !io.ws_off || !io.h_ws_off) return fail(h, "icp: null device argument or B < 1");
+  IcpClouds c;   // (nothing of it is uploaded here: its buffers stay empty)
+  c.pts[0] = pts[0]; c.pts[1] = pts[1]; c.off = off; c.rows = rows;
+  c.n2.assign(n2, n2 + B);
+  if (plane) return run_icp_plane(h, c, B, io.init, radius, normal_radius, its, full, io.out, io.fitness, io.rmse, io.iters, nullptr, &io);
+  return run_icp(h, c, stage_n2 > 0 ? stage_n2 : kIcpLdsBudget, B, io.init, radius, its, full, io.out, io.fitness, io.rmse, io.iters, nullptr, &io);
+}
 
 extern "C" int alignnet_icp_refine(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
                                    const double* init, double radius, int32_t its, double* out, double* fitness, double* rmse,

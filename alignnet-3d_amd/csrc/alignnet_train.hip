@@ -2130,6 +2130,23 @@ extern "C" int alignnet_eval_loss(alignnet_handle* h, const alignnet_labels* lab
   return 0;
 }
 
+size_t alignnet_eval_loss_work_floats(int B) { return 32 + loss_scratch_floats(B); }
+
+int alignnet_eval_loss_launch(alignnet_handle* h, const alignnet_labels* d_labels, int B, float* d_work)
+{
+  if (B != h->last_B || B < 1) return fail(h, "eval loss: B must equal the batch of the preceding forward");
+  Workspace& ws = h->ws;
+  const int nb = h->cfg.num_bins, nb2 = 2 * nb;
+  LossArgs la{};
+  la.B = B; la.nb = nb; la.esf = h->cfg.early_stage_factor; la.af = h->cfg.angle_factor; la.accept_inverted = h->cfg.accept_inverted_angle;
+  la.s1c = ws.s1c; la.s2c = ws.s2c; la.o2 = ws.o2; la.ldo2 = 3 + nb2; la.o3 = ws.o3; la.ldo3 = 3 + nb2; la.theta = ws.theta; la.pcls = ws.cls;
+  la.tr = d_labels->translations; la.c1 = d_labels->pc1_centers; la.c2 = d_labels->pc2_centers; la.a1 = d_labels->pc1_angles; la.a2 = d_labels->pc2_angles;
+  la.out = d_work; la.scratch = d_work + 32; la.want_grad = 0;
+  launch_loss(h, la);
+  HIP_TRY(h, hipGetLastError());
+  return 0;
+}
+
 extern "C" int alignnet_grad_buffer(alignnet_handle* h, float** d_grad, size_t* count)
 {
   if (!h) return 1;

@@ -59,7 +59,16 @@ struct Workspace {
 }  // namespace alignnet
 
 namespace alignnet {
-struct DatasetTables { const float* pts[2]; const long long* off; long long n; const long long* h_off; };   // device pointers of the uploaded dataset; h_off: the host's copy of off
+struct DatasetTables { const float* pts[2]; const long long* off; long long n; const long long* h_off; const float* labels; };   // device pointers of the uploaded dataset; h_off: the host's copy of off
+// what one launch of the device sampler reads (alignnet_dataset.hip: dataset_sample_kernel): point blobs, offsets [n + 1][2], labels [n][12] or null,
+// rows [B] or null (pair b = row b), streams [B] or null (the random stream of pair b is its row's)
+struct SampleSource { const float* pts[2]; const long long* off; const float* labels; const int* rows; const long long* streams; };
+// ICP from buffers that are on the device already (alignnet_icp.hip: alignnet_icp_run_device): no upload of the inits, no download, no synchronisation
+struct IcpDeviceIo {
+  const double* init; double* out; double* fitness; double* rmse; int* iters;   // [B][16], [B][16], [B], [B], [B]
+  long long* ws_off;                    // [2 B] device scratch: the pairs' workspace offsets
+  std::vector<long long>* h_ws_off;     // their host staging; must outlive the queued copy (the caller's next synchronisation)
+};
 }
 // A/B dispatch overrides (alignnet_set_option "ab_<name>", default 0): each selects another kernel variant of the SAME arithmetic (an
 // earlier instantiation kept for same-box comparisons and as a test hook); results agree up to summation order.  The library reads
@@ -89,6 +98,17 @@ bool alignnet_dataset_tables(alignnet_handle* h, alignnet::DatasetTables* out); 
 // alignnet_dataset.hip: what alignnet_dataset_upload does, the point blobs read from host or (device_points) from device memory; `fn` names the caller in messages
 int alignnet_dataset_install(alignnet_handle* h, const float* points1, const float* points2, bool device_points, const int64_t* offsets, const float* labels,
                              int64_t n_examples, const char* fn);
+// alignnet_dataset.hip: queue one draw (no jitter) of B pairs from `s` into out0 / out1 [B][N][3] and, with labels, into lab [12][cap]; lab_ptrs: the six tensors inside lab
+int alignnet_dataset_sample_launch(alignnet_handle* h, const alignnet::SampleSource& s, int B, int cap, uint64_t seed, float* out0, float* out1,
+                                   float* lab, alignnet_labels* lab_ptrs);
+// alignnet_icp.hip: what alignnet_icp_register* / alignnet_icp_plane_register* (plane) queue for clouds that are staged already, from and into device
+// buffers.  n2: the B target sizes (host); stage_n2: what the scan's LDS stage is sized for (<= 0: its budget, as the _dataset entry points size it)
+int alignnet_icp_run_device(alignnet_handle* h, const float* const pts[2], const long long* off, const int* rows, const long long* n2, long long stage_n2,
+                            int B, const alignnet::IcpDeviceIo& io, double radius, double normal_radius, int its, bool full, bool plane);
+// alignnet_train.hip: the loss of alignnet_eval_loss on the last eval forward from DEVICE labels, queued only: d_work[0] = loss, [1..16] = summaries
+size_t alignnet_eval_loss_work_floats(int B);
+int alignnet_eval_loss_launch(alignnet_handle* h, const alignnet_labels* d_labels, int B, float* d_work);
+void alignnet_register_free(alignnet_handle* h);   // alignnet_register.hip
 int alignnet_drain_profile(alignnet_handle* h);
 // options that live with the training / communicator code (alignnet_train.hip); -1 = not one of its keys
 int alignnet_train_set_option(alignnet_handle* h, const std::string& key, int64_t value);
@@ -141,6 +161,7 @@ struct alignnet_handle {
   void* globalreg_ws = nullptr;    // stage arrays of the global registration (alignnet_globalreg.hip), grown on demand
   size_t globalreg_ws_bytes = 0;
   int icp_search = 0;              // alignnet_set_option("icp_search"): 0 = scan, 1 = grid, 2 = grid for pairs beyond the scan's LDS stage (alignnet_icp.hip)
+  void* register_ws = nullptr;     // buffers of the one-call registration (alignnet_register.hip), grown on demand
   void* icp_grid_ws = nullptr;     // bucket-sorted targets + cell tables of the grid search (alignnet_icp.hip), grown on demand
   size_t icp_grid_ws_bytes = 0, icp_grid_ws_used = 0;   // allocated; carved by the last call ("icp_grid_ws_bytes")
   size_t icp_plane_ws_budget = 0;  // "icp_plane_ws_budget": workspace of one chunk of point-to-plane pairs; 0 = the grid search's 1 GiB

@@ -115,6 +115,20 @@ class Run:
         if flags.refineICP:
             set_icp_search(self.engine)
             log_icp_estimate()
+        # evaluation.register = "device": one engine call per evaluation batch (Engine.register_rows) in place of forward + host decode +
+        # get_mat_angle + ICP call; it needs the full clouds in HBM like --refineICP
+        self.register_device = False
+        if register_option() == "device":
+            if self.world > 1:
+                logger.info("evaluation.register = device: the batch is split over %d ranks, falling back to host" % self.world)
+            elif flags.use_old_results and flags.refineICP:
+                logger.info("evaluation.register = device: --use_old_results takes the ICP inits from files, falling back to host")
+            else:
+                self.register_device = True
+                if self.icp_data is None:
+                    self.icp_data = provider.use_packed_cache()
+                    self.icp_data.upload(self.engine)
+                logger.info("evaluation: one register call per batch (evaluation.register = device)")
         self.train_idx = provider.getDataFiles("%s/split/train.txt" % cfg.data.basepath)
         self.val_idx = provider.getDataFiles("%s/split/val.txt" % cfg.data.basepath)
         self.batches_per_epoch = len(self.train_idx) // cfg.training.batch_size
@@ -216,9 +230,34 @@ class Run:
         for b in range(int(np.ceil(nval / B))):
             s, e = b * B, min((b + 1) * B, nval)
             n = e - s
-            batch = provider.load_batch(val[s:e], override_batch_size=override_batch_size, dont_load_pointclouds=self.device_data is not None)
+            batch = provider.load_batch(val[s:e], override_batch_size=override_batch_size,
+                                        dont_load_pointclouds=self.device_data is not None or self.register_device)
             lo, hi = parallel.shard_range(n, self.rank, self.world)
             t0 = time.time()
+            if self.register_device:
+                # sampler, forward, decode, initial transform and (with --refineICP) the ICP on the full clouds in one call; the seed is drawn
+                # from np.random as the forward_rows path draws it
+                estimate, normal_radius = icp_estimate_option()
+                res = self.engine.register_rows(self.icp_data.rows_of(val[s:e]), seed=int(np.random.randint(0, 2 ** 62)),
+                                                refine=estimate if refine else None, radius=0.1, normal_radius=normal_radius,
+                                                its=int(flags.its) if refine else 0, want_net=True, want_loss=n == B)
+                cumulated += time.time() - t0
+                if n == B:   # last (partial) batch is not counted (train.py:458)
+                    loss_sum += res["loss"][0]
+                ep = {k: res[k] for k in ("pred_translations", "pred_remaining_angle_logits", "pred_s1_pc1centers", "pred_s1_pc2centers",
+                                          "pred_s2_pc1centers", "pred_s2_pc2centers", "pred_pc1angle_logits", "pred_pc2angle_logits")}
+                a1, a2, pred_angles = res["angles"][:, 0], res["angles"][:, 1], res["angles"][:, 3]
+                if refine:   # as below: the refined transform is about the origin
+                    T = res["transforms"]
+                    ep["pred_translations"] = T[:, :3, 3].astype(np.float32)
+                    pred_angles = np.arctan2(T[:, 1, 0], T[:, 0, 0])
+                    ep["pred_s2_pc1centers"] = np.zeros((n, 3), np.float32)
+                store["pred_angles"][s:e, 0] = pred_angles
+                store["pred_s2_pc1angles"][s:e, 0], store["pred_s2_pc2angles"][s:e, 0] = a1, a2
+                for k in names3:
+                    store[k][s:e] = ep[k]
+                gt_t[s:e], gt_a[s:e], gt_c1[s:e] = batch[2][:n], batch[3][:n], batch[4][:n]
+                continue
             if hi > lo and self.device_data is not None:
                 ep = self.engine.forward_rows(self.device_data.rows_of(val[s:e])[lo:hi], seed=int(np.random.randint(0, 2 ** 62)))
             elif hi > lo:
@@ -348,6 +387,21 @@ def set_icp_search(engine):
     engine.set_option("icp_search", value)
     if value:
         logger.info("ICP correspondence search: %s" % name)
+
+
+REGISTER = ("host", "device")
+
+
+def register_option(config=None, environ=None):
+    """Optional, not a reference key: "evaluation": {"register": "host" | "device"} (or ALIGNNET_REGISTER, which wins when set).  host (default):
+    the evaluation loop as it was -- forward, host decode, get_mat_angle, ICP call.  device: one Engine.register_rows call per batch, the join
+    between the stages on the device.  Returns the name."""
+    config = cfg if config is None else config
+    environ = os.environ if environ is None else environ
+    name = str(environ.get("ALIGNNET_REGISTER", "") or getattr(getattr(config, "evaluation", None), "register", "host")).lower()
+    if name not in REGISTER:
+        raise ValueError("evaluation.register / ALIGNNET_REGISTER = %r: expected one of %s" % (name, ", ".join(REGISTER)))
+    return name
 
 
 ICP_ESTIMATE = ("point", "plane")

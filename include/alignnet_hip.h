@@ -377,6 +377,56 @@ int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1, int64_t n
                              int32_t* neighbours, int32_t* index, double* dist2, int32_t* inlier, double* residual,
                              double* sums, double* update, double* fitness, double* rmse);
 
+/* ---- one-call registration: two raw clouds per pair in, a 4x4 transform per pair out ------------
+ * The chain the evaluation loop joins in host Python (train.py:447-481), queued as one piece on the device: the
+ * sampler (alignnet_dataset_sample's draw, no jitter), the eval forward, the decode of the three yaws in fp64
+ * (models/tp8.py:55-65 classLogits2angle: first maximum of the nb class logits, angle = class * (2 pi / nb) +
+ * residual logit of that class, minus 2 pi when > pi; the residual is not de-normalised), pred_angle = (a2 - a1) + a_rem,
+ * T_net = get_mat_angle(pred_translation, pred_angle, rotation_center = pred_s2_pc1center) (evaluation.py:46-57:
+ * rotation about z around the centre, then the translation; float32 inputs widened, everything else float64), and with
+ * `refine` the ICP of alignnet_icp_register (1) or alignnet_icp_plane_register (2) on the FULL clouds from T_net:
+ * the handle's "icp_search" option, that entry point's stop rule and results, bit for bit what it returns for
+ * init = T_net.  Nothing returns to the host between the stages: one synchronisation, at the end, with the downloads;
+ * the buffers live in a workspace on the handle that grows with B (and, for host clouds, with their size) and is
+ * released by alignnet_destroy.
+ *   alignnet_register_dataset: rows of the uploaded dataset; draws the batch alignnet_forward_dataset(rows, B, seed)
+ *     draws, so `net` receives exactly what that call returns.
+ *   alignnet_register: clouds from the host, concatenated, offsets [B + 1][2] as in alignnet_icp_register.  Pair b is
+ *     drawn as the dataset form would draw it were the pair installed as example streams[b] (NULL: b, the pair index).
+ *   An empty cloud samples to N points at the origin (provider.py:97-98); ICP leaves such a pair at T_net.
+ *   options: refine 0 = none (its must be 0; fitness / rmse / iterations must be NULL), 1 = point-to-point, 2 =
+ *     point-to-plane; its >= 0; flags = ALIGNNET_ICP_FULL_ROTATION or 0; radius > 0 when refining; normal_radius > 0
+ *     for refine 2.
+ *   outputs: every pointer may be NULL except transforms.  transforms / network_transforms [B][16] row-major float64
+ *     (transforms = the refined estimate, or T_net without refinement); angles [B][4] = a1, a2, a_rem, pred_angle;
+ *     net = host arrays for the eight raw forward outputs (each may be NULL); loss [17] = loss + the 16 summaries of
+ *     alignnet_eval_loss against the dataset's labels of the rows (_dataset only; a partial batch is the caller's
+ *     business).
+ * Errors (null arguments, B < 1, offsets that decrease or start below 0, a row out of range, no dataset, bad option
+ * values) are found before anything is queued: the engine's state is what it was. */
+typedef struct {
+  int32_t refine;        /* 0 none, 1 point-to-point, 2 point-to-plane */
+  int32_t its;           /* ICP iterations, >= 0; with refine 0 must be 0 */
+  int32_t flags;         /* ALIGNNET_ICP_FULL_ROTATION or 0; anything else is an error */
+  double  radius;        /* > 0 when refine != 0 */
+  double  normal_radius; /* refine 2 only */
+} alignnet_register_options;
+
+typedef struct {         /* every pointer may be NULL except transforms */
+  double* transforms;          /* [B][16] final estimate: refined, or T_net when refine == 0 */
+  double* network_transforms;  /* [B][16] T_net */
+  double* angles;              /* [B][4] a1, a2, a_rem, pred_angle (fp64) */
+  const alignnet_outputs* net; /* the eight raw forward outputs, as alignnet_forward_dataset fills them */
+  double* fitness; double* rmse; int32_t* iterations;  /* of the refinement; error if non-NULL with refine == 0 */
+  float*  loss;                /* [17] loss + 16 summaries vs the dataset's labels; _dataset only */
+} alignnet_register_outputs;
+
+int alignnet_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets,
+                      int32_t B, uint64_t seed, const int64_t* streams, const alignnet_register_options* options,
+                      const alignnet_register_outputs* outputs);
+int alignnet_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, uint64_t seed,
+                              const alignnet_register_options* options, const alignnet_register_outputs* outputs);
+
 /* ---- global registration: RANSAC on FPFH feature matches (the `o3_gicp` baseline, icp.py:85-143) --------------
  * Per pair: voxel downsample (0.05 m) of both clouds, normals (radius 0.10, 30 nearest), FPFH (radius 0.25, 100
  * nearest), nearest-feature matches, then RANSAC (4 correspondences, edge-length 0.9 and distance checks, threshold
