@@ -168,6 +168,9 @@ SYMBOLS = {
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "alignnet_debug_scene_cast_binned": (C.c_int, [H, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "alignnet_debug_scene_cast_rows": (C.c_int, [H, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_int64)]),
     "alignnet_set_option": (C.c_int, [H, C.c_char_p, C.c_int64]),
     "alignnet_get_option": (C.c_int, [H, C.c_char_p, C.POINTER(C.c_int64)]),
     "alignnet_profile_read_kernel": (C.c_int, [H, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

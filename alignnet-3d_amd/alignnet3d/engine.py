@@ -744,25 +744,34 @@ class Engine:
         assert hasattr(self, "_scene_offsets") and lab.shape[0] == self._scene_offsets.shape[0] - 1, "one label row per generated scene"
         self._check(self._lib.alignnet_scene_install_dataset(self._h, _fp(lab)))
 
-    def debug_scene_cast(self, mesh, scale, pose, lds_triangles=0, binned=False):
+    def debug_scene_cast(self, mesh, scale, pose, lds_triangles=0, binned=False, rows=False):
         """Test hook: ONE cloud by the shipped cast kernel, no noise.  Returns dict(t [64, 4500] float64 (inf = miss), triangle [64, 4500] (-1), window =
         (first column, columns), lds_triangles as used).  lds_triangles in 1 .. 512 forces several LDS chunks on small meshes.  binned=False: the scan;
         True: the binned cast (set_option("scene_cast", 1) selects it for scene_generate; this read-back takes it whatever the option says), and the
-        dict also holds tile_counts [tiles of the window] (the length of every tile's triangle list) and entries (their sum)."""
+        dict also holds tile_counts [tiles of the window] (the length of every tile's triangle list) and entries (their sum).  rows=True: the
+        chosen staging with its inner loop by elevation band (set_option("scene_rows", 1) selects that for scene_generate; again whatever the option
+        says): the record (t, triangle, window, lds_triangles) plus cell_counts [tiles of the window, 8] (the staged triangles per tile and band of 8
+        rows whose band bit was set) and cells (their sum)."""
         pose = np.ascontiguousarray(pose, np.float64).reshape(4)
         t, tri = np.empty(64 * 4500, np.float64), np.empty(64 * 4500, np.int32)
         win, used = np.zeros(2, np.int32), np.zeros(1, np.int32)
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         args = (self._h, int(mesh), float(scale), pose.ctypes.data_as(C.POINTER(C.c_double)), int(lds_triangles),
                 t.ctypes.data_as(C.POINTER(C.c_double)), ip(tri), ip(win), ip(used))
-        if binned:
+        if rows:
+            cell_counts, cells = np.zeros((563, 8), np.int32), C.c_int64(0)
+            self._check(self._lib.alignnet_debug_scene_cast_rows(*args[:5], int(bool(binned)), ip(win), args[5], ip(tri), ip(used), ip(cell_counts),
+                                                                 C.byref(cells)))
+        elif binned:
             counts, entries = np.zeros(563, np.int32), C.c_int64(0)
             self._check(self._lib.alignnet_debug_scene_cast_binned(*args, ip(counts), C.byref(entries)))
         else:
             self._check(self._lib.alignnet_debug_scene_cast(*args))
         self.__dict__.pop("_scene_offsets", None)
         out = dict(t=t.reshape(64, 4500), triangle=tri.reshape(64, 4500), window=(int(win[0]), int(win[1])), lds_triangles=int(used[0]))
-        if binned:
+        if rows:
+            out.update(cell_counts=cell_counts[:(int(win[1]) + 7) // 8].copy(), cells=int(cells.value))
+        elif binned:
             out.update(tile_counts=counts[:(int(win[1]) + 7) // 8].copy(), entries=int(entries.value))
         return out
 
@@ -952,7 +961,7 @@ class Engine:
 
     PROFILED_KERNELS = ("backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1",
                         "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact",
-                        "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane")
+                        "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band")
 
     def profile_kernels(self):
         """{kernel: (ms, launches)} accumulated since the last profile_read(reset=True); call BEFORE that reset."""

@@ -295,16 +295,21 @@ def cast_option(cast):
     return CASTS[cast]
 
 
-def generate(engine, scenes, seed=0, meshes="builtin", noise=True, sigma=0.05, clip=0.05, install=False, cast="scan"):
+def generate(engine, scenes, seed=0, meshes="builtin", noise=True, sigma=0.05, clip=0.05, install=False, cast="scan", rows=False):
     """Cast `scenes` (draw_scene results) on the GPU.  The noise key of a scene is (seed, scene.seed): a scene's clouds do not depend on
     what else is in the list.  Returns the offsets table [B + 1, 2]; the clouds stay on the device -- engine.scene_read() copies them
     out, install=True makes them the HBM-resident dataset (engine.sample_batch, train_step_rows, icp_refine_rows, ... work on it).
     cast: "scan" (every tile of a cloud's window goes through the whole mesh), "binned" (the triangles are binned to the tiles first) or
     "auto" (binned for meshes of more than 512 triangles); it sets the engine option "scene_cast", which stays set.  The clouds are the same
     bit for bit whichever is chosen; "binned" and "auto" are exact alternatives that were slower than "scan" at every mesh size measured
-    (516 to 100,002 triangles: profiles/scene_cast_rate.json)."""
+    (516 to 100,002 triangles: profiles/scene_cast_rate.json).
+    rows: True runs the inner loop of the chosen cast by elevation band (a staged triangle is intersected only with the bands of 8 rows
+    it can reach); it sets the engine option "scene_rows", which stays set, and changes no result either (profiles/scene_rows_rate.json)."""
     option = cast_option(cast)
+    if not isinstance(rows, (bool, np.bool_)):
+        raise ValueError("rows = %r: expected True or False" % (rows,))
     engine.set_option("scene_cast", option)
+    engine.set_option("scene_rows", int(rows))
     lib = meshes if isinstance(meshes, MeshLibrary) else MeshLibrary(meshes)
     first = len(lib.meshes)
     ids = [lib.add(s.cat, s.mesh_id) for s in scenes]

@@ -994,6 +994,7 @@ extern "C" int alignnet_set_option(alignnet_handle* h, const char* key, int64_t 
   if (k == "icp_search") { if (value < 0 || value > 2) return fail(h, "icp_search must be 0 (scan), 1 (grid) or 2 (automatic)"); h->icp_search = (int)value; return 0; }
   if (k == "icp_plane_ws_budget") { if (value < 0) return fail(h, "icp_plane_ws_budget must be >= 0 (0 = 1 GiB)"); h->icp_plane_ws_budget = (size_t)value; return 0; }
   if (k == "scene_cast") { if (value < 0 || value > 2) return fail(h, "scene_cast must be 0 (scan), 1 (binned) or 2 (automatic)"); h->scene_cast = (int)value; return 0; }
+  if (k == "scene_rows") { if (value != 0 && value != 1) return fail(h, "scene_rows must be 0 (whole tiles) or 1 (by elevation band)"); h->scene_rows = (int)value; return 0; }
   for (const auto& ak : kAbKeys)
     if (k == ak.key) {
       const unsigned before = h->ab;
@@ -1035,6 +1036,7 @@ extern "C" int alignnet_get_option(alignnet_handle* h, const char* key, int64_t*
   if (k == "icp_plane_chunks") { *value = h->icp_plane_chunks; return 0; }
   if (k == "icp_grid_ws_bytes") { *value = (int64_t)h->icp_grid_ws_used; return 0; }
   if (k == "scene_cast") { *value = h->scene_cast; return 0; }
+  if (k == "scene_rows") { *value = h->scene_rows; return 0; }
   if (k == "scene_binned_clouds") { *value = h->scene_binned_clouds; return 0; }
   if (k == "scene_bin_entries") { *value = h->scene_bin_entries; return 0; }
   if (k == "ab_mask") { *value = h->ab; return 0; }

@@ -50,7 +50,12 @@
 //     20,001 or 100,002 triangles (0.79 - 0.95 x).  Both casts are bound by the inner loop -- every staged triangle against all 64 x 8 rays of the tile, about
 //     0.6 - 0.8 ns of chip time per (tile, triangle) entry -- and the scan's side tests leave it the same entries; the T / 256 term that binning removes is
 //     the small one (cast kernel 13.6 -> 12.8 ms at 20,001 triangles) and the binning costs more (1.6 ms there).  Fewer rays per entry -- binning by
-//     elevation row inside a tile, for which these lists are the input -- is the step that would pay.  The default stays the scan.
+//     elevation row inside a tile, for which these lists are the input -- is the step that would pay (2c).  The default stays the scan.
+//  2c. BY ELEVATION BAND ("scene_rows" = 1, orthogonal to "scene_cast"; 0, the default, is exactly the kernels above): scene_band_scan_kernel and
+//     scene_band_list_kernel keep the two stagings and replace the inner loop.  A staged triangle gets an 8-bit mask of the bands of 8 rows it can
+//     reach (in SceneTri::pad; the rule and why it is conservative stand above the kernels) and is intersected only with those cells of 8 rows x 8
+//     columns, a lane being one ray; the four waves share the staged entries and merge their candidates per ray at the end.  Bit for bit the scan.
+//     Measured: tools/scene_rows_rate.py, profiles/scene_rows_rate.json, DESIGN.md 4.9c.
 //  3. scene_count_kernel (hits per (cloud, row)), scene_scan_kernel (exclusive scan in (scene, row) order per cloud index: the offsets table),
 //     scene_scatter_kernel (per (cloud, row): columns in ascending COLUMN order -- a wrapped window starts at column 0 -- ballot prefix, location = t d in
 //     fp64 rounded to float, + noise).  Counts, a scan, a scatter: no atomics that could reorder points.
@@ -497,6 +502,299 @@ __global__ __launch_bounds__(kCastThreads) void scene_bincast_kernel(const Scene
   }
 }
 
+// ---- stage 2c: both casts by elevation band ("scene_rows" = 1) --------------------------------------------------------------------------------
+// The tile and the workgroup stay (8 window columns x 64 rows, 256 threads); the unit of work becomes a CELL, one band of 8 consecutive rows x the
+// tile's 8 columns = 64 rays = one wave.  A lane is a ray: column lane & 7 of the tile, row 8 b + (lane >> 3) in band b.  A staged triangle carries
+// an 8-bit band mask in SceneTri::pad and is intersected only with the cells whose bit is set (a wave-uniform skip).
+//
+// THE MASK RULE, and why it is conservative.  A ray of column c and row r has the direction d = (dir_x[c], dir_y[c], dir_z[r]) and meets the
+// triangle at P = t d, t > 0, so P.z = t dir_z[r] and rho(P) = sqrt(P.x^2 + P.y^2) = t n_c with n_c = sqrt(dir_x[c]^2 + dir_y[c]^2):
+//     dir_z[r] = n_c s(P),   s(P) = P.z / rho(P).
+// Over the triangle P.z lies between the extreme vertex z, and rho between rho_min, the distance from the z axis to the triangle's xy projection
+// when that does not hold the axis -- the smallest of the three point-to-segment distances, which an edge can attain strictly inside itself, so
+// it is NOT the smallest vertex rho -- and rho_max, the largest vertex rho (rho is convex).  By the signs of z_min and z_max:
+//     s_lo = z_min / (z_min >= 0 ? rho_max : rho_min),   s_hi = z_max / (z_max >= 0 ? rho_min : rho_max),
+// and with n_lo <= n_c <= n_hi over the tile's columns dir_z[r] lies in [min(s_lo n_lo, s_lo n_hi), max(s_hi n_lo, s_hi n_hi)].  Bit b is set iff
+// one of the band's eight dir_z values lies in that interval, compared one by one (a ballot over lane = row): the table may be any finite numbers.
+// The margin.  s_lo and s_hi are widened by kBandMargin (1 + |s|), 1e-8: seven orders above the rounding of the dozen fp64 operations behind them
+// (the closest point of an edge is p + t e, good to 1e-16 rho_max absolute, and rho_min > 1e-6 rho_max is required below, so rho_min is good to
+// 1e-10 relative), and 1e-6 of a row of the default sensor.  The same margin has to cover what cast_ray calls a hit: it tests the rounded
+// numerators un, vn, un + vn against the rounded den, each off by at most E = 2e-15 |d| e_max P_max (e_max the longest edge, P_max the farthest
+// vertex; their own rounding included), so a "hit" can lie at barycentric coordinates as far as eta = 2 E / |den| outside [0, 1].  At a hit
+// |den| = |c| |d| / |P| >= |c| |d| / (5 P_max) while eta < 1/2, hence eta <= kBandEta e_max P_max^2 / |c| with kBandEta = 2e-14, the point lies
+// within dev = 2 eta e_max of the triangle, and s moves by at most (dev / rho_min) (1 + |s|) (|grad s| = sqrt(1 + s^2) / rho).  A triangle gets
+// the interval only when eta < 1/2 and dev < kBandMargin rho_min / 2.  Everything else gets EVERY band: a projection that holds the z axis
+// (the test of tri_reach, rho_min = 0), rho_min <= 1e-6 rho_max, a plane through or next to the sensor (c = 0: an edge-on face, whose hits are
+// decided by rounding alone) or a sliver.  A face of zero area (N = 0 exactly: den = 0, never hit) gets no band.
+constexpr int kBands = kRows / 8;
+constexpr double kBandMargin = 1e-8, kBandEta = 2e-14;
+static_assert(kTileCols == 8 && kCastThreads == 256 && kBands == 8, "a cell is 8 rows x 8 columns, one wave; the mask is 8 bits");
+
+// squared distance from the origin to the segment p .. q of the xy plane
+__device__ __forceinline__ double seg_dist2(const V3& p, const V3& q)
+{
+#pragma clang fp contract(off)
+  const double ex = q.x - p.x, ey = q.y - p.y, ee = ex * ex + ey * ey;
+  const double t = ee > 0.0 ? fmin(fmax(-(p.x * ex + p.y * ey) / ee, 0.0), 1.0) : 0.0;
+  const double x = p.x + t * ex, y = p.y + t * ey;
+  return x * x + y * y;
+}
+
+// [*lo, *hi]: where dir_z[r] of a row that can hit the posed triangle (a, b, d) lies, for the columns with n_lo <= n_c <= n_hi (the rule above)
+__device__ __forceinline__ void band_interval(const V3& a, const V3& b, const V3& d, const SceneTri& t, double n_lo, double n_hi, double* lo, double* hi)
+{
+#pragma clang fp contract(off)
+  if (t.N[0] == 0.0 && t.N[1] == 0.0 && t.N[2] == 0.0) { *lo = INFINITY; *hi = -INFINITY; return; }   // zero area: no band
+  *lo = -INFINITY; *hi = INFINITY;   // every band, unless all of the following holds
+  const double o1 = a.x * b.y - a.y * b.x, o2 = b.x * d.y - b.y * d.x, o3 = d.x * a.y - d.y * a.x;
+  const double ext = fmax(fmax(fabs(a.x) + fabs(a.y), fabs(b.x) + fabs(b.y)), fabs(d.x) + fabs(d.y));
+  const double m = kSideMargin * ext * ext;
+  bool full;
+  if (fabs(o1 + o2 + o3) > m)
+    full = (o1 >= -m && o2 >= -m && o3 >= -m) || (o1 <= m && o2 <= m && o3 <= m);
+  else
+    full = fmin(fmin(a.x * b.x + a.y * b.y, b.x * d.x + b.y * d.y), d.x * a.x + d.y * a.y) <= m;
+  if (full) return;
+  const double ra = a.x * a.x + a.y * a.y, rb = b.x * b.x + b.y * b.y, rd = d.x * d.x + d.y * d.y;
+  const double rmax2 = fmax(fmax(ra, rb), rd), rmin2 = fmin(fmin(seg_dist2(a, b), seg_dist2(b, d)), seg_dist2(d, a));
+  if (!(rmin2 > 1e-12 * rmax2)) return;
+  const double rmin = sqrt(rmin2), rmax = sqrt(rmax2);
+  const double p2 = fmax(fmax(ra + a.z * a.z, rb + b.z * b.z), rd + d.z * d.z);
+  const double ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z, vx = d.x - b.x, vy = d.y - b.y, vz = d.z - b.z, wx = a.x - d.x, wy = a.y - d.y, wz = a.z - d.z;
+  const double e2 = fmax(fmax((ux * ux + uy * uy) + uz * uz, (vx * vx + vy * vy) + vz * vz), (wx * wx + wy * wy) + wz * wz);
+  // eta < 1/2 and dev = 2 eta e_max < kBandMargin rho_min / 2, eta = kBandEta e_max P_max^2 / |c|, without dividing (a NaN or c = 0 fails both)
+  const double g = kBandEta * p2, ac = fabs(t.c);
+  if (!((g * g) * e2 < 0.25 * (ac * ac)) || !(4.0 * (g * e2) < (kBandMargin * rmin) * ac)) return;
+  const double zmin = fmin(fmin(a.z, b.z), d.z), zmax = fmax(fmax(a.z, b.z), d.z);
+  double s_lo = zmin / (zmin >= 0.0 ? rmax : rmin), s_hi = zmax / (zmax >= 0.0 ? rmin : rmax);
+  s_lo -= kBandMargin * (1.0 + fabs(s_lo)); s_hi += kBandMargin * (1.0 + fabs(s_hi));
+  *lo = fmin(s_lo * n_lo, s_lo * n_hi); *hi = fmax(s_hi * n_lo, s_hi * n_hi);
+}
+
+// the band masks of a wave's triangles, one per lane (have = false: none, mask 0): one triangle at a time, its interval read from its lane and
+// every lane answering for the row of its own number (dzl = dir_z[lane]); the ballot's byte b is band b.  Called by whole waves.
+__device__ __forceinline__ int band_masks(bool have, double lo, double hi, double dzl, int lane)
+{
+  int mine = 0;
+  for (unsigned long long todo = __ballot(have); todo; todo &= todo - 1) {
+    const int src = __ffsll((long long)todo) - 1;
+    const double l = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lo), src), __builtin_amdgcn_readlane(__double2loint(lo), src));
+    const double u = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(hi), src), __builtin_amdgcn_readlane(__double2loint(hi), src));
+    unsigned long long x = __ballot(l <= dzl && dzl <= u);
+    x |= x >> 4; x |= x >> 2; x |= x >> 1;                                            // bit 8 b: some row of band b
+    const int mask = (int)(((x & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56);   // ... gathered into bit b
+    if (lane == src) mine = mask;
+  }
+  return mine;
+}
+
+// one staged triangle against ONE ray: cast_triangle's expressions in cast_triangle's shape (xn, xa, xb: the ray's dx N0 + dy N1, dx A0 + dy A1,
+// dx B0 + dy B1, which the bands of a lane share)
+__device__ __forceinline__ void cast_ray(const SceneTri& t, double xn, double xa, double xb, double dz, double& best, int& bid)
+{
+#pragma clang fp contract(off)
+  const double cc = t.c;
+  const int id = t.id;
+  const double nz = dz * t.N[2], az = dz * t.A[2], bz = dz * t.Bv[2];
+  const double den = xn + nz;
+  const double un = xa + az;
+  const double vn = xb + bz;
+  const double sum = un + vn;
+  const bool hit = den > 0.0 ? (un >= 0.0 && vn >= 0.0 && sum <= den && cc > 0.0)
+                             : (den < 0.0 && un <= 0.0 && vn <= 0.0 && sum >= den && cc < 0.0);
+  if (hit) {
+    const double tt = cc / den;
+    if (tt > 0.0 && (tt < best || (tt == best && id < bid))) { best = tt; bid = id; }
+  }
+}
+
+struct SceneBandArgs {
+  SceneBinCastArgs b;            // (off and list: the list staging only)
+  int* cells;                    // [tiles][8] staged triangles per (tile, band) whose bit is set; the traced instantiations only
+};
+
+// the rays of a lane and what the staging needs of the tile.  Balance: the bands an object covers are few and adjacent, so fixed bands per wave
+// would leave most waves idle; instead wave w takes the staged entries k = w mod 4 over all their set bands, with best / bid per band in
+// registers under an unrolled wave-uniform test, and the four candidates per ray are merged through LDS at the end by the tie rule (the
+// smallest (t, triangle) of a ray in any order is the scan's).  That needs no list of (entry, band) pairs, no prefix sum and no atomics.
+struct BandLane { double dx, dy, dz[kBands], best[kBands]; int bid[kBands]; };
+
+__device__ __forceinline__ void band_begin(const SceneCastArgs& a, const SceneCloud& c, int j0, int ncol, int lane, BandLane& r, double* n_lo, double* n_hi)
+{
+  const int col = (c.first + j0 + min(lane & 7, ncol - 1)) % kCols;   // (a column past the tile's end runs along on the last one; never stored)
+  r.dx = a.dir[col]; r.dy = a.dir[kCols + col];
+#pragma unroll
+  for (int b = 0; b < kBands; ++b) { r.dz[b] = a.dir[2 * kCols + 8 * b + (lane >> 3)]; r.best[b] = INFINITY; r.bid[b] = -1; }
+  double lo = INFINITY, hi = 0.0;
+  for (int q = 0; q < ncol; ++q) {
+    const int cq = (c.first + j0 + q) % kCols;
+    const double x = a.dir[cq], y = a.dir[kCols + cq], n = sqrt(x * x + y * y);
+    lo = fmin(lo, n); hi = fmax(hi, n);
+  }
+  *n_lo = lo; *n_hi = hi;
+}
+
+// the n staged triangles against the tile: wave w takes k = w, w + 4, ...
+__device__ __forceinline__ void band_cast(const SceneTri* tris, int n, int wave, BandLane& r)
+{
+#pragma clang fp contract(off)
+  for (int k = wave; k < n; k += kCastThreads / 64) {
+    const SceneTri& t = tris[k];   // every lane reads the same address: a broadcast
+    const int mask = __builtin_amdgcn_readfirstlane(t.pad);
+    if (mask == 0) continue;
+    const double xn = r.dx * t.N[0] + r.dy * t.N[1], xa = r.dx * t.A[0] + r.dy * t.A[1], xb = r.dx * t.Bv[0] + r.dy * t.Bv[1];
+#pragma unroll
+    for (int b = 0; b < kBands; ++b)
+      if (mask & (1 << b)) cast_ray(t, xn, xa, xb, r.dz[b], r.best[b], r.bid[b]);
+  }
+}
+
+// traced: threads 0 .. 7 count the staged triangles whose bit of their band is set
+__device__ __forceinline__ int band_tally(const SceneTri* tris, int n, int band)
+{
+  int s = 0;
+  for (int k = 0; k < n; ++k) s += (tris[k].pad >> band) & 1;
+  return s;
+}
+
+// the four waves' candidates per ray, two bands at a time through 6 KiB of LDS; t (and the triangle) to the [row][window column] table
+template <bool kTrace>
+__device__ __forceinline__ void band_merge_store(const SceneCastArgs& a, const SceneCloud& c, int j0, int ncol, const BandLane& r,
+                                                 double (*mt)[2][64], int (*mi)[2][64])
+{
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int g = 0; g < kBands / 2; ++g) {
+    mt[wave][0][lane] = r.best[2 * g]; mt[wave][1][lane] = r.best[2 * g + 1];
+    mi[wave][0][lane] = r.bid[2 * g]; mi[wave][1][lane] = r.bid[2 * g + 1];
+    __syncthreads();
+    if (tid < 128) {
+      const int h = tid >> 6;
+      double bt = mt[0][h][lane];
+      int bi = mi[0][h][lane];
+#pragma unroll
+      for (int w = 1; w < kCastThreads / 64; ++w) {
+        const double tt = mt[w][h][lane];
+        const int id = mi[w][h][lane];
+        if (tt < bt || (tt == bt && id < bi)) { bt = tt; bi = id; }
+      }
+      if ((lane & 7) < ncol) {
+        const long long o = c.tbase + (long long)(8 * (2 * g + h) + (lane >> 3)) * c.count + j0 + (lane & 7);
+        a.t[o] = bt;
+        if constexpr (kTrace) a.tri[o] = bi;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the scan's staging (scene_cast_kernel's, with the mask; a triangle of no band is not staged)
+template <bool kTrace>
+__global__ __launch_bounds__(kCastThreads) void scene_band_scan_kernel(const SceneBandArgs s)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  SceneTri* tris = reinterpret_cast<SceneTri*>(lds_raw);
+  __shared__ int wcnt[kCastThreads / 64];
+  __shared__ double mt[kCastThreads / 64][2][64];
+  __shared__ int mi[kCastThreads / 64][2][64];
+  const SceneCastArgs& a = s.b.c;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ci = a.tiles[blockIdx.x * 2], j0 = a.tiles[blockIdx.x * 2 + 1] * kTileCols;
+  const SceneCloud c = a.clouds[ci];
+  const int ncol = min(kTileCols, c.count - j0);
+  const int col_a = (c.first + j0) % kCols, col_b = (c.first + j0 + ncol - 1) % kCols;
+  const double ax = a.dir[col_a], ay = a.dir[kCols + col_a], bx = a.dir[col_b], by = a.dir[kCols + col_b];
+  const double dzl = a.dir[2 * kCols + lane];
+  BandLane r;
+  double n_lo, n_hi;
+  band_begin(a, c, j0, ncol, lane, r, &n_lo, &n_hi);
+  int cells = 0;
+  const int L = a.lds_triangles;
+  for (int f0 = 0; f0 < c.nf; f0 += L) {
+    const int fend = min(c.nf, f0 + L);
+    int n = 0;   // triangles staged so far (the same in every thread)
+    for (int r0 = f0; r0 < fend; r0 += kCastThreads) {
+      const int f = r0 + tid;
+      bool keep = false;
+      SceneTri tr;
+      double lo = 0.0, hi = 0.0;
+      if (f < fend) {
+        const int* fi = a.faces + (c.f0 + f) * 3;
+        const V3 p = pose(c, a.verts + (c.v0 + fi[0]) * 3), q = pose(c, a.verts + (c.v0 + fi[1]) * 3), v = pose(c, a.verts + (c.v0 + fi[2]) * 3);
+        const double mp = kSideMargin * 120.0 * (fabs(p.x) + fabs(p.y)), mq = kSideMargin * 120.0 * (fabs(q.x) + fabs(q.y)), mv = kSideMargin * 120.0 * (fabs(v.x) + fabs(v.y));
+        const bool before = ax * p.y - ay * p.x > mp && ax * q.y - ay * q.x > mq && ax * v.y - ay * v.x > mv;
+        const bool behind = bx * p.y - by * p.x < -mp && bx * q.y - by * q.x < -mq && bx * v.y - by * v.x < -mv;
+        keep = !before && !behind;
+        if (keep) { tri_setup(p, q, v, tr); tr.id = f; band_interval(p, q, v, tr, n_lo, n_hi, &lo, &hi); }
+      }
+      tr.pad = band_masks(keep, lo, hi, dzl, lane);
+      keep = keep && tr.pad != 0;
+      const unsigned long long m = __ballot(keep);
+      if (lane == 0) wcnt[wave] = __popcll(m);
+      __syncthreads();
+      int base = n, total = 0;
+#pragma unroll
+      for (int w = 0; w < kCastThreads / 64; ++w) { const int k = wcnt[w]; if (w < wave) base += k; total += k; }
+      if (keep) tris[base + __popcll(m & ((1ull << lane) - 1ull))] = tr;
+      n += total;
+      __syncthreads();
+    }
+    band_cast(tris, n, wave, r);
+    if constexpr (kTrace) if (tid < kBands) cells += band_tally(tris, n, tid);
+    __syncthreads();   // the stage is rewritten by the next chunk
+  }
+  band_merge_store<kTrace>(a, c, j0, ncol, r, mt, mi);
+  if constexpr (kTrace) if (tid < kBands) s.cells[(long long)blockIdx.x * kBands + tid] = cells;
+}
+
+// the list staging (scene_bincast_kernel's, with the mask)
+template <bool kTrace>
+__global__ __launch_bounds__(kCastThreads) void scene_band_list_kernel(const SceneBandArgs s)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  SceneTri* tris = reinterpret_cast<SceneTri*>(lds_raw);
+  __shared__ double mt[kCastThreads / 64][2][64];
+  __shared__ int mi[kCastThreads / 64][2][64];
+  const SceneCastArgs& a = s.b.c;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ci = a.tiles[blockIdx.x * 2], j0 = a.tiles[blockIdx.x * 2 + 1] * kTileCols;
+  const SceneCloud c = a.clouds[ci];
+  const int ncol = min(kTileCols, c.count - j0);
+  const double dzl = a.dir[2 * kCols + lane];
+  BandLane r;
+  double n_lo, n_hi;
+  band_begin(a, c, j0, ncol, lane, r, &n_lo, &n_hi);
+  int cells = 0;
+  const long long e0 = s.b.off[blockIdx.x], e1 = s.b.off[(long long)blockIdx.x + 1];
+  const int L = a.lds_triangles;
+  for (long long s0 = e0; s0 < e1; s0 += L) {
+    const int n = (int)min((long long)L, e1 - s0);
+    for (int k0 = 0; k0 < n; k0 += kCastThreads) {   // (whole waves: band_masks ballots)
+      const int k = k0 + tid;
+      const int f = k < n ? s.b.list[s0 + k] : -1;
+      const bool face = (unsigned)f < (unsigned)c.nf;
+      SceneTri tr;
+      double lo = 0.0, hi = 0.0;
+      if (face) {
+        const int* fi = a.faces + (c.f0 + f) * 3;
+        const V3 p = pose(c, a.verts + (c.v0 + fi[0]) * 3), q = pose(c, a.verts + (c.v0 + fi[1]) * 3), v = pose(c, a.verts + (c.v0 + fi[2]) * 3);
+        tri_setup(p, q, v, tr);
+        band_interval(p, q, v, tr, n_lo, n_hi, &lo, &hi);
+      } else {   // (not a face of this mesh: a triangle that no ray hits, no band)
+        tr.N[0] = tr.N[1] = tr.N[2] = tr.A[0] = tr.A[1] = tr.A[2] = tr.Bv[0] = tr.Bv[1] = tr.Bv[2] = tr.c = 0.0;
+      }
+      tr.id = f; tr.pad = band_masks(face, lo, hi, dzl, lane);
+      if (k < n) tris[k] = tr;
+    }
+    __syncthreads();
+    band_cast(tris, n, wave, r);
+    if constexpr (kTrace) if (tid < kBands) cells += band_tally(tris, n, tid);
+    __syncthreads();   // the stage is rewritten by the next chunk
+  }
+  band_merge_store<kTrace>(a, c, j0, ncol, r, mt, mi);
+  if constexpr (kTrace) if (tid < kBands) s.cells[(long long)blockIdx.x * kBands + tid] = cells;
+}
+
 // ---- stage 3: compaction into ray order + noise ---------------------------------------------------------------------------------------------
 // position k of a window in ascending COLUMN order -> (column, window column)
 __device__ __forceinline__ void ordered_col(const SceneCloud& c, int k, int* col, int* j)
@@ -619,6 +917,7 @@ struct SceneWS {
   // binned cast: list lengths / fill cursors and offsets per (cloud, tile) of the binned clouds, the triangle lists
   int* d_bincnt = nullptr; long long* d_binoff = nullptr; size_t cap_bincnt = 0, cap_binoff = 0;
   int* d_binlist = nullptr; size_t cap_binlist = 0;
+  int* d_cells = nullptr; size_t cap_cells = 0;   // the band read-back: [tiles][8]
   // the last result (alignnet_scene_generate)
   int B = -1;
   std::vector<long long> offsets;           // [B + 1][2]
@@ -666,6 +965,7 @@ int ensure_ws(alignnet_handle* h)
 struct SceneTrace {
   int lds_triangles; double* t; int32_t* triangle; int32_t* window; int32_t* lds_triangles_used;
   bool binned; int32_t* tile_counts /*[kMaxTiles]*/; int64_t* entries;   // the binned read-back
+  bool rows; int32_t* cell_counts /*[kMaxTiles][8]*/; int64_t* cells;    // the band read-back
 };
 
 // B scenes x 2 clouds (or, traced: ONE cloud, pose [4]); results stay on the device
@@ -726,6 +1026,7 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
   // deal the work: (cloud, tile of the window); the t tables and the point blobs are sized by the windows.  Which cast a cloud takes ("scene_cast";
   // the read-backs choose their own) depends on its mesh alone, never on what else is in the call; the binned clouds' tiles come behind the scan's.
   const int mode = trace ? (trace->binned ? 1 : 0) : h->scene_cast;
+  const bool rows = trace ? trace->rows : h->scene_rows != 0;
   std::vector<int> btiles;
   int nbinned = 0, max_nf = 0;
   size_t nt = 0, npts[2] = {0, 0};
@@ -747,6 +1048,7 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
   tiles.insert(tiles.end(), btiles.begin(), btiles.end());
   if (grow(h, &w->d_t, &w->cap_t, nt)) return 1;
   if (trace && grow(h, &w->d_tri, &w->cap_tri, nt)) return 1;
+  if (trace && rows && grow(h, &w->d_cells, &w->cap_cells, (nscan + nbt) * kBands)) return 1;
   if (grow(h, &w->d_tiles, &w->cap_tiles, tiles.size())) return 1;
   for (int k = 0; k < 2; ++k) if (grow(h, &w->d_pts[k], &w->cap_pts[k], npts[k] * 3)) return 1;
   int L = kLdsTriangles;
@@ -781,20 +1083,40 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
       a.clouds = w->d_clouds; a.tiles = w->d_tiles; a.verts = w->d_verts; a.faces = w->d_faces; a.dir = w->d_dir; a.t = w->d_t; a.tri = w->d_tri;
       a.lds_triangles = L;
       const size_t lds = (size_t)L * sizeof(SceneTri);
-      alignnet::ProfScope prof_scope(h, alignnet::PK_SCENE_CAST);
-      if (nscan > 0) {
-        if (trace)
-          hipLaunchKernelGGL(scene_cast_kernel<true>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, a);
-        else
-          hipLaunchKernelGGL(scene_cast_kernel<false>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, a);
-      }
-      if (nbt > 0) {
-        SceneBinCastArgs b;
-        b.c = a; b.c.tiles = w->d_tiles + nscan * 2; b.off = w->d_binoff; b.list = w->d_binlist;
-        if (trace)
-          hipLaunchKernelGGL(scene_bincast_kernel<true>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, b);
-        else
-          hipLaunchKernelGGL(scene_bincast_kernel<false>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, b);
+      alignnet::ProfScope prof_scope(h, rows ? alignnet::PK_SCENE_BAND : alignnet::PK_SCENE_CAST);
+      if (rows) {
+        // by elevation band: the same grids, stage and tile order; the cell counts of the list tiles follow those of the scan tiles, as the tiles do
+        SceneBandArgs s;
+        s.b.c = a; s.b.off = w->d_binoff; s.b.list = w->d_binlist; s.cells = w->d_cells;
+        if (nscan > 0) {
+          if (trace)
+            hipLaunchKernelGGL(scene_band_scan_kernel<true>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, s);
+          else
+            hipLaunchKernelGGL(scene_band_scan_kernel<false>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, s);
+        }
+        if (nbt > 0) {
+          s.b.c.tiles = w->d_tiles + nscan * 2;
+          if (trace) {
+            s.cells = w->d_cells + nscan * kBands;
+            hipLaunchKernelGGL(scene_band_list_kernel<true>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, s);
+          } else
+            hipLaunchKernelGGL(scene_band_list_kernel<false>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, s);
+        }
+      } else {
+        if (nscan > 0) {
+          if (trace)
+            hipLaunchKernelGGL(scene_cast_kernel<true>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, a);
+          else
+            hipLaunchKernelGGL(scene_cast_kernel<false>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, a);
+        }
+        if (nbt > 0) {
+          SceneBinCastArgs b;
+          b.c = a; b.c.tiles = w->d_tiles + nscan * 2; b.off = w->d_binoff; b.list = w->d_binlist;
+          if (trace)
+            hipLaunchKernelGGL(scene_bincast_kernel<true>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, b);
+          else
+            hipLaunchKernelGGL(scene_bincast_kernel<false>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, b);
+        }
       }
     }
     HIP_TRY(h, hipGetLastError());
@@ -804,6 +1126,8 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
     std::vector<double> t(nt); std::vector<int> tri(nt);
     std::vector<long long> boff(nbt + 1, 0);
     if (trace->binned && nbt) HIP_TRY(h, hipMemcpyAsync(boff.data(), w->d_binoff, boff.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    std::vector<int> cells((nscan + nbt) * kBands, 0);
+    if (rows && !cells.empty()) HIP_TRY(h, hipMemcpyAsync(cells.data(), w->d_cells, cells.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (nt) {
       HIP_TRY(h, hipMemcpyAsync(t.data(), w->d_t, nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(h, hipMemcpyAsync(tri.data(), w->d_tri, nt * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -821,6 +1145,13 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
     if (trace->binned) {
       for (int k = 0; k < kMaxTiles; ++k) trace->tile_counts[k] = (size_t)k < nbt ? (int32_t)(boff[k + 1] - boff[k]) : 0;
       *trace->entries = bin_entries;
+    }
+    if (rows) {
+      *trace->cells = 0;
+      for (size_t k = 0; k < (size_t)kMaxTiles * kBands; ++k) {
+        trace->cell_counts[k] = k < cells.size() ? cells[k] : 0;
+        *trace->cells += trace->cell_counts[k];
+      }
     }
     return 0;
   }
@@ -848,7 +1179,7 @@ extern "C" void alignnet_scene_free(alignnet_handle* h)
   SceneWS* w = sws(h);
   if (h->stream) hipStreamSynchronize(h->stream);
   void* const ptrs[] = {w->d_verts, w->d_faces, w->d_dir, w->d_clouds, w->d_win, w->d_rowcount, w->d_rowoff, w->d_tiles, w->d_t, w->d_tri, w->d_offsets,
-                        w->d_pts[0], w->d_pts[1], w->d_bincnt, w->d_binoff, w->d_binlist};
+                        w->d_pts[0], w->d_pts[1], w->d_bincnt, w->d_binoff, w->d_binlist, w->d_cells};
   for (void* p : ptrs) if (p) hipFree(p);
   delete w;
   h->scene_ws = nullptr;
@@ -983,5 +1314,22 @@ extern "C" int alignnet_debug_scene_cast_binned(alignnet_handle* h, int32_t mesh
   if (lds_triangles < 0 || lds_triangles > kLdsTriangles)
     return fail(h, name + ": lds_triangles must be in [0, " + std::to_string(kLdsTriangles) + "] (0 = as shipped)");
   const SceneTrace tr = {lds_triangles, t, triangle, window, lds_triangles_used, true, tile_counts, entries};
+  return run_scene(h, name.c_str(), &mesh, &scale, pose, nullptr, 1, 0, 0.0, 0.0, &tr);
+}
+
+extern "C" int alignnet_debug_scene_cast_rows(alignnet_handle* h, int32_t mesh, double scale, const double* pose, int32_t lds_triangles, int32_t binned,
+                                              int32_t* window, double* t, int32_t* triangle, int32_t* lds_triangles_used, int32_t* cell_counts,
+                                              int64_t* cells)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_debug_scene_cast_rows");
+  if (!h->scene_ws || sws(h)->M < 0) return fail(h, name + ": no meshes uploaded");
+  if (!pose || !t || !triangle || !window || !lds_triangles_used || !cell_counts || !cells) return fail(h, name + ": null argument");
+  if (binned != 0 && binned != 1) return fail(h, name + ": binned must be 0 or 1");
+  if (lds_triangles < 0 || lds_triangles > kLdsTriangles)
+    return fail(h, name + ": lds_triangles must be in [0, " + std::to_string(kLdsTriangles) + "] (0 = as shipped)");
+  std::vector<int32_t> tile_counts(kMaxTiles);
+  int64_t entries = 0;
+  const SceneTrace tr = {lds_triangles, t, triangle, window, lds_triangles_used, binned != 0, tile_counts.data(), &entries, true, cell_counts, cells};
   return run_scene(h, name.c_str(), &mesh, &scale, pose, nullptr, 1, 0, 0.0, 0.0, &tr);
 }

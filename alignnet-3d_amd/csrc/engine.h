@@ -37,9 +37,9 @@ struct Stack { int first, n; };   // range of layers
 // Kernels whose launches are bracketed with HIP events on the handle's stream while profiling is enabled
 // (alignnet_profile_enable; read back by name through alignnet_profile_read_kernel -- bench.py's roofline legs).
 enum ProfKernel { PK_BACKBONE = 0, PK_KNN, PK_TRAIN_PHASE2, PK_TRAIN_PHASE3, PK_TRAIN_GRAM, PK_TRAIN_B2, PK_TRAIN_B1, PK_DG_FWD, PK_DG_BWD_EDGE,
-                  PK_ALLREDUCE, PK_OPTIMIZER, PK_SCENE_WINDOW, PK_SCENE_CAST, PK_SCENE_COMPACT, PK_ICP_GRID_BUILD, PK_ICP_GRID, PK_SCENE_BIN, PK_ICP_PLANE_NORMALS, PK_ICP_PLANE, PK_COUNT };
+                  PK_ALLREDUCE, PK_OPTIMIZER, PK_SCENE_WINDOW, PK_SCENE_CAST, PK_SCENE_COMPACT, PK_ICP_GRID_BUILD, PK_ICP_GRID, PK_SCENE_BIN, PK_ICP_PLANE_NORMALS, PK_ICP_PLANE, PK_SCENE_BAND, PK_COUNT };
 static const char* const kProfKernelNames[PK_COUNT] = {"backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2",
-                                                       "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact", "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane"};
+                                                       "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact", "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band"};
 
 struct Workspace {
   int cap = 0;                     // pairs
@@ -167,6 +167,7 @@ struct alignnet_handle {
   size_t icp_plane_ws_budget = 0;  // "icp_plane_ws_budget": workspace of one chunk of point-to-plane pairs; 0 = the grid search's 1 GiB
   int icp_plane_chunks = 0;        // "icp_plane_chunks" (read-only): chunks the last point-to-plane call ran
   int scene_cast = 0;              // alignnet_set_option("scene_cast"): 0 = scan, 1 = binned, 2 = binned for meshes beyond one LDS chunk of the scan (alignnet_scene.hip)
+  int scene_rows = 0;              // alignnet_set_option("scene_rows"): 1 = both casts run their inner loop by elevation band (alignnet_scene.hip, stage 2c)
   int scene_binned_clouds = 0;     // clouds of the last alignnet_scene_generate that took the binned cast ("scene_binned_clouds"), and the
   long long scene_bin_entries = 0; // entries of their tile lists ("scene_bin_entries")
   void* scene_ws = nullptr;        // mesh library, work buffers and the last result of the scene generator (alignnet_scene.hip)

@@ -536,7 +536,12 @@ int alignnet_debug_fgr_stages(alignnet_handle* h, const float* points1, int64_t 
  * alignnet_debug_scene_cast_binned (test hook, outside the stable surface): the same read-back through the BINNED cast
  *   (alignnet_set_option "scene_cast"), whatever the option says; the same arguments and lds_triangles range, and
  *   tile_counts [563] the length of the triangle list of every 8-column tile of the window (0 beyond the window's
- *   tiles), entries [1] their sum. */
+ *   tiles), entries [1] their sum.
+ * alignnet_debug_scene_cast_rows (test hook, outside the stable surface): the same read-back with the inner loop BY
+ *   ELEVATION BAND (alignnet_set_option "scene_rows"), whatever the options say: binned = 0 the scan's staging, 1 the
+ *   tile lists'; window, t, triangle and lds_triangles_used as above; cell_counts [563][8] the staged triangles per
+ *   (8-column tile of the window, band of 8 rows) whose band bit was set (0 beyond the window's tiles), cells [1] their
+ *   sum. */
 int alignnet_scene_set_sensor(alignnet_handle* h, const double* dir_x, const double* dir_y, const double* dir_z);
 int alignnet_scene_upload_meshes(alignnet_handle* h, const double* vertices, const int32_t* faces, const int64_t* offsets,
                                  const double* centroids, int32_t M);
@@ -550,6 +555,9 @@ int alignnet_debug_scene_cast(alignnet_handle* h, int32_t mesh, double scale, co
 int alignnet_debug_scene_cast_binned(alignnet_handle* h, int32_t mesh, double scale, const double* pose,
                                      int32_t lds_triangles, double* t, int32_t* triangle, int32_t* window,
                                      int32_t* lds_triangles_used, int32_t* tile_counts, int64_t* entries);
+int alignnet_debug_scene_cast_rows(alignnet_handle* h, int32_t mesh, double scale, const double* pose,
+                                   int32_t lds_triangles, int32_t binned, int32_t* window, double* t, int32_t* triangle,
+                                   int32_t* lds_triangles_used, int32_t* cell_counts, int64_t* cells);
 
 /* ---- run-time options with no counterpart in the reference's config surface --------
  * "train_matmul_bf16" (0/1, default 0): training only -- the two MFMA convs of every backbone (the hidden 1x1 conv
@@ -613,6 +621,13 @@ int alignnet_debug_scene_cast_binned(alignnet_handle* h, int32_t mesh, double sc
  *   size tried, 516 to 100,002 triangles (profiles/scene_cast_rate.json): 1 and 2 are exact alternatives, not accelerations, today.
  *   "scene_binned_clouds" (read-only): how many clouds of the last alignnet_scene_generate took the binned cast;
  *   "scene_bin_entries" (read-only): the entries of their tile lists together.
+ * "scene_rows" (0/1, default 0): how both casts of "scene_cast" run their inner loop.  0 = every staged triangle against all 64 rows x 8
+ *   columns of the tile (the kernels as they were before the key existed).  1 = by elevation band: a staged triangle carries a mask of the
+ *   eight bands of 8 rows it can reach (conservative: csrc/alignnet_scene.hip, stage 2c) and is intersected only with those -- exact:
+ *   offsets and points are bit for bit those of 0.  Orthogonal to "scene_cast".  Other values are an error and leave the value as it was.
+ *   Measured on an MI355X (profiles/scene_rows_rate.json; README, "cast by elevation band") 1 is ahead of 0 at every mesh size tried, under
+ *   both stagings: 1.57 x for a 516-triangle mesh with "scene_cast" 0, and 2.1 x - 2.7 x from 5,001 to 100,002 triangles with "scene_cast" 1,
+ *   which is the faster staging there once the bands have cut the intersections.  Off by default.
  *   "icp_grid_ws_bytes" (read-only): the workspace the last call with grid pairs carved (per chunk of pairs, at most 1 GiB unless one pair
  *   needs more; freed with the handle).
  * "icp_plane_ws_budget" (bytes, default 0 = 1 GiB): the workspace one chunk of pairs of alignnet_icp_plane_register* may take (two grids,
@@ -663,7 +678,7 @@ int alignnet_profile_read(alignnet_handle* h, double* backbone_ms, int64_t* back
  * on the stream it is launched on while profiling is enabled.  name: "backbone" (eval-mode fused backbone), "knn",
  * "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge",
  * "allreduce" (what the compute stream waits for), "optimizer", and the stages of alignnet_scene_generate: "scene_window" (azimuth windows),
- * "scene_cast", "scene_compact" (counts, scan, scatter + noise), and of the ICP grid search: "icp_grid_build", "icp_grid" (the iterations), and of
+ * "scene_cast" ("scene_band" instead when "scene_rows" is 1), "scene_compact" (counts, scan, scatter + noise), and of the ICP grid search: "icp_grid_build", "icp_grid" (the iterations), and of
  * point-to-plane ICP: "icp_plane_normals" (the ordering of the second grid's buckets + the normals), "icp_plane" (the iterations; its two grid builds
  * count under "icp_grid_build"). */
 int alignnet_profile_read_kernel(alignnet_handle* h, const char* name, double* ms, int64_t* launches);
