@@ -164,6 +164,11 @@ SYMBOLS = {
                                           C.c_double, C.c_double, C.POINTER(C.c_int64)]),
     "alignnet_scene_read": (C.c_int, [H, FP, FP]),
     "alignnet_scene_install_dataset": (C.c_int, [H, FP]),
+    "alignnet_tracklet_upload_scans": (C.c_int, [H, FP, C.c_int32, C.POINTER(C.c_int64), C.c_int32]),
+    "alignnet_tracklet_free_scans": (C.c_int, [H]),
+    "alignnet_tracklet_extract": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_double), FP, C.c_int32, C.POINTER(C.c_int64)]),
+    "alignnet_tracklet_read": (C.c_int, [H, FP, FP]),
+    "alignnet_tracklet_install_dataset": (C.c_int, [H, FP]),
     "alignnet_debug_scene_cast": (C.c_int, [H, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "alignnet_debug_scene_cast_binned": (C.c_int, [H, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32),

@@ -744,6 +744,53 @@ class Engine:
         assert hasattr(self, "_scene_offsets") and lab.shape[0] == self._scene_offsets.shape[0] - 1, "one label row per generated scene"
         self._check(self._lib.alignnet_scene_install_dataset(self._h, _fp(lab)))
 
+    # ---- KITTI tracklet extraction (csrc/alignnet_crop.hip; alignnet3d/tracklets.py builds the arguments) ----
+    def tracklet_upload_scans(self, scans):
+        """scans: list of float32 arrays [n, 3] or [n, 4] (a KITTI .bin is [n, 4]: x y z reflectance), all of one width, or a tuple (points
+        [sum n, stride], offsets [F + 1]) that is concatenated already.  Copied to the device once; frame f of tracklet_extract is scans[f]."""
+        if isinstance(scans, tuple):
+            pts, off = np.ascontiguousarray(scans[0], np.float32), np.ascontiguousarray(scans[1], np.int64).ravel()
+            stride = pts.shape[1] if pts.ndim == 2 else 0
+        else:
+            arrs = [np.asarray(s, np.float32) for s in scans]
+            widths = {a.shape[1] if a.ndim == 2 else 0 for a in arrs}
+            stride = widths.pop() if len(widths) == 1 else (3 if not arrs else 0)
+            off = np.zeros(len(arrs) + 1, np.int64)
+            off[1:] = np.cumsum([len(a) for a in arrs])
+            pts = np.ascontiguousarray(np.concatenate(arrs, 0)) if arrs and stride else np.zeros((0, max(stride, 1)), np.float32)
+        self._check(self._lib.alignnet_tracklet_upload_scans(self._h, _fp(pts), int(stride), off.ctypes.data_as(C.POINTER(C.c_int64)), off.size - 1))
+
+    def tracklet_free_scans(self):
+        self._check(self._lib.alignnet_tracklet_free_scans(self._h))
+
+    def tracklet_extract(self, frames, boxes, dz=None):
+        """frames [B, 2] indices into the uploaded scans, boxes [B, 2, 7] float64 = (x, y, z, h, w, l, ry) of the KITTI label (camera frame),
+        dz [B, 2] float32 subtracted from z (None = 0).  The crops stay on the device (tracklet_read / tracklet_install_dataset); returns the
+        offsets table [B + 1, 2]."""
+        frames = np.ascontiguousarray(frames, np.int32).reshape(-1, 2)
+        B = frames.shape[0]
+        boxes = np.ascontiguousarray(boxes, np.float64).reshape(B, 2, 7)
+        dz = np.zeros((B, 2), np.float32) if dz is None else np.ascontiguousarray(dz, np.float32).reshape(B, 2)
+        off = np.zeros((B + 1, 2), np.int64)
+        self._check(self._lib.alignnet_tracklet_extract(self._h, frames.ctypes.data_as(C.POINTER(C.c_int32)), boxes.ctypes.data_as(C.POINTER(C.c_double)),
+                                                        _fp(dz), B, off.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._tracklet_offsets = off
+        return off
+
+    def tracklet_read(self, offsets=None):
+        """(points1, points2) float32 [n, 3] blobs of the last tracklet_extract (offsets: its return value, None = remembered)."""
+        off = self._tracklet_offsets if offsets is None and hasattr(self, "_tracklet_offsets") else offsets
+        n1, n2 = (0, 0) if off is None else (int(off[-1, 0]), int(off[-1, 1]))
+        p1, p2 = np.empty((n1, 3), np.float32), np.empty((n2, 3), np.float32)
+        self._check(self._lib.alignnet_tracklet_read(self._h, _fp(p1), _fp(p2)))
+        return p1, p2
+
+    def tracklet_install_dataset(self, labels):
+        """The last tracklet_extract becomes the HBM-resident dataset (device to device); labels [B, 12] as for upload_dataset."""
+        lab = np.ascontiguousarray(labels, np.float32).reshape(-1, 12)
+        assert hasattr(self, "_tracklet_offsets") and lab.shape[0] == self._tracklet_offsets.shape[0] - 1, "one label row per extracted pair"
+        self._check(self._lib.alignnet_tracklet_install_dataset(self._h, _fp(lab)))
+
     def debug_scene_cast(self, mesh, scale, pose, lds_triangles=0, binned=False, rows=False):
         """Test hook: ONE cloud by the shipped cast kernel, no noise.  Returns dict(t [64, 4500] float64 (inf = miss), triangle [64, 4500] (-1), window =
         (first column, columns), lds_triangles as used).  lds_triangles in 1 .. 512 forces several LDS chunks on small meshes.  binned=False: the scan;
@@ -961,7 +1008,8 @@ class Engine:
 
     PROFILED_KERNELS = ("backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1",
                         "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact",
-                        "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band")
+                        "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band",
+                        "tracklet_test", "tracklet_compact")
 
     def profile_kernels(self):
         """{kernel: (ms, launches)} accumulated since the last profile_read(reset=True); call BEFORE that reset."""

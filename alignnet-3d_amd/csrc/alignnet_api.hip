@@ -197,6 +197,7 @@ extern "C" int alignnet_dataset_free(alignnet_handle* h);
 extern "C" void alignnet_comm_free(alignnet_handle* h);
 extern "C" void alignnet_globalreg_free(alignnet_handle* h);
 extern "C" void alignnet_scene_free(alignnet_handle* h);
+extern "C" void alignnet_tracklet_free(alignnet_handle* h);
 extern "C" void alignnet_icp_free(alignnet_handle* h);
 
 namespace { void pipe_free(alignnet_handle* h); hipStream_t pipe_stream(alignnet_handle* h, int which); }   // pipelined host path, defined with alignnet_forward_submit below
@@ -211,6 +212,7 @@ extern "C" void alignnet_destroy(alignnet_handle* h)
   alignnet_dataset_free(h);
   alignnet_globalreg_free(h);
   alignnet_scene_free(h);
+  alignnet_tracklet_free(h);
   alignnet_icp_free(h);
   alignnet_register_free(h);
   pipe_free(h);
@@ -1039,6 +1041,8 @@ extern "C" int alignnet_get_option(alignnet_handle* h, const char* key, int64_t*
   if (k == "scene_rows") { *value = h->scene_rows; return 0; }
   if (k == "scene_binned_clouds") { *value = h->scene_binned_clouds; return 0; }
   if (k == "scene_bin_entries") { *value = h->scene_bin_entries; return 0; }
+  if (k == "tracklet_chunk") { *value = alignnet::kTrackletChunk; return 0; }
+  if (k == "tracklet_jobs_per_pass") { *value = alignnet::kTrackletJobsPerPass; return 0; }
   if (k == "ab_mask") { *value = h->ab; return 0; }
   for (const auto& ak : kAbKeys) if (k == ak.key) { *value = (h->ab & ak.bit) ? 1 : 0; return 0; }
   if (k == "comm_buckets") { *value = h->comm_buckets; return 0; }

@@ -1,0 +1,461 @@
+// KITTI tracklet extraction (the KITTITracklets* datasets of tp_utils/pointcloud.py:769-778, 840-869, 918-940, 1000-1033), gfx950 only.
+//
+// Replaces extract_pointcloud -> compute_box_3d -> extract_pc_in_box3d (scipy's Delaunay.find_simplex on the box's eight corners): the
+// points of a LiDAR scan that lie in a tracked 3D box are kept in scan order.  The semantics are DEFINED by tests/tracklet_ref.py (fp64, NumPy):
+//  - a scan point p = (x, y, z) float32 in the Velodyne frame has camera-frame coordinates q = (-y, -z, x) (the reference's R = R1 R2, a signed
+//    permutation: exact);
+//  - a box b = (bx, by, bz, h, w, l, ry) (the label's location, dimensions, rotation_y); d = q - (bx, by, bz) in fp64, c = cos ry, s = sin ry evaluated ONCE on
+//    the host in fp64 and handed over, lx = c dx - s dz, ly = dy, lz = s dx + c dz, every product and difference rounded as written (no fused
+//    multiply-add: bit for bit the restatement's numbers).  Inside iff |lx| <= l / 2, -h <= ly <= 0, |lz| <= w / 2: the box is CLOSED;
+//  - a point with a non-finite coordinate is in no box;
+//  - the crop keeps the points in scan order with their float32 bits unchanged (the reference's pc[inds]); dz is subtracted from z in ONE
+//    float32 subtraction (pc2[:, 2] -= z_difference on a float32 array under the NumPy of the reference's time).  No colour columns.
+//
+// Stages of one alignnet_tracklet_extract (B pairs = 2 B crop jobs against the uploaded scans); the host groups the jobs by frame:
+//  1. tracklet_test_kernel, one workgroup of four waves per (frame, chunk of kTrackletChunk points): the chunk's points are loaded once (stride 4:
+//     one 16-byte load per point) and held in registers, four per thread, a wave holding 64 consecutive points per quarter.  The frame's jobs go
+//     through LDS in passes of kTrackletJobsPerPass.  Per job: a float32 pre-test, then (only where some lane of the wave passed it) the fp64
+//     test; ballot + popcount gives the wave's count, the four waves' counts go to counts[job][chunk].
+//     The pre-test is CONSERVATIVE: with bf = float(b) and df = q (-) bf in float32, |df| <= (|d| + 2^-24 |b|)(1 + 2^-24); an inside point has
+//     |dx|, |dz| <= hypot(l / 2, w / 2) and |dy| <= h, so a point is rejected only when |df| exceeds that bound enlarged by (|b| 6e-8) and a factor
+//     1 + 1e-6, rounded up to the next float.  A NaN compares false and is never rejected here (the fp64 test refuses it).
+//  2. tracklet_jobscan_kernel, one workgroup per job: the exclusive scan of the job's counts in chunk order -> the position of every (job, chunk)
+//     inside the job's crop, and the job's total; tracklet_scan_kernel, one workgroup: the exclusive scan of the totals in pair order per cloud
+//     index -> the offsets table [B + 1][2].  It goes to the host (the one small copy of a call), which sizes the blobs from its last row.
+//  3. tracklet_scatter_kernel, the grid of stage 1: a workgroup reads its chunk's counts of 64 jobs at once (a lane each) and skips every job whose
+//     count is zero (typically under 2 % of a frame's points are in any box: most chunks load no point at all), repeats the test of stage 1
+//     for the others (the same function on the same numbers) and writes the members at offsets[pair][cloud] + position + ballot prefix.
+//     Counts, a scan, a scatter: no atomics that could reorder points.
+// The result is built in a second pair of blobs and swapped in on success: an error leaves the previous result and the uploaded scans as they were.
+#include "engine.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+namespace {
+
+int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1; }
+
+#define HIP_TRY(h, expr)                                                                         \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess) return fail(h, std::string(#expr) + ": " + hipGetErrorString(e_));     \
+  } while (0)
+
+constexpr int kChunk = alignnet::kTrackletChunk, kJobsPerPass = alignnet::kTrackletJobsPerPass;
+constexpr int kThreads = 256, kQuarters = kChunk / kThreads;
+static_assert(kChunk % kThreads == 0 && kQuarters == 4, "a thread holds four points of a chunk");
+
+struct CropJob {
+  double bx, by, bz, c, s, hl, h, hw;   // box centre (camera frame), cos / sin of ry, l / 2, h, w / 2
+  float fx, fy, fz, txz, ty, dz;        // float32 pre-test: centre, bounds on |dx|, |dz| and on |dy|; dz: subtracted from z
+  long long cbase;                      // the job's first entry in the counts / positions tables
+  int which, pair;                      // cloud index 0 / 1; the pair: the crop starts at offsets[pair][which]
+};
+static_assert(sizeof(CropJob) == 104, "LDS budget");
+
+struct CropFrame { long long pt0; int n, job0, njobs, pad; };   // first point of the frame in the uploaded scans, its points, its jobs in the sorted job list
+
+struct Pt { float x, y, z; };
+
+__device__ __forceinline__ bool crop_pre(const CropJob& j, const Pt& p)
+{
+  // q = (-y, -z, x); false = certainly outside (NaN: never rejected here)
+  return !(fabsf(-p.y - j.fx) > j.txz) && !(fabsf(-p.z - j.fy) > j.ty) && !(fabsf(p.x - j.fz) > j.txz);
+}
+
+__device__ __forceinline__ bool crop_inside(const CropJob& j, const Pt& p)
+{
+#pragma clang fp contract(off)
+  if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) return false;
+  const double dx = (double)(-p.y) - j.bx, dy = (double)(-p.z) - j.by, dz = (double)p.x - j.bz;
+  const double lx = j.c * dx - j.s * dz, lz = j.s * dx + j.c * dz;
+  return fabs(lx) <= j.hl && -j.h <= dy && dy <= 0.0 && fabs(lz) <= j.hw;
+}
+
+// the membership of the wave's 64 points of one quarter: the pre-test first, the fp64 test only where some lane passed it
+__device__ __forceinline__ unsigned long long crop_ballot(const CropJob& j, const Pt& p, bool valid)
+{
+  const bool pre = valid && crop_pre(j, p);
+  if (__ballot(pre) == 0ull) return 0ull;
+  return __ballot(pre && crop_inside(j, p));
+}
+
+template <int STRIDE>
+__device__ __forceinline__ void load_points(const float* __restrict__ scans, const CropFrame& f, int chunk, Pt* p, bool* valid)
+{
+#pragma unroll
+  for (int i = 0; i < kQuarters; ++i) {
+    const int k = chunk * kChunk + i * kThreads + (int)threadIdx.x;   // a wave holds 64 consecutive points of quarter i
+    valid[i] = k < f.n;
+    p[i].x = p[i].y = p[i].z = 0.f;
+    if (valid[i]) {
+      const long long e = f.pt0 + k;
+      if (STRIDE == 4) {
+        const float4 v = *reinterpret_cast<const float4*>(scans + e * 4);   // the scans' base is an allocation's: 16-byte aligned
+        p[i].x = v.x; p[i].y = v.y; p[i].z = v.z;
+      } else {
+        p[i].x = scans[e * 3]; p[i].y = scans[e * 3 + 1]; p[i].z = scans[e * 3 + 2];
+      }
+    }
+  }
+}
+
+// grid: the (frame, chunk) items
+template <int STRIDE>
+__global__ __launch_bounds__(kThreads) void tracklet_test_kernel(const float* __restrict__ scans, const CropFrame* __restrict__ frames,
+                                                                 const int2* __restrict__ items, const CropJob* __restrict__ jobs,
+                                                                 int* __restrict__ counts)
+{
+  __shared__ CropJob sj[kJobsPerPass];
+  __shared__ int wcnt[kJobsPerPass][4];
+  const int2 it = items[blockIdx.x];
+  const CropFrame f = frames[it.x];
+  const int chunk = it.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  Pt p[kQuarters]; bool valid[kQuarters];
+  load_points<STRIDE>(scans, f, chunk, p, valid);
+  for (int j0 = 0; j0 < f.njobs; j0 += kJobsPerPass) {
+    const int nj = min(kJobsPerPass, f.njobs - j0);
+    {
+      // stage the pass's jobs: 26 dwords each
+      const int* src = reinterpret_cast<const int*>(jobs + f.job0 + j0);
+      int* dst = reinterpret_cast<int*>(sj);
+      for (int e = tid; e < nj * (int)(sizeof(CropJob) / 4); e += kThreads) dst[e] = src[e];
+    }
+    __syncthreads();
+    for (int j = 0; j < nj; ++j) {
+      int n = 0;
+#pragma unroll
+      for (int i = 0; i < kQuarters; ++i) n += __popcll(crop_ballot(sj[j], p[i], valid[i]));
+      if (lane == 0) wcnt[j][wave] = n;
+    }
+    __syncthreads();
+    for (int j = tid; j < nj; j += kThreads) counts[sj[j].cbase + chunk] = wcnt[j][0] + wcnt[j][1] + wcnt[j][2] + wcnt[j][3];
+    __syncthreads();
+  }
+}
+
+struct JobSpan { long long cbase; int chunks, pad; };   // a job's entries in the counts / positions tables, in (pair, cloud) order
+
+// grid: the 2 B jobs in (pair, cloud) order.  pos[entry] = members of the job in earlier chunks; total[job]
+__global__ __launch_bounds__(kThreads) void tracklet_jobscan_kernel(const int* __restrict__ counts, const JobSpan* __restrict__ spans, int* __restrict__ pos,
+                                                                    int* __restrict__ total)
+{
+  __shared__ int wsum[4];
+  const JobSpan sp = spans[blockIdx.x];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int run = 0;   // members in the chunks before this tile of 256 (the same in every thread)
+  for (int e0 = 0; e0 < sp.chunks; e0 += kThreads) {
+    const int e = e0 + tid;
+    const int v = e < sp.chunks ? counts[sp.cbase + e] : 0;
+    int inc = v;   // inclusive scan inside the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int before = run, all = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { const int n = wsum[w]; if (w < wave) before += n; all += n; }
+    if (e < sp.chunks) pos[sp.cbase + e] = before + inc - v;
+    run += all;
+    __syncthreads();
+  }
+  if (tid == 0) total[blockIdx.x] = run;
+}
+
+// one workgroup of 1024: per cloud index w, the exclusive scan of total[b][w] over the pairs -> offsets [B + 1][2]
+__global__ __launch_bounds__(1024) void tracklet_scan_kernel(const int* __restrict__ total, long long* __restrict__ offsets, int B)
+{
+  __shared__ long long part[1024];
+  const int tid = threadIdx.x;
+  const long long n = B, per = (n + 1023) / 1024;
+  for (int w = 0; w < 2; ++w) {
+    const long long lo = min(n, tid * per), hi = min(n, lo + per);
+    long long s = 0;
+    for (long long b = lo; b < hi; ++b) s += total[b * 2 + w];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+      long long run = 0;
+      for (int i = 0; i < 1024; ++i) { const long long v = part[i]; part[i] = run; run += v; }
+      offsets[n * 2 + w] = run;
+    }
+    __syncthreads();
+    long long run = part[tid];
+    for (long long b = lo; b < hi; ++b) { offsets[b * 2 + w] = run; run += total[b * 2 + w]; }
+    __syncthreads();
+  }
+}
+
+// grid: the (frame, chunk) items
+template <int STRIDE>
+__global__ __launch_bounds__(kThreads) void tracklet_scatter_kernel(const float* __restrict__ scans, const CropFrame* __restrict__ frames,
+                                                                    const int2* __restrict__ items, const CropJob* __restrict__ jobs,
+                                                                    const int* __restrict__ counts, const int* __restrict__ pos,
+                                                                    const long long* __restrict__ offsets, float* __restrict__ out0, float* __restrict__ out1)
+{
+  __shared__ int wcnt[kQuarters][4];
+  const int2 it = items[blockIdx.x];
+  const CropFrame f = frames[it.x];
+  const int chunk = it.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  Pt p[kQuarters]; bool valid[kQuarters];
+  bool loaded = false;
+  for (int j0 = 0; j0 < f.njobs; j0 += 64) {
+    // the counts of 64 jobs at once, a lane each: every wave reads the same numbers, so `hit` is the same in the whole workgroup
+    const int mine_job = j0 + lane;
+    const int cnt = mine_job < f.njobs ? counts[jobs[f.job0 + mine_job].cbase + chunk] : 0;
+    unsigned long long hit = __ballot(cnt != 0);
+    while (hit) {
+      const int jj = j0 + __ffsll((long long)hit) - 1;
+      hit &= hit - 1;
+      const CropJob& gj = jobs[f.job0 + jj];
+      const long long slot = gj.cbase + chunk;
+      if (!loaded) { load_points<STRIDE>(scans, f, chunk, p, valid); loaded = true; }
+      const CropJob j = gj;
+      unsigned long long m[kQuarters];
+#pragma unroll
+      for (int i = 0; i < kQuarters; ++i) {
+        m[i] = crop_ballot(j, p[i], valid[i]);
+        if (lane == 0) wcnt[i][wave] = __popcll(m[i]);
+      }
+      __syncthreads();
+      float* out = (j.which ? out1 : out0) + (offsets[(long long)j.pair * 2 + j.which] + pos[slot]) * 3;
+      int before = 0;   // members of this (job, chunk) ahead of the wave's 64 points of quarter i: scan order is (quarter, wave, lane)
+#pragma unroll
+      for (int i = 0; i < kQuarters; ++i) {
+        int mine = before;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const int n = wcnt[i][w]; if (w < wave) mine += n; before += n; }
+        if ((m[i] >> lane) & 1ull) {
+          float* o = out + (size_t)(mine + __popcll(m[i] & ((1ull << lane) - 1ull))) * 3;
+          o[0] = p[i].x; o[1] = p[i].y; o[2] = p[i].z - j.dz;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// ---- host state ------------------------------------------------------------------------------------------------------------------------------
+struct TrackletWS {
+  // uploaded scans (alignnet_tracklet_upload_scans)
+  int F = -1, stride = 0;                   // F = -1: nothing uploaded
+  std::vector<long long> foff;              // [F + 1] first point of every frame
+  float* d_scans = nullptr;
+  // work buffers, grown on demand
+  CropJob* d_jobs = nullptr; size_t cap_jobs = 0;
+  CropFrame* d_frames = nullptr; size_t cap_frames = 0;
+  int2* d_items = nullptr; size_t cap_items = 0;
+  int* d_counts = nullptr; int* d_pos = nullptr; size_t cap_counts = 0, cap_pos = 0;
+  JobSpan* d_spans = nullptr; int* d_total = nullptr; size_t cap_spans = 0, cap_total = 0;
+  long long* d_offsets = nullptr; size_t cap_off = 0;
+  // the last result (alignnet_tracklet_extract) and the blobs the next one is built in
+  int B = -1;
+  std::vector<long long> offsets;           // [B + 1][2]
+  float* d_pts[2] = {nullptr, nullptr}; size_t cap_pts[2] = {0, 0};
+  float* d_next[2] = {nullptr, nullptr}; size_t cap_next[2] = {0, 0};
+};
+
+TrackletWS* tws(alignnet_handle* h) { return static_cast<TrackletWS*>(h->tracklet_ws); }
+
+template <typename T>
+int grow(alignnet_handle* h, T** p, size_t* cap, size_t need)
+{
+  if (need <= *cap && *p) return 0;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (*p) hipFree(*p);
+  *p = nullptr; *cap = 0;
+  HIP_TRY(h, hipMalloc(p, std::max<size_t>(need, 1) * sizeof(T)));
+  *cap = std::max<size_t>(need, 1);
+  return 0;
+}
+
+// the float32 bound of the pre-test: (r + |b| 6e-8)(1 + 1e-6) rounded up (the header of this file); not finite -> nothing is rejected
+float pre_bound(double r, double b)
+{
+  const double t = (r + std::fabs(b) * 6e-8) * (1.0 + 1e-6);
+  if (!(t < 3e38)) return INFINITY;
+  return std::nextafter((float)t, INFINITY);
+}
+
+}  // namespace
+
+extern "C" int alignnet_tracklet_free_scans(alignnet_handle* h)
+{
+  if (!h) return 1;
+  if (!h->tracklet_ws) return 0;
+  TrackletWS* w = tws(h);
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (w->d_scans) hipFree(w->d_scans);
+  w->d_scans = nullptr; w->F = -1; w->stride = 0; w->foff.clear();
+  return 0;
+}
+
+extern "C" void alignnet_tracklet_free(alignnet_handle* h)
+{
+  if (!h || !h->tracklet_ws) return;
+  TrackletWS* w = tws(h);
+  if (h->stream) hipStreamSynchronize(h->stream);
+  void* const ptrs[] = {w->d_scans, w->d_jobs, w->d_frames, w->d_items, w->d_counts, w->d_pos, w->d_spans, w->d_total, w->d_offsets,
+                        w->d_pts[0], w->d_pts[1], w->d_next[0], w->d_next[1]};
+  for (void* p : ptrs) if (p) hipFree(p);
+  delete w;
+  h->tracklet_ws = nullptr;
+}
+
+extern "C" int alignnet_tracklet_upload_scans(alignnet_handle* h, const float* points, int32_t stride, const int64_t* offsets, int32_t F)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_tracklet_upload_scans");
+  if (stride != 3 && stride != 4) return fail(h, name + ": stride must be 3 or 4 floats per point");
+  if (F < 0 || !offsets) return fail(h, name + ": F < 0 or null offsets");
+  if (offsets[0] != 0) return fail(h, name + ": offsets must start at 0");
+  for (int f = 0; f < F; ++f) {
+    if (offsets[f + 1] < offsets[f]) return fail(h, name + ": offsets must be non-decreasing");
+    if (offsets[f + 1] - offsets[f] > 0x7fffffff - kChunk) return fail(h, name + ": frame " + std::to_string(f) + " too large");
+  }
+  const size_t n = (size_t)offsets[F];
+  if (n && !points) return fail(h, name + ": null points");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  float* d = nullptr;
+  HIP_TRY(h, hipMalloc(&d, std::max<size_t>(n, 1) * stride * sizeof(float)));
+  if (n) {
+    const hipError_t e = hipMemcpy(d, points, n * stride * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { hipFree(d); return fail(h, name + ": hipMemcpy: " + hipGetErrorString(e)); }
+  }
+  if (!h->tracklet_ws) h->tracklet_ws = new TrackletWS();
+  if (alignnet_tracklet_free_scans(h)) { hipFree(d); return 1; }
+  TrackletWS* w = tws(h);
+  w->d_scans = d; w->F = F; w->stride = stride;
+  w->foff.assign(offsets, offsets + (size_t)F + 1);
+  return 0;
+}
+
+extern "C" int alignnet_tracklet_extract(alignnet_handle* h, const int32_t* frames, const double* boxes, const float* dz, int32_t B, int64_t* offsets)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_tracklet_extract");
+  if (!h->tracklet_ws || tws(h)->F < 0) return fail(h, name + ": no scans uploaded");
+  if (B < 0 || B > (1 << 24)) return fail(h, name + ": B out of range");
+  if (B > 0 && (!frames || !boxes || !dz)) return fail(h, name + ": null argument");
+  TrackletWS* w = tws(h);
+  const int J = 2 * B;
+  for (int j = 0; j < J; ++j) {
+    const std::string where = " (pair " + std::to_string(j / 2) + ", cloud " + std::to_string(j % 2 + 1) + ")";
+    if (frames[j] < 0 || frames[j] >= w->F) return fail(h, name + ": frame " + std::to_string(frames[j]) + " out of range" + where);
+    for (int k = 0; k < 7; ++k) if (!std::isfinite(boxes[(size_t)j * 7 + k])) return fail(h, name + ": non-finite box value" + where);
+    for (int k = 3; k < 6; ++k) if (boxes[(size_t)j * 7 + k] < 0.0) return fail(h, name + ": negative box extent" + where);
+    if (!std::isfinite(dz[j])) return fail(h, name + ": non-finite dz" + where);
+  }
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  // the tables: entries of the counts table in (pair, cloud, chunk) order; jobs sorted by frame
+  std::vector<JobSpan> spans(J);
+  long long entries_ll = 0;
+  for (int j = 0; j < J; ++j) {
+    const long long ch = (w->foff[frames[j] + 1] - w->foff[frames[j]] + kChunk - 1) / kChunk;
+    spans[j].cbase = entries_ll; spans[j].chunks = (int)ch; spans[j].pad = 0;
+    entries_ll += ch;
+  }
+  const size_t entries = (size_t)entries_ll;
+  std::vector<int> order(J);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return frames[a] < frames[b]; });
+  std::vector<CropJob> jobs(J);
+  std::vector<CropFrame> groups;
+  std::vector<int2> items;
+  for (int i = 0; i < J; ++i) {
+    const int j = order[i];
+    const double* b = boxes + (size_t)j * 7;
+    CropJob& c = jobs[i];
+    c.bx = b[0]; c.by = b[1]; c.bz = b[2];
+    c.c = std::cos(b[6]); c.s = std::sin(b[6]);
+    c.h = b[3]; c.hw = b[4] * 0.5; c.hl = b[5] * 0.5;
+    const double rxz = std::hypot(c.hl, c.hw) * (1.0 + 1e-12);
+    c.fx = (float)b[0]; c.fy = (float)b[1]; c.fz = (float)b[2];
+    c.txz = pre_bound(rxz, std::max(std::fabs(b[0]), std::fabs(b[2])));
+    c.ty = pre_bound(c.h, b[1]);
+    c.dz = dz[j]; c.cbase = spans[j].cbase; c.which = j % 2; c.pair = j / 2;
+    if (groups.empty() || frames[j] != frames[order[i - 1]]) {
+      CropFrame g;
+      g.pt0 = w->foff[frames[j]]; g.n = (int)(w->foff[frames[j] + 1] - w->foff[frames[j]]); g.job0 = i; g.njobs = 0; g.pad = 0;
+      for (int ch = 0; ch < (g.n + kChunk - 1) / kChunk; ++ch) items.push_back(make_int2((int)groups.size(), ch));
+      groups.push_back(g);
+    }
+    ++groups.back().njobs;
+  }
+  if (items.size() > 0x7fffffffull) return fail(h, name + ": too many (frame, chunk) work items");
+  std::vector<long long> off((size_t)(B + 1) * 2, 0);
+  if (J > 0) {
+    if (grow(h, &w->d_jobs, &w->cap_jobs, jobs.size()) || grow(h, &w->d_frames, &w->cap_frames, groups.size()) ||
+        grow(h, &w->d_items, &w->cap_items, items.size()) || grow(h, &w->d_counts, &w->cap_counts, entries) ||
+        grow(h, &w->d_pos, &w->cap_pos, entries) || grow(h, &w->d_spans, &w->cap_spans, spans.size()) ||
+        grow(h, &w->d_total, &w->cap_total, spans.size()) ||
+        grow(h, &w->d_offsets, &w->cap_off, off.size()))
+      return 1;
+    HIP_TRY(h, hipMemcpyAsync(w->d_jobs, jobs.data(), jobs.size() * sizeof(CropJob), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(w->d_frames, groups.data(), groups.size() * sizeof(CropFrame), hipMemcpyHostToDevice, h->stream));
+    if (!items.empty()) HIP_TRY(h, hipMemcpyAsync(w->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(w->d_spans, spans.data(), spans.size() * sizeof(JobSpan), hipMemcpyHostToDevice, h->stream));
+    if (!items.empty()) {
+      alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_TEST);
+      if (w->stride == 4)
+        hipLaunchKernelGGL(tracklet_test_kernel<4>, dim3((unsigned)items.size()), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs, w->d_counts);
+      else
+        hipLaunchKernelGGL(tracklet_test_kernel<3>, dim3((unsigned)items.size()), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs, w->d_counts);
+    }
+    {
+      alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_COMPACT);
+      hipLaunchKernelGGL(tracklet_jobscan_kernel, dim3((unsigned)J), dim3(kThreads), 0, h->stream, w->d_counts, w->d_spans, w->d_pos, w->d_total);
+      hipLaunchKernelGGL(tracklet_scan_kernel, dim3(1), dim3(1024), 0, h->stream, w->d_total, w->d_offsets, B);
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(off.data(), w->d_offsets, off.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 2; ++k)
+      if (grow(h, &w->d_next[k], &w->cap_next[k], (size_t)off[(size_t)B * 2 + k] * 3)) return 1;
+    if (!items.empty() && off[(size_t)B * 2] + off[(size_t)B * 2 + 1] > 0) {
+      alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_COMPACT);
+      if (w->stride == 4)
+        hipLaunchKernelGGL(tracklet_scatter_kernel<4>, dim3((unsigned)items.size()), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs,
+                           w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
+      else
+        hipLaunchKernelGGL(tracklet_scatter_kernel<3>, dim3((unsigned)items.size()), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs,
+                           w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 2; ++k) { std::swap(w->d_pts[k], w->d_next[k]); std::swap(w->cap_pts[k], w->cap_next[k]); }
+  }
+  w->offsets.swap(off);
+  w->B = B;
+  if (offsets) for (size_t i = 0; i < w->offsets.size(); ++i) offsets[i] = w->offsets[i];
+  return 0;
+}
+
+extern "C" int alignnet_tracklet_read(alignnet_handle* h, float* points1, float* points2)
+{
+  if (!h) return 1;
+  if (!h->tracklet_ws || tws(h)->B < 0) return fail(h, "alignnet_tracklet_read: nothing extracted yet");
+  TrackletWS* w = tws(h);
+  float* const dst[2] = {points1, points2};
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  for (int k = 0; k < 2; ++k) {
+    const size_t n = (size_t)w->offsets[(size_t)w->B * 2 + k];
+    if (n && dst[k]) HIP_TRY(h, hipMemcpyAsync(dst[k], w->d_pts[k], n * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+extern "C" int alignnet_tracklet_install_dataset(alignnet_handle* h, const float* labels)
+{
+  if (!h) return 1;
+  if (!h->tracklet_ws || tws(h)->B < 0) return fail(h, "alignnet_tracklet_install_dataset: nothing extracted yet");
+  TrackletWS* w = tws(h);
+  if (w->B < 1 || !labels) return fail(h, "alignnet_tracklet_install_dataset: no pairs or null labels");
+  static_assert(sizeof(long long) == sizeof(int64_t), "offsets");
+  return alignnet_dataset_install(h, w->d_pts[0], w->d_pts[1], true, reinterpret_cast<const int64_t*>(w->offsets.data()), labels, w->B,
+                                  "alignnet_tracklet_install_dataset");
+}

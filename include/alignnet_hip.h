@@ -559,6 +559,42 @@ int alignnet_debug_scene_cast_rows(alignnet_handle* h, int32_t mesh, double scal
                                    int32_t lds_triangles, int32_t binned, int32_t* window, double* t, int32_t* triangle,
                                    int32_t* lds_triangles_used, int32_t* cell_counts, int64_t* cells);
 
+/* ---- KITTI tracklet extraction (the KITTITracklets* datasets, tp_utils/pointcloud.py:769-778, 840-869, 918-940, 1000-1033) ----
+ * The points of a LiDAR scan inside a tracked 3D box, in scan order: extract_pointcloud -> compute_box_3d -> in_hull
+ * (scipy's Delaunay.find_simplex on the eight corners) as one pass over points x boxes on the device.  The computation is
+ * DEFINED by tests/tracklet_ref.py (fp64):
+ *   a point p = (x, y, z) float32 in the Velodyne frame has camera-frame coordinates q = (-y, -z, x) (the reference's
+ *   R = R1 R2, a signed permutation: exact); a box is b = (bx, by, bz, h, w, l, ry), the KITTI label's location, dimensions
+ *   and rotation_y; d = q - (bx, by, bz) in fp64; c = cos ry and s = sin ry are evaluated once on the host in fp64;
+ *   lx = c dx - s dz, ly = dy, lz = s dx + c dz, every product and difference rounded as written (no fused multiply-add);
+ *   the point is inside iff |lx| <= l / 2, -h <= ly <= 0 and |lz| <= w / 2.  The box is CLOSED: a point on a face, an
+ *   edge or a corner is inside.  This is the convex hull of compute_box_3d's corners (checked against scipy on the CPU:
+ *   tests/test_tracklet_cpu.py).  A point with a non-finite coordinate is in no box.
+ *   ORDER: a crop holds its points in scan order (the reference's pc[inds]) with their float32 bits unchanged.
+ *   dz: subtracted from z in ONE float32 subtraction, z' = z (-) dz -- the reference's `pc2[:, 2] -= z_difference` on a
+ *   float32 array, where the NumPy of the reference's time casts the float64 scalar to float32 before it subtracts; the
+ *   caller passes float32(z_difference) for cloud 2 and 0 for cloud 1 (x - 0 keeps every bit, -0 included).
+ *   No colour columns: the reference reads [:, :3] everywhere, and colours need the camera images.
+ * alignnet_tracklet_upload_scans: F >= 0 frames, points [offsets[F]][stride] with stride 3 or 4 floats per point (a KITTI
+ *   .bin is 4: x y z reflectance; only x y z are read), offsets [F + 1] the first point of every frame (offsets[0] = 0).
+ *   Copied to the device once, nothing retained; replaces an earlier upload.  A bad stride or decreasing offsets fail and
+ *   leave the earlier upload in place.
+ * alignnet_tracklet_free_scans: frees the uploaded scans (the last result stays readable).
+ * alignnet_tracklet_extract: B >= 0 pairs; frames [B][2] the frame index of each cloud, boxes [B][2][7] fp64 as above,
+ *   dz [B][2] float32.  The two point blobs stay on the device; offsets [B + 1][2] (may be NULL) receives their row offsets
+ *   in the layout of alignnet_dataset_upload / alignnet_scene_generate.  A pair's crops do not depend on what else is in
+ *   the call.  A frame index out of range, a non-finite box value or dz, or a negative extent fails; a failed call leaves
+ *   the previous result and the uploaded scans as they were.
+ * alignnet_tracklet_read: copies the blobs of the last alignnet_tracklet_extract out (points1 / points2 [offsets[B][k]][3]).
+ * alignnet_tracklet_install_dataset: makes the last result the HBM-resident dataset (device to device), labels [B][12] as
+ *   for alignnet_dataset_upload; every *_dataset / *_rows entry point then works on the crops. */
+int alignnet_tracklet_upload_scans(alignnet_handle* h, const float* points, int32_t stride, const int64_t* offsets, int32_t F);
+int alignnet_tracklet_free_scans(alignnet_handle* h);
+int alignnet_tracklet_extract(alignnet_handle* h, const int32_t* frames, const double* boxes, const float* dz, int32_t B,
+                              int64_t* offsets);
+int alignnet_tracklet_read(alignnet_handle* h, float* points1, float* points2);
+int alignnet_tracklet_install_dataset(alignnet_handle* h, const float* labels);
+
 /* ---- run-time options with no counterpart in the reference's config surface --------
  * "train_matmul_bf16" (0/1, default 0): training only -- the two MFMA convs of every backbone (the hidden 1x1 conv
  *   and the -> C3 feature lift, 96 % of the step's FLOPs, models/tp8.py:55-57), in the forward and in the backward's
@@ -634,6 +670,8 @@ int alignnet_debug_scene_cast_rows(alignnet_handle* h, int32_t mesh, double scal
  *   ordered records, normals and counts per pair; a pair that needs more forms a chunk alone).  Results do not depend on it: a smaller value
  *   only cuts a call into more chunks (a test hook for the chunking, and a way to bound the allocation).
  *   "icp_plane_chunks" (read-only): the chunks the last point-to-plane call ran.
+ * "tracklet_chunk" (read-only): the points of a frame one workgroup of alignnet_tracklet_extract takes (1024);
+ *   "tracklet_jobs_per_pass" (read-only): the crop jobs of a frame it stages in LDS per pass (32).  Tests size their edge cases from them.
  * "ab_*" (0/1, default 0): A/B dispatch overrides -- each selects an earlier kernel variant of the SAME arithmetic for same-box comparisons
  *   (results agree up to summation order; tests/test_train_gpu.py runs them against the default): "ab_no_ld_const", "ab_infer_tile64",
  *   "ab_phase2_legacy", "ab_b1_legacy", "ab_b1_fp32", "ab_p3_bf16_generic", "ab_p3_nogram", "ab_no_defer", "ab_dg_sparse",
@@ -680,7 +718,7 @@ int alignnet_profile_read(alignnet_handle* h, double* backbone_ms, int64_t* back
  * "allreduce" (what the compute stream waits for), "optimizer", and the stages of alignnet_scene_generate: "scene_window" (azimuth windows),
  * "scene_cast" ("scene_band" instead when "scene_rows" is 1), "scene_compact" (counts, scan, scatter + noise), and of the ICP grid search: "icp_grid_build", "icp_grid" (the iterations), and of
  * point-to-plane ICP: "icp_plane_normals" (the ordering of the second grid's buckets + the normals), "icp_plane" (the iterations; its two grid builds
- * count under "icp_grid_build"). */
+ * count under "icp_grid_build"), and of alignnet_tracklet_extract: "tracklet_test" (membership + counts), "tracklet_compact" (scan + scatter). */
 int alignnet_profile_read_kernel(alignnet_handle* h, const char* name, double* ms, int64_t* launches);
 
 #ifdef __cplusplus
