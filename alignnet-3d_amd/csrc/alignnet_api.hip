@@ -476,6 +476,7 @@ static int run_backbone(alignnet_handle* h, const Stack& st, const float* p1, co
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused<128, 68, 132>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused<128, 68, 132, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused_stream<128, 68, 132, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused<64, 68, 132, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set.mark(h->cfg.device);
@@ -552,7 +553,14 @@ static int run_backbone(alignnet_handle* h, const Stack& st, const float* p1, co
     h->last_kernel = ALIGNNET_KERNEL_POINTNET_FUSED_64_128_K16_TP64;
   } else if (TP == 64) { TIMED_LAUNCH(pointnet_fused<64>, grid, dim3(kWaves * 64), lds, a); h->last_kernel = ALIGNNET_KERNEL_POINTNET_FUSED_TP64; }
   else if (a.ld[0] == 68 && a.ld[1] == 132 && st.n == 3 && h->layers[st.first + 2].cin == 128 && !(h->ab & AB_NO_LD_CONST)) {
-    TIMED_LAUNCH((pointnet_fused<128, 68, 132, 16>), grid, dim3(kWaves * 64), lds, a);
+    // row-serial last layer by default; the weight-stream schedule it replaced under "ab_last_layer_stream" (and in the cycle-stamp build, whose stamps it carries)
+#ifdef ALIGNNET_KSTAMP
+    const bool stream = true;
+#else
+    const bool stream = h->ab & AB_LAST_LAYER_STREAM;
+#endif
+    if (stream) { TIMED_LAUNCH((pointnet_fused_stream<128, 68, 132, 16>), grid, dim3(kWaves * 64), lds, a); }
+    else { TIMED_LAUNCH((pointnet_fused<128, 68, 132, 16>), grid, dim3(kWaves * 64), lds, a); }
     h->last_kernel = ALIGNNET_KERNEL_POINTNET_FUSED_64_128_K16;
   } else if (a.ld[0] == 68 && a.ld[1] == 132 && !(h->ab & AB_NO_LD_CONST)) {   // the shipped widths 64, 128
     TIMED_LAUNCH((pointnet_fused<128, 68, 132>), grid, dim3(kWaves * 64), lds, a);

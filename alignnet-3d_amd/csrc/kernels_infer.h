@@ -343,11 +343,50 @@ __device__ __forceinline__ void hidden_layer(const float* in, int ldi, float* ou
   for (int item = wave; item < CT * RG; item += kWaves) hidden_item<MR>(in, ldi, out, ldo, L, tower, item / RG, item % RG, lane);
 }
 
+// Row-serial last layer (shipped shape on 128-point tiles): one row tile of a channel tile, acc = A[rows M*32 .., :8 KG] * bw as ONE
+// dependent chain of 4 KG MFMAs (issue interval = dependent-accumulator latency = 64 cycles: a single chain runs at full rate).  The
+// channel tile's whole weight image bw[] stays in registers for its four chains, so a fragment is still fetched once per channel tile.
+// Under k-groups 1 .. 4 the PREVIOUS chain's accumulator (the other of two sets) goes through scale / shift / max, four registers per
+// k-group: the epilogue never takes the wave off the matrix pipe.  RELOAD (the channel tile's last chain): every fragment is requested
+// for the wave's next channel tile right after its last use, a whole chain (>= 4 k cycles) ahead of its first.  Per (row, column) the
+// products are accumulated in ascending k from a zero C operand: the same ordered fmaf chain as mfma_rows.
+// A fragments: one ds_read_b128 per k-group, two k-groups ahead (av[] is a ring over the channel tile's 4 KG steps).  Every k-group ends
+// with a compiler barrier AND a scheduling barrier: without the first hipcc hoists all the LDS reads of the unrolled chains to the top
+// (256 VGPRs + spills); with the first alone it sinks each read to its use behind lgkmcnt(0) and bunches the whole epilogue behind the
+// next chain's first MFMA.
+template <int KG, int M, bool RELOAD>
+__device__ __forceinline__ void rowserial_chain(const float* arow, int lda, f32x4 (&bw)[KG], const f32x4* __restrict__ wnext, f32x4 (&av)[3],
+                                                f32x16& acc, const f32x16& prev, float sc, float sh, float& mx)
+{
+  constexpr int MT = 4;
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kg = 0; kg < KG; ++kg) {
+    const int t = M * KG + kg;
+    if (t + 2 < MT * KG) av[(t + 2) % 3] = *reinterpret_cast<const f32x4*>(arow + ((t + 2) / KG) * 32 * lda + ((t + 2) % KG) * 8);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (kg == 0 && s == 0) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t % 3][s], bw[kg][s], zero, 0, 0, 0);
+      else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t % 3][s], bw[kg][s], acc, 0, 0, 0);
+    }
+    if (kg >= 1 && kg <= 4) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, fmaf(prev[(kg - 1) * 4 + r], sc, sh));
+    }
+    if (RELOAD) bw[kg] = wnext[kg * 64];
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // LD0 / LD1: compile-time LDS row strides of the two activation buffers (0 = from the arguments): immediates instead of address
 // registers in the unrolled hidden-layer epilogues
-template <int TP, int LD0 = 0, int LD1 = 0, int KGL = 0>   // KGL: k-groups of the last layer (0 = from the arguments)
-__global__ __launch_bounds__(kWaves * 64, 2) void pointnet_fused(const BackboneArgs a)
+// ROWSER: the last layer walks a channel tile's row tiles one after the other (rowserial_chain) instead of k-group outer, row tiles inner
+// on the hand-issued weight stream (mfma_rows)
+template <int TP, int LD0, int LD1, int KGL, bool ROWSER>   // KGL: k-groups of the last layer (0 = from the arguments)
+__device__ __forceinline__ void pointnet_fused_body(const BackboneArgs& a)
 {
+  static_assert(!ROWSER || (TP == 128 && LD1 != 0 && KGL != 0), "row-serial last layer: 128-point tiles, compile-time depth");
   const int lds_ld[2] = {LD0 ? LD0 : a.ld[0], LD1 ? LD1 : a.ld[1]};
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -385,6 +424,16 @@ __global__ __launch_bounds__(kWaves * 64, 2) void pointnet_fused(const BackboneA
     const bool live = c < L0.cout;
     l0w[g][0] = live ? L0.w[c] : 0.f; l0w[g][1] = live ? L0.w[L0.cout + c] : 0.f; l0w[g][2] = live ? L0.w[2 * L0.cout + c] : 0.f;
     l0w[g][3] = live ? L0.scale[tower * L0.cout + c] : 0.f; l0w[g][4] = live ? L0.shift[tower * L0.cout + c] : 0.f;
+  }
+  // row-serial last layer: the weight image of the wave's next channel tile (16 k-groups x f32x4), here the first one -- the first
+  // tile's prologue and hidden layer cover its round trip; from then on the last chain of a channel tile requests its successor's
+  [[maybe_unused]] f32x4 bw[ROWSER ? KGL : 1];
+  if constexpr (ROWSER) {
+    if (wave * 32 < a.L[a.nlayers - 1].cout) {
+      const f32x4* wp = reinterpret_cast<const f32x4*>(a.L[a.nlayers - 1].w) + (size_t)wave * KGL * 64 + lane;
+#pragma unroll
+      for (int kg = 0; kg < KGL; ++kg) bw[kg] = wp[kg * 64];
+    }
   }
   for (int tile = tile_lo; tile < tile_hi; ++tile) {
   if (tile != tile_lo) __syncthreads();   // the previous tile's readers are done with the LDS buffers
@@ -446,7 +495,59 @@ __global__ __launch_bounds__(kWaves * 64, 2) void pointnet_fused(const BackboneA
   }
 
   // ---- last layer + max over the tile's points (utils/tf_util.py:350-373) ----
-  {
+  if constexpr (ROWSER) {
+    const ConvLayerDev& L = a.L[a.nlayers - 1];   // three conv layers: input = buffer 1, stride LD1, depth KGL
+    const int CT = (L.cout + 31) >> 5;
+    const float* arow = smem + boff[1] + (lane & 31) * LD1 + (lane >> 5) * 4;
+    float* dst = a.pooled + tower * a.tower_stride + b * a.row_stride;
+    // a channel tile's maximum is complete when its last row tile's epilogue has run -- under the NEXT channel tile's first chain; only
+    // the wave's last channel tile of a point tile has that epilogue exposed (below the loop)
+    auto retire = [&](float m, int q, bool live, int col) {
+      if (q < kPoolRegs) {
+#pragma unroll
+        for (int u = 0; u < kPoolRegs; ++u)
+          if (u == q) pool[u] = fmaxf(pool[u], m);
+      } else {   // very wide last layers: beyond the register slots, publish per tile
+        m = fmaxf(m, __shfl_xor(m, 32));
+        if (lane < 32 && live) atomicMax(reinterpret_cast<int*>(dst + col), __float_as_int(m));   // >= 0: monotone bit pattern
+      }
+    };
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc1[r] = 0.f;   // nothing pending yet: with scale = shift = 0 the first spliced epilogue yields max(0, 0)
+    float scp = 0.f, shp = 0.f, mx = 0.f;
+    int qp = 0, colp = 0;
+    bool livep = false;
+    for (int ct = wave; ct < CT; ct += kWaves) {
+      // scale / shift are requested BEFORE the chains: first used a whole chain later
+      const int col = ct * 32 + (lane & 31);
+      const bool live = col < L.cout;
+      const float sc = live ? L.scale[tower * L.cout + col] : 0.f;
+      const float sh = live ? L.shift[tower * L.cout + col] : 0.f;
+      // the channel tile this wave touches next: ct + kWaves, else its first one on the next point tile; no reload when that is the
+      // resident one (C3 <= 256: one channel tile per wave) or when the workgroup has no further point tile
+      const int nct = ct + kWaves < CT ? ct + kWaves : wave;
+      const bool reload = nct != ct && (ct + kWaves < CT || tile + 1 < tile_hi);
+      const f32x4* wnext = reinterpret_cast<const f32x4*>(L.w) + (size_t)nct * KGL * 64 + lane;
+      f32x4 av[3];
+      av[0] = *reinterpret_cast<const f32x4*>(arow);
+      av[1] = *reinterpret_cast<const f32x4*>(arow + 8);
+      asm volatile("" ::: "memory");
+      rowserial_chain<KGL, 0, false>(arow, LD1, bw, wnext, av, acc0, acc1, scp, shp, mx);
+      retire(mx, qp, livep, colp);   // the previous channel tile (first one: max(pool[0], 0), a no-op)
+      mx = 0.f;   // relu folded into the max: max_n relu(v_n) = max(0, max_n v_n)
+      rowserial_chain<KGL, 1, false>(arow, LD1, bw, wnext, av, acc1, acc0, sc, sh, mx);
+      rowserial_chain<KGL, 2, false>(arow, LD1, bw, wnext, av, acc0, acc1, sc, sh, mx);
+      if (reload) rowserial_chain<KGL, 3, true>(arow, LD1, bw, wnext, av, acc1, acc0, sc, sh, mx);
+      else rowserial_chain<KGL, 3, false>(arow, LD1, bw, wnext, av, acc1, acc0, sc, sh, mx);
+      scp = sc; shp = sh; qp = (ct - wave) / kWaves; colp = col; livep = live;
+    }
+    if (wave < CT) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, fmaf(acc1[r], scp, shp));
+      retire(mx, qp, livep, colp);
+    }
+  } else {
     const int l = a.nlayers - 1;
     const ConvLayerDev& L = a.L[l];
     const float* in = smem + (((l - 1) & 1) ? boff[1] : boff[0]);
@@ -502,6 +603,19 @@ __global__ __launch_bounds__(kWaves * 64, 2) void pointnet_fused(const BackboneA
       }
     }
   }
+}
+
+// the shipped shape on 128-point tiles runs the row-serial last layer; every other instantiation the weight-stream one
+template <int TP, int LD0 = 0, int LD1 = 0, int KGL = 0>
+__global__ __launch_bounds__(kWaves * 64, 2) void pointnet_fused(const BackboneArgs a)
+{
+  pointnet_fused_body<TP, LD0, LD1, KGL, TP == 128 && LD0 == 68 && LD1 == 132 && KGL == 16>(a);
+}
+// the same instantiation with the weight-stream last layer ("ab_last_layer_stream": same-box comparisons, and the cycle stamps of the -DALIGNNET_KSTAMP build)
+template <int TP, int LD0, int LD1, int KGL>
+__global__ __launch_bounds__(kWaves * 64, 2) void pointnet_fused_stream(const BackboneArgs a)
+{
+  pointnet_fused_body<TP, LD0, LD1, KGL, false>(a);
 }
 
 // ---------------------------------------------------------------------------------

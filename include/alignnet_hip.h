@@ -675,7 +675,7 @@ int alignnet_tracklet_install_dataset(alignnet_handle* h, const float* labels);
  * "ab_*" (0/1, default 0): A/B dispatch overrides -- each selects an earlier kernel variant of the SAME arithmetic for same-box comparisons
  *   (results agree up to summation order; tests/test_train_gpu.py runs them against the default): "ab_no_ld_const", "ab_infer_tile64",
  *   "ab_phase2_legacy", "ab_b1_legacy", "ab_b1_fp32", "ab_p3_bf16_generic", "ab_p3_nogram", "ab_no_defer", "ab_dg_sparse",
- *   "ab_no_glue_fold", "ab_gemm_jobs_ksplit", "ab_fc_direct", "ab_fc_no_splitk", "ab_split_tilewise" (csrc/engine.h: AbBit), and "ab_tiles_per_wg" (eval PointNet backbone: point tiles per workgroup, 0 = automatic);
+ *   "ab_no_glue_fold", "ab_gemm_jobs_ksplit", "ab_fc_direct", "ab_fc_no_splitk", "ab_split_tilewise", "ab_last_layer_stream" (csrc/engine.h: AbBit), and "ab_tiles_per_wg" (eval PointNet backbone: point tiles per workgroup, 0 = automatic);
  *   "dg_cloud_parts" (dgcnn training: workgroups per cloud of the edge kernels, 0 = as many as fill the chip at this batch, 1 .. 8 = fixed; results agree up to the grouping of partial sums);
  *   "infer_tile_points" (eval PointNet backbone: points per workgroup tile; 0 = automatic -- 64-point tiles while the 128-point tiling would cover at most half of the
  *   256 CUs (2B x ceil(N / 128) <= 128: B <= 8 at N = 1024; 0.19 -> 0.134 ms per step at B = 1, 0.198 -> 0.142 at B = 8), 128 otherwise; 64 / 128 = fixed; bit-identical outputs);
