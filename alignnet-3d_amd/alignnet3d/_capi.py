@@ -167,6 +167,8 @@ SYMBOLS = {
     "alignnet_tracklet_upload_scans": (C.c_int, [H, FP, C.c_int32, C.POINTER(C.c_int64), C.c_int32]),
     "alignnet_tracklet_free_scans": (C.c_int, [H]),
     "alignnet_tracklet_extract": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_double), FP, C.c_int32, C.POINTER(C.c_int64)]),
+    "alignnet_tracklet_extract_frustum": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_double), FP, C.c_int32, C.POINTER(C.c_double),
+                                                    C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int64)]),
     "alignnet_tracklet_read": (C.c_int, [H, FP, FP]),
     "alignnet_tracklet_install_dataset": (C.c_int, [H, FP]),
     "alignnet_debug_scene_cast": (C.c_int, [H, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32),
@@ -183,7 +185,7 @@ SYMBOLS = {
 }
 
 # symbols added after ABI version 1 was fixed: an earlier build named by ALIGNNET_HIP_LIB loads without them
-LATE_SYMBOLS = ("alignnet_register", "alignnet_register_dataset")
+LATE_SYMBOLS = ("alignnet_register", "alignnet_register_dataset", "alignnet_tracklet_extract_frustum")
 
 _lib = None
 
@@ -211,7 +213,8 @@ def load_library():
             # an A/B build of an EARLIER revision (ALIGNNET_HIP_LIB, tools/ab_build.sh) may predate a test hook; the in-tree library must export everything
             if os.environ.get("ALIGNNET_HIP_LIB") and name.startswith("alignnet_debug_"):
                 continue
-            # likewise the one-call registration, added without moving ABI_VERSION: Engine.register* reports its absence (EngineError)
+            # likewise the one-call registration and the frustum crop, added without moving ABI_VERSION: Engine.register* and
+            # Engine.tracklet_extract_frustum report their absence (EngineError)
             if os.environ.get("ALIGNNET_HIP_LIB") and name in LATE_SYMBOLS:
                 continue
             raise

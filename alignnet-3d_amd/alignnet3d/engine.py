@@ -464,7 +464,7 @@ class Engine:
         try:
             return getattr(self._lib, name)
         except AttributeError:
-            raise EngineError("%s does not export %s: it was built from a revision before the one-call registration; rebuild it "
+            raise EngineError("%s does not export %s: it was built from a revision before that entry point was added; rebuild it "
                               "(make -C alignnet-3d_amd/csrc)" % (_capi.library_path(), name)) from None
 
     def _register_bufs(self, B, refine, radius, normal_radius, its, constrained, want_net, want_loss):
@@ -759,9 +759,11 @@ class Engine:
             off[1:] = np.cumsum([len(a) for a in arrs])
             pts = np.ascontiguousarray(np.concatenate(arrs, 0)) if arrs and stride else np.zeros((0, max(stride, 1)), np.float32)
         self._check(self._lib.alignnet_tracklet_upload_scans(self._h, _fp(pts), int(stride), off.ctypes.data_as(C.POINTER(C.c_int64)), off.size - 1))
+        self._tracklet_frames = off.size - 1
 
     def tracklet_free_scans(self):
         self._check(self._lib.alignnet_tracklet_free_scans(self._h))
+        self._tracklet_frames = 0
 
     def tracklet_extract(self, frames, boxes, dz=None):
         """frames [B, 2] indices into the uploaded scans, boxes [B, 2, 7] float64 = (x, y, z, h, w, l, ry) of the KITTI label (camera frame),
@@ -774,6 +776,34 @@ class Engine:
         off = np.zeros((B + 1, 2), np.int64)
         self._check(self._lib.alignnet_tracklet_extract(self._h, frames.ctypes.data_as(C.POINTER(C.c_int32)), boxes.ctypes.data_as(C.POINTER(C.c_double)),
                                                         _fp(dz), B, off.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._tracklet_offsets = off
+        return off
+
+    def tracklet_extract_frustum(self, frames, rects, proj, image, dz=None, clip=2.0):
+        """The image-frustum crop (the reference's from_bbox2d): frames [B, 2] as for tracklet_extract, rects [B, 2, 4] float64 = (xmin, ymin,
+        xmax, ymax) in pixels, proj the velodyne-to-image matrix M (tracklets.projection) as [3, 4] or [12] for all uploaded frames or [F, 3, 4]
+        one per frame, image = (W, H) or [F, 2], dz [B, 2] float32 (None = 0), clip the least x kept (exclusive).  A point is kept when its
+        projection lies in the image and in the rectangle, both half-open.  The result replaces, and is read and installed like, a
+        tracklet_extract's; returns the offsets table [B + 1, 2]."""
+        fn = self._register_fn("alignnet_tracklet_extract_frustum")
+        frames = np.ascontiguousarray(frames, np.int32).reshape(-1, 2)
+        B, F = frames.shape[0], getattr(self, "_tracklet_frames", 0)
+        rects = np.ascontiguousarray(rects, np.float64).reshape(B, 2, 4)
+        dz = np.zeros((B, 2), np.float32) if dz is None else np.ascontiguousarray(dz, np.float32).reshape(B, 2)
+        proj, image = np.asarray(proj, np.float64), np.asarray(image, np.float64)
+        if proj.size == 12:
+            proj = np.broadcast_to(proj.reshape(1, 12), (F, 12))
+        elif proj.shape != (F, 3, 4) and proj.shape != (F, 12):
+            raise ValueError("proj of shape %s: expected [3, 4], [12] or [%d, 3, 4] (one per uploaded frame)" % (proj.shape, F))
+        if image.size == 2 and image.ndim == 1:
+            image = np.broadcast_to(image.reshape(1, 2), (F, 2))
+        elif image.shape != (F, 2):
+            raise ValueError("image of shape %s: expected (W, H) or [%d, 2] (one per uploaded frame)" % (image.shape, F))
+        proj, image = np.ascontiguousarray(proj).reshape(F, 12), np.ascontiguousarray(image).reshape(F, 2)
+        off = np.zeros((B + 1, 2), np.int64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(fn(self._h, frames.ctypes.data_as(C.POINTER(C.c_int32)), dp(rects), _fp(dz), B, dp(proj), dp(image), float(clip),
+                       off.ctypes.data_as(C.POINTER(C.c_int64))))
         self._tracklet_offsets = off
         return off
 

@@ -6,11 +6,18 @@ get_transform_components (:876-885) give the labels, KittiTrackingLabels (:597-6
 (csrc/alignnet_crop.hip, defined by tests/tracklet_ref.py) and this module restates the host side: label parsing, the pairing, the twelve
 label columns, the meta record and the 4 x 4 transform.
 
+extract_pointcloud's other branch, from_bbox2d (extract_pc_in_box2d :794-801 -> get_lidar_in_image_fov :781-791 ->
+Calibration.project_velo_to_image :41-202), keeps every return whose image projection falls inside the label's 2D box: the crop a tracker
+has before any 3D box exists.  extract(..., from_bbox2d=True, calib=..., image_size=...) runs it on the GPU (defined by
+tests/frustum_ref.py); read_calib parses a calibration file as Calibration.read_calib_file does, projection multiplies P, R0 and V2C once,
+read_image_size reads (W, H) from a PNG's header (all the reference takes from the image on this path).
+
 What is this project's own: the reference's script that chooses WHICH (frame, frame) pairs of a track become examples is unpublished, the
 selection of the `Hard` variants included; `pairs` therefore pairs one track id in frames f and f + gap, and `gap` and `min_points` are
 options of this project, not the reference's.  No colour columns are produced (the reference reads [:, :3] everywhere, and colours need the
-camera images); from_bbox2d (the image-frustum crop) and FromHeldScene are not provided."""
+camera images' pixels); FromHeldScene is not provided."""
 import os
+import struct
 from collections import namedtuple
 
 import numpy as np
@@ -168,11 +175,77 @@ def extract_args(pair_list, frame_index):
     return frames, boxes, dz, lab
 
 
-def extract(engine, scans, pair_list, install=False):
+Calib = namedtuple("Calib", "P R0 V2C")
+
+
+def read_calib(path):
+    """A KITTI calibration file as Calib(P [3, 4] from P2, R0 [3, 3], V2C [3, 4]) float64.  Calibration.read_calib_file's parsing (:99-122):
+    `key value ...` per line, ':' stripped from the key, a line whose values are not all floats is skipped.  The tracking files' names
+    (Tr_velo_cam, R_rect) and the detection files' (Tr_velo_to_cam, R0_rect) are both accepted."""
+    data = {}
+    with open(path) as fh:
+        for line in fh:
+            line = line.rstrip()
+            if not line:
+                continue
+            key, _, value = line.partition(" ")
+            try:
+                data[key.replace(":", "")] = np.array([float(x) for x in value.split()])
+            except ValueError:
+                pass
+
+    def field(names, shape):
+        for n in names:
+            if n in data:
+                if data[n].size != shape[0] * shape[1]:
+                    raise ValueError("%s: %s has %d values, expected %d" % (path, n, data[n].size, shape[0] * shape[1]))
+                return data[n].reshape(shape)
+        raise ValueError("%s: no %s line" % (path, " / ".join(names)))
+
+    return Calib(field(("P2",), (3, 4)), field(("R_rect", "R0_rect"), (3, 3)), field(("Tr_velo_cam", "Tr_velo_to_cam"), (3, 4)))
+
+
+def projection(calib):
+    """M [3, 4] = P R0' V2C' (R0, V2C padded to 4 x 4) of a Calib: Velodyne point to homogeneous pixel, the three products of
+    project_velo_to_image (:157-202) multiplied once.  These bits are what the device receives."""
+    R4, V4 = np.eye(4), np.eye(4)
+    R4[:3, :3] = np.asarray(calib.R0, np.float64).reshape(3, 3)
+    V4[:3, :4] = np.asarray(calib.V2C, np.float64).reshape(3, 4)
+    return np.matmul(np.asarray(calib.P, np.float64).reshape(3, 4), np.matmul(R4, V4))
+
+
+def read_image_size(path):
+    """(W, H) of a PNG from its first 24 bytes (signature, IHDR length and tag, width, height): im.size of the reference (:854, :857)."""
+    with open(path, "rb") as fh:
+        head = fh.read(24)
+    if len(head) < 24 or head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
+        raise ValueError("%s: not a PNG header" % path)
+    return struct.unpack(">II", head[16:24])
+
+
+def frustum_args(pair_list, frame_index, calib, image_size):
+    """(rects [B, 2, 4] float64, proj [F, 3, 4], image [F, 2]) of Engine.tracklet_extract_frustum.  calib: a Calib, a matrix M [3, 4], or
+    {frame number: either}; image_size: (W, H) or {frame number: (W, H)}."""
+    rects = np.zeros((len(pair_list), 2, 4))
+    for i, p in enumerate(pair_list):
+        rects[i, 0], rects[i, 1] = p.bbox2d1, p.bbox2d2
+    of = lambda table, f: table[f] if isinstance(table, dict) else table
+    proj, image = np.zeros((len(frame_index), 3, 4)), np.zeros((len(frame_index), 2))
+    for f, i in frame_index.items():
+        c = of(calib, f)
+        proj[i] = projection(c) if isinstance(c, Calib) else np.asarray(c, np.float64).reshape(3, 4)
+        image[i] = of(image_size, f)
+    return rects, proj, image
+
+
+def extract(engine, scans, pair_list, install=False, from_bbox2d=False, calib=None, image_size=None, clip=2.0):
     """Crop `pair_list` (pairs of ONE sequence) on the GPU.  scans: {frame number: float32 [n, 3 or 4]} or a list indexed by frame number;
     the frames the pairs use are uploaded in one call.  Returns the offsets table [B + 1, 2]; the crops stay on the device --
     engine.tracklet_read() copies them out, install=True makes them the HBM-resident dataset with the pairs' labels (sample_batch,
-    train_step_rows, register_rows, ... then work on them)."""
+    train_step_rows, register_rows, ... then work on them).  from_bbox2d=True: the image-frustum crop to the pairs' bbox2d1 / bbox2d2 in
+    place of the 3D boxes (calib, image_size: see frustum_args; clip: the reference's clip_distance); labels and dz are the same."""
+    if from_bbox2d and (calib is None or image_size is None):
+        raise ValueError("from_bbox2d=True needs calib and image_size")
     get = scans.__getitem__
     used = sorted({f for p in pair_list for f in p.frames})
     index = {f: i for i, f in enumerate(used)}
@@ -181,7 +254,11 @@ def extract(engine, scans, pair_list, install=False):
     else:
         engine.tracklet_upload_scans([get(f) for f in used])
     frames, boxes, dz, lab = extract_args(pair_list, index)
-    off = engine.tracklet_extract(frames, boxes, dz)
+    if from_bbox2d:
+        rects, proj, image = frustum_args(pair_list, index, calib, image_size)
+        off = engine.tracklet_extract_frustum(frames, rects, proj, image, dz, clip)
+    else:
+        off = engine.tracklet_extract(frames, boxes, dz)
     if install:
         engine.tracklet_install_dataset(lab)
     return off

@@ -27,6 +27,24 @@
 //     for the others (the same function on the same numbers) and writes the members at offsets[pair][cloud] + position + ballot prefix.
 //     Counts, a scan, a scatter: no atomics that could reorder points.
 // The result is built in a second pair of blobs and swapped in on success: an error leaves the previous result and the uploaded scans as they were.
+//
+// The image-frustum crop (extract_pointcloud with from_bbox2d: extract_pc_in_box2d -> get_lidar_in_image_fov -> project_velo_to_image,
+// tp_utils/pointcloud.py:781-801, 41-202): every LiDAR return whose image projection falls inside the object's 2D box.  DEFINED by
+// tests/frustum_ref.py (fp64, NumPy):
+//  - a frame has a projection M [3][4] = P (R0 padded to 4 x 4) (V2C padded to 4 x 4), multiplied ONCE on the host in fp64 and handed over, an
+//    image size (W, H) and the call a clip distance; a job has a rectangle (xmin, ymin, xmax, ymax);
+//  - w_i = ((M[i][0] x + M[i][1] y) + M[i][2] z) + M[i][3] with x, y, z widened to fp64, every product and sum rounded as written (no fused
+//    multiply-add); u = w_0 / w_2, v = w_1 / w_2 (IEEE fp64 divisions);
+//  - the point is kept iff its coordinates are finite, x > clip, 0 <= u < W, 0 <= v < H, xmin <= u < xmax and ymin <= v < ymax: HALF-OPEN
+//    intervals, the reference's.  A comparison with a NaN or infinite u / v is false (w_2 == 0 needs no special case); the sign of w_2 is not
+//    tested (the reference's front test is x > clip);
+//  - order, bits and dz as for the box crop.
+// The calibration belongs to the FRAME: frustum_test_kernel has the grid and the registers of tracklet_test_kernel, projects each of its four
+// points ONCE (u, v and an "in the image and in front" flag: the two divisions are paid per chunk, not per job) and runs the frame's jobs,
+// staged through LDS in the same passes, over those registers: four fp64 compares, a ballot and a popcount per quarter and job.  There is no
+// float32 pre-test.  tracklet_jobscan_kernel and tracklet_scan_kernel are shared; frustum_scatter_kernel is tracklet_scatter_kernel with the
+// same projection (the same function on the same numbers) when a chunk has a member at all.  alignnet_tracklet_extract_frustum shares the
+// host's tables, buffers and result blobs with alignnet_tracklet_extract (run_extract below).
 #include "engine.h"
 #include <algorithm>
 #include <cmath>
@@ -56,7 +74,8 @@ struct CropJob {
 };
 static_assert(sizeof(CropJob) == 104, "LDS budget");
 
-struct CropFrame { long long pt0; int n, job0, njobs, pad; };   // first point of the frame in the uploaded scans, its points, its jobs in the sorted job list
+// first point of the frame in the uploaded scans, its points, its jobs in the sorted job list, its index in the upload (the frustum's calibration)
+struct CropFrame { long long pt0; int n, job0, njobs, frame; };
 
 struct Pt { float x, y, z; };
 
@@ -238,6 +257,133 @@ __global__ __launch_bounds__(kThreads) void tracklet_scatter_kernel(const float*
   }
 }
 
+// ---- the image-frustum crop ------------------------------------------------------------------------------------------------------------------
+struct FrustumJob {
+  double xmin, ymin, xmax, ymax;   // the 2D box, pixels
+  long long cbase;                 // as CropJob's
+  float dz;
+  int which, pair, pad;
+};
+static_assert(sizeof(FrustumJob) == 56, "LDS budget");
+
+struct FrustumCal { double m[12], W, H, clip; };   // of an uploaded frame: M row-major, the image size, the clip distance
+
+struct Px { double u, v; bool ok; };   // a projected point; ok: finite, in front of the clip distance and in the image
+
+__device__ __forceinline__ Px frustum_project(const FrustumCal& c, const Pt& p, bool valid)
+{
+#pragma clang fp contract(off)
+  const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
+  const double w0 = ((c.m[0] * x + c.m[1] * y) + c.m[2] * z) + c.m[3];
+  const double w1 = ((c.m[4] * x + c.m[5] * y) + c.m[6] * z) + c.m[7];
+  const double w2 = ((c.m[8] * x + c.m[9] * y) + c.m[10] * z) + c.m[11];
+  Px q;
+  q.u = w0 / w2; q.v = w1 / w2;
+  // a NaN or infinite u / v fails a comparison of every pair below
+  q.ok = valid && isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && x > c.clip && 0.0 <= q.u && q.u < c.W && 0.0 <= q.v && q.v < c.H;
+  return q;
+}
+
+__device__ __forceinline__ bool frustum_inside(const FrustumJob& j, const Px& q)
+{
+  return q.ok && j.xmin <= q.u && q.u < j.xmax && j.ymin <= q.v && q.v < j.ymax;
+}
+
+// grid: the (frame, chunk) items
+template <int STRIDE>
+__global__ __launch_bounds__(kThreads) void frustum_test_kernel(const float* __restrict__ scans, const CropFrame* __restrict__ frames,
+                                                                const int2* __restrict__ items, const FrustumJob* __restrict__ jobs,
+                                                                const FrustumCal* __restrict__ cals, int* __restrict__ counts)
+{
+  __shared__ FrustumJob sj[kJobsPerPass];
+  __shared__ int wcnt[kJobsPerPass][4];
+  const int2 it = items[blockIdx.x];
+  const CropFrame f = frames[it.x];
+  const FrustumCal cal = cals[f.frame];
+  const int chunk = it.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  Px q[kQuarters];
+  {
+    Pt p[kQuarters]; bool valid[kQuarters];
+    load_points<STRIDE>(scans, f, chunk, p, valid);
+#pragma unroll
+    for (int i = 0; i < kQuarters; ++i) q[i] = frustum_project(cal, p[i], valid[i]);
+  }
+  for (int j0 = 0; j0 < f.njobs; j0 += kJobsPerPass) {
+    const int nj = min(kJobsPerPass, f.njobs - j0);
+    {
+      // stage the pass's jobs: 14 dwords each
+      const int* src = reinterpret_cast<const int*>(jobs + f.job0 + j0);
+      int* dst = reinterpret_cast<int*>(sj);
+      for (int e = tid; e < nj * (int)(sizeof(FrustumJob) / 4); e += kThreads) dst[e] = src[e];
+    }
+    __syncthreads();
+    for (int j = 0; j < nj; ++j) {
+      int n = 0;
+#pragma unroll
+      for (int i = 0; i < kQuarters; ++i) n += __popcll(__ballot(frustum_inside(sj[j], q[i])));
+      if (lane == 0) wcnt[j][wave] = n;
+    }
+    __syncthreads();
+    for (int j = tid; j < nj; j += kThreads) counts[sj[j].cbase + chunk] = wcnt[j][0] + wcnt[j][1] + wcnt[j][2] + wcnt[j][3];
+    __syncthreads();
+  }
+}
+
+// grid: the (frame, chunk) items; tracklet_scatter_kernel with the frustum's test
+template <int STRIDE>
+__global__ __launch_bounds__(kThreads) void frustum_scatter_kernel(const float* __restrict__ scans, const CropFrame* __restrict__ frames,
+                                                                   const int2* __restrict__ items, const FrustumJob* __restrict__ jobs,
+                                                                   const FrustumCal* __restrict__ cals, const int* __restrict__ counts,
+                                                                   const int* __restrict__ pos, const long long* __restrict__ offsets,
+                                                                   float* __restrict__ out0, float* __restrict__ out1)
+{
+  __shared__ int wcnt[kQuarters][4];
+  const int2 it = items[blockIdx.x];
+  const CropFrame f = frames[it.x];
+  const int chunk = it.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  Pt p[kQuarters]; Px q[kQuarters];
+  bool loaded = false;
+  for (int j0 = 0; j0 < f.njobs; j0 += 64) {
+    // the counts of 64 jobs at once, a lane each: every wave reads the same numbers, so `hit` is the same in the whole workgroup
+    const int mine_job = j0 + lane;
+    const int cnt = mine_job < f.njobs ? counts[jobs[f.job0 + mine_job].cbase + chunk] : 0;
+    unsigned long long hit = __ballot(cnt != 0);
+    while (hit) {
+      const int jj = j0 + __ffsll((long long)hit) - 1;
+      hit &= hit - 1;
+      if (!loaded) {
+        bool valid[kQuarters];
+        const FrustumCal cal = cals[f.frame];
+        load_points<STRIDE>(scans, f, chunk, p, valid);
+#pragma unroll
+        for (int i = 0; i < kQuarters; ++i) q[i] = frustum_project(cal, p[i], valid[i]);
+        loaded = true;
+      }
+      const FrustumJob j = jobs[f.job0 + jj];
+      unsigned long long m[kQuarters];
+#pragma unroll
+      for (int i = 0; i < kQuarters; ++i) {
+        m[i] = __ballot(frustum_inside(j, q[i]));
+        if (lane == 0) wcnt[i][wave] = __popcll(m[i]);
+      }
+      __syncthreads();
+      float* out = (j.which ? out1 : out0) + (offsets[(long long)j.pair * 2 + j.which] + pos[j.cbase + chunk]) * 3;
+      int before = 0;   // members of this (job, chunk) ahead of the wave's 64 points of quarter i: scan order is (quarter, wave, lane)
+#pragma unroll
+      for (int i = 0; i < kQuarters; ++i) {
+        int mine = before;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const int n = wcnt[i][w]; if (w < wave) mine += n; before += n; }
+        if ((m[i] >> lane) & 1ull) {
+          float* o = out + (size_t)(mine + __popcll(m[i] & ((1ull << lane) - 1ull))) * 3;
+          o[0] = p[i].x; o[1] = p[i].y; o[2] = p[i].z - j.dz;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // ---- host state ------------------------------------------------------------------------------------------------------------------------------
 struct TrackletWS {
   // uploaded scans (alignnet_tracklet_upload_scans)
@@ -246,6 +392,8 @@ struct TrackletWS {
   float* d_scans = nullptr;
   // work buffers, grown on demand
   CropJob* d_jobs = nullptr; size_t cap_jobs = 0;
+  FrustumJob* d_fjobs = nullptr; size_t cap_fjobs = 0;
+  FrustumCal* d_cals = nullptr; size_t cap_cals = 0;
   CropFrame* d_frames = nullptr; size_t cap_frames = 0;
   int2* d_items = nullptr; size_t cap_items = 0;
   int* d_counts = nullptr; int* d_pos = nullptr; size_t cap_counts = 0, cap_pos = 0;
@@ -280,6 +428,84 @@ float pre_bound(double r, double b)
   return std::nextafter((float)t, INFINITY);
 }
 
+// What the box and the frustum extraction share, after their arguments are checked: the tables (entries of the counts table in (pair, cloud,
+// chunk) order; jobs sorted by frame), the three stages and the swap of the result blobs.  fill(job, j) sets what the test of job j = 2 pair +
+// cloud needs; test(items) and scatter(items) launch the two kernels over the (frame, chunk) items with the jobs at *d_jobs.
+template <typename Job, typename Fill, typename Test, typename Scatter>
+int run_extract(alignnet_handle* h, const std::string& name, const int32_t* frames, const float* dz, int32_t B, Job** d_jobs, size_t* cap_jobs,
+                Fill fill, Test test, Scatter scatter, int64_t* offsets)
+{
+  TrackletWS* w = tws(h);
+  const int J = 2 * B;
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  std::vector<JobSpan> spans(J);
+  long long entries_ll = 0;
+  for (int j = 0; j < J; ++j) {
+    const long long ch = (w->foff[frames[j] + 1] - w->foff[frames[j]] + kChunk - 1) / kChunk;
+    spans[j].cbase = entries_ll; spans[j].chunks = (int)ch; spans[j].pad = 0;
+    entries_ll += ch;
+  }
+  const size_t entries = (size_t)entries_ll;
+  std::vector<int> order(J);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return frames[a] < frames[b]; });
+  std::vector<Job> jobs(J);
+  std::vector<CropFrame> groups;
+  std::vector<int2> items;
+  for (int i = 0; i < J; ++i) {
+    const int j = order[i];
+    Job& c = jobs[i];
+    fill(c, j);
+    c.dz = dz[j]; c.cbase = spans[j].cbase; c.which = j % 2; c.pair = j / 2;
+    if (groups.empty() || frames[j] != frames[order[i - 1]]) {
+      CropFrame g;
+      g.pt0 = w->foff[frames[j]]; g.n = (int)(w->foff[frames[j] + 1] - w->foff[frames[j]]); g.job0 = i; g.njobs = 0; g.frame = frames[j];
+      for (int ch = 0; ch < (g.n + kChunk - 1) / kChunk; ++ch) items.push_back(make_int2((int)groups.size(), ch));
+      groups.push_back(g);
+    }
+    ++groups.back().njobs;
+  }
+  if (items.size() > 0x7fffffffull) return fail(h, name + ": too many (frame, chunk) work items");
+  std::vector<long long> off((size_t)(B + 1) * 2, 0);
+  if (J > 0) {
+    if (grow(h, d_jobs, cap_jobs, jobs.size()) || grow(h, &w->d_frames, &w->cap_frames, groups.size()) ||
+        grow(h, &w->d_items, &w->cap_items, items.size()) || grow(h, &w->d_counts, &w->cap_counts, entries) ||
+        grow(h, &w->d_pos, &w->cap_pos, entries) || grow(h, &w->d_spans, &w->cap_spans, spans.size()) ||
+        grow(h, &w->d_total, &w->cap_total, spans.size()) ||
+        grow(h, &w->d_offsets, &w->cap_off, off.size()))
+      return 1;
+    HIP_TRY(h, hipMemcpyAsync(*d_jobs, jobs.data(), jobs.size() * sizeof(Job), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(w->d_frames, groups.data(), groups.size() * sizeof(CropFrame), hipMemcpyHostToDevice, h->stream));
+    if (!items.empty()) HIP_TRY(h, hipMemcpyAsync(w->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(w->d_spans, spans.data(), spans.size() * sizeof(JobSpan), hipMemcpyHostToDevice, h->stream));
+    if (!items.empty()) {
+      alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_TEST);
+      test((unsigned)items.size());
+    }
+    {
+      alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_COMPACT);
+      hipLaunchKernelGGL(tracklet_jobscan_kernel, dim3((unsigned)J), dim3(kThreads), 0, h->stream, w->d_counts, w->d_spans, w->d_pos, w->d_total);
+      hipLaunchKernelGGL(tracklet_scan_kernel, dim3(1), dim3(1024), 0, h->stream, w->d_total, w->d_offsets, B);
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(off.data(), w->d_offsets, off.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 2; ++k)
+      if (grow(h, &w->d_next[k], &w->cap_next[k], (size_t)off[(size_t)B * 2 + k] * 3)) return 1;
+    if (!items.empty() && off[(size_t)B * 2] + off[(size_t)B * 2 + 1] > 0) {
+      alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_COMPACT);
+      scatter((unsigned)items.size());
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 2; ++k) { std::swap(w->d_pts[k], w->d_next[k]); std::swap(w->cap_pts[k], w->cap_next[k]); }
+  }
+  w->offsets.swap(off);
+  w->B = B;
+  if (offsets) for (size_t i = 0; i < w->offsets.size(); ++i) offsets[i] = w->offsets[i];
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int alignnet_tracklet_free_scans(alignnet_handle* h)
@@ -298,7 +524,7 @@ extern "C" void alignnet_tracklet_free(alignnet_handle* h)
   if (!h || !h->tracklet_ws) return;
   TrackletWS* w = tws(h);
   if (h->stream) hipStreamSynchronize(h->stream);
-  void* const ptrs[] = {w->d_scans, w->d_jobs, w->d_frames, w->d_items, w->d_counts, w->d_pos, w->d_spans, w->d_total, w->d_offsets,
+  void* const ptrs[] = {w->d_scans, w->d_jobs, w->d_fjobs, w->d_cals, w->d_frames, w->d_items, w->d_counts, w->d_pos, w->d_spans, w->d_total, w->d_offsets,
                         w->d_pts[0], w->d_pts[1], w->d_next[0], w->d_next[1]};
   for (void* p : ptrs) if (p) hipFree(p);
   delete w;
@@ -349,89 +575,94 @@ extern "C" int alignnet_tracklet_extract(alignnet_handle* h, const int32_t* fram
     for (int k = 3; k < 6; ++k) if (boxes[(size_t)j * 7 + k] < 0.0) return fail(h, name + ": negative box extent" + where);
     if (!std::isfinite(dz[j])) return fail(h, name + ": non-finite dz" + where);
   }
-  HIP_TRY(h, hipSetDevice(h->cfg.device));
-  // the tables: entries of the counts table in (pair, cloud, chunk) order; jobs sorted by frame
-  std::vector<JobSpan> spans(J);
-  long long entries_ll = 0;
+  return run_extract(
+      h, name, frames, dz, B, &w->d_jobs, &w->cap_jobs,
+      [&](CropJob& c, int j) {
+        const double* b = boxes + (size_t)j * 7;
+        c.bx = b[0]; c.by = b[1]; c.bz = b[2];
+        c.c = std::cos(b[6]); c.s = std::sin(b[6]);
+        c.h = b[3]; c.hw = b[4] * 0.5; c.hl = b[5] * 0.5;
+        const double rxz = std::hypot(c.hl, c.hw) * (1.0 + 1e-12);
+        c.fx = (float)b[0]; c.fy = (float)b[1]; c.fz = (float)b[2];
+        c.txz = pre_bound(rxz, std::max(std::fabs(b[0]), std::fabs(b[2])));
+        c.ty = pre_bound(c.h, b[1]);
+      },
+      [&](unsigned items) {
+        if (w->stride == 4)
+          hipLaunchKernelGGL(tracklet_test_kernel<4>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs, w->d_counts);
+        else
+          hipLaunchKernelGGL(tracklet_test_kernel<3>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs, w->d_counts);
+      },
+      [&](unsigned items) {
+        if (w->stride == 4)
+          hipLaunchKernelGGL(tracklet_scatter_kernel<4>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs,
+                             w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
+        else
+          hipLaunchKernelGGL(tracklet_scatter_kernel<3>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs,
+                             w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
+      },
+      offsets);
+}
+
+extern "C" int alignnet_tracklet_extract_frustum(alignnet_handle* h, const int32_t* frames, const double* rects, const float* dz, int32_t B,
+                                                 const double* proj, const double* image, double clip, int64_t* offsets)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_tracklet_extract_frustum");
+  if (!h->tracklet_ws || tws(h)->F < 0) return fail(h, name + ": no scans uploaded");
+  if (B < 0 || B > (1 << 24)) return fail(h, name + ": B out of range");
+  TrackletWS* w = tws(h);
+  if ((B > 0 && (!frames || !rects || !dz)) || (w->F > 0 && (!proj || !image))) return fail(h, name + ": null argument");
+  if (!std::isfinite(clip)) return fail(h, name + ": non-finite clip");
+  for (int f = 0; f < w->F; ++f) {
+    const std::string where = " (frame " + std::to_string(f) + ")";
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(proj[(size_t)f * 12 + k])) return fail(h, name + ": non-finite proj value" + where);
+    for (int k = 0; k < 2; ++k) {
+      if (!std::isfinite(image[(size_t)f * 2 + k])) return fail(h, name + ": non-finite image size" + where);
+      if (image[(size_t)f * 2 + k] <= 0.0) return fail(h, name + ": image size <= 0" + where);
+    }
+  }
+  const int J = 2 * B;
   for (int j = 0; j < J; ++j) {
-    const long long ch = (w->foff[frames[j] + 1] - w->foff[frames[j]] + kChunk - 1) / kChunk;
-    spans[j].cbase = entries_ll; spans[j].chunks = (int)ch; spans[j].pad = 0;
-    entries_ll += ch;
+    const std::string where = " (pair " + std::to_string(j / 2) + ", cloud " + std::to_string(j % 2 + 1) + ")";
+    if (frames[j] < 0 || frames[j] >= w->F) return fail(h, name + ": frame " + std::to_string(frames[j]) + " out of range" + where);
+    for (int k = 0; k < 4; ++k) if (!std::isfinite(rects[(size_t)j * 4 + k])) return fail(h, name + ": non-finite rect value" + where);
+    if (!std::isfinite(dz[j])) return fail(h, name + ": non-finite dz" + where);
   }
-  const size_t entries = (size_t)entries_ll;
-  std::vector<int> order(J);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return frames[a] < frames[b]; });
-  std::vector<CropJob> jobs(J);
-  std::vector<CropFrame> groups;
-  std::vector<int2> items;
-  for (int i = 0; i < J; ++i) {
-    const int j = order[i];
-    const double* b = boxes + (size_t)j * 7;
-    CropJob& c = jobs[i];
-    c.bx = b[0]; c.by = b[1]; c.bz = b[2];
-    c.c = std::cos(b[6]); c.s = std::sin(b[6]);
-    c.h = b[3]; c.hw = b[4] * 0.5; c.hl = b[5] * 0.5;
-    const double rxz = std::hypot(c.hl, c.hw) * (1.0 + 1e-12);
-    c.fx = (float)b[0]; c.fy = (float)b[1]; c.fz = (float)b[2];
-    c.txz = pre_bound(rxz, std::max(std::fabs(b[0]), std::fabs(b[2])));
-    c.ty = pre_bound(c.h, b[1]);
-    c.dz = dz[j]; c.cbase = spans[j].cbase; c.which = j % 2; c.pair = j / 2;
-    if (groups.empty() || frames[j] != frames[order[i - 1]]) {
-      CropFrame g;
-      g.pt0 = w->foff[frames[j]]; g.n = (int)(w->foff[frames[j] + 1] - w->foff[frames[j]]); g.job0 = i; g.njobs = 0; g.pad = 0;
-      for (int ch = 0; ch < (g.n + kChunk - 1) / kChunk; ++ch) items.push_back(make_int2((int)groups.size(), ch));
-      groups.push_back(g);
-    }
-    ++groups.back().njobs;
-  }
-  if (items.size() > 0x7fffffffull) return fail(h, name + ": too many (frame, chunk) work items");
-  std::vector<long long> off((size_t)(B + 1) * 2, 0);
+  std::vector<FrustumCal> cals;   // lives until run_extract has synchronised the stream
   if (J > 0) {
-    if (grow(h, &w->d_jobs, &w->cap_jobs, jobs.size()) || grow(h, &w->d_frames, &w->cap_frames, groups.size()) ||
-        grow(h, &w->d_items, &w->cap_items, items.size()) || grow(h, &w->d_counts, &w->cap_counts, entries) ||
-        grow(h, &w->d_pos, &w->cap_pos, entries) || grow(h, &w->d_spans, &w->cap_spans, spans.size()) ||
-        grow(h, &w->d_total, &w->cap_total, spans.size()) ||
-        grow(h, &w->d_offsets, &w->cap_off, off.size()))
-      return 1;
-    HIP_TRY(h, hipMemcpyAsync(w->d_jobs, jobs.data(), jobs.size() * sizeof(CropJob), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(w->d_frames, groups.data(), groups.size() * sizeof(CropFrame), hipMemcpyHostToDevice, h->stream));
-    if (!items.empty()) HIP_TRY(h, hipMemcpyAsync(w->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(w->d_spans, spans.data(), spans.size() * sizeof(JobSpan), hipMemcpyHostToDevice, h->stream));
-    if (!items.empty()) {
-      alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_TEST);
-      if (w->stride == 4)
-        hipLaunchKernelGGL(tracklet_test_kernel<4>, dim3((unsigned)items.size()), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs, w->d_counts);
-      else
-        hipLaunchKernelGGL(tracklet_test_kernel<3>, dim3((unsigned)items.size()), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs, w->d_counts);
+    // the calibration of every uploaded frame (120 bytes each), indexed by CropFrame::frame
+    cals.resize(w->F);
+    for (int f = 0; f < w->F; ++f) {
+      std::copy(proj + (size_t)f * 12, proj + (size_t)f * 12 + 12, cals[f].m);
+      cals[f].W = image[(size_t)f * 2]; cals[f].H = image[(size_t)f * 2 + 1]; cals[f].clip = clip;
     }
-    {
-      alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_COMPACT);
-      hipLaunchKernelGGL(tracklet_jobscan_kernel, dim3((unsigned)J), dim3(kThreads), 0, h->stream, w->d_counts, w->d_spans, w->d_pos, w->d_total);
-      hipLaunchKernelGGL(tracklet_scan_kernel, dim3(1), dim3(1024), 0, h->stream, w->d_total, w->d_offsets, B);
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(off.data(), w->d_offsets, off.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int k = 0; k < 2; ++k)
-      if (grow(h, &w->d_next[k], &w->cap_next[k], (size_t)off[(size_t)B * 2 + k] * 3)) return 1;
-    if (!items.empty() && off[(size_t)B * 2] + off[(size_t)B * 2 + 1] > 0) {
-      alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_COMPACT);
-      if (w->stride == 4)
-        hipLaunchKernelGGL(tracklet_scatter_kernel<4>, dim3((unsigned)items.size()), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs,
-                           w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
-      else
-        hipLaunchKernelGGL(tracklet_scatter_kernel<3>, dim3((unsigned)items.size()), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs,
-                           w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int k = 0; k < 2; ++k) { std::swap(w->d_pts[k], w->d_next[k]); std::swap(w->cap_pts[k], w->cap_next[k]); }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (grow(h, &w->d_cals, &w->cap_cals, cals.size())) return 1;
   }
-  w->offsets.swap(off);
-  w->B = B;
-  if (offsets) for (size_t i = 0; i < w->offsets.size(); ++i) offsets[i] = w->offsets[i];
-  return 0;
+  return run_extract(
+      h, name, frames, dz, B, &w->d_fjobs, &w->cap_fjobs,
+      [&](FrustumJob& c, int j) {
+        const double* r = rects + (size_t)j * 4;
+        c.xmin = r[0]; c.ymin = r[1]; c.xmax = r[2]; c.ymax = r[3]; c.pad = 0;
+      },
+      [&](unsigned items) {
+        // with the other tables: the stream is synchronised before `cals` goes (an error of the copy is the next hipGetLastError's)
+        (void)hipMemcpyAsync(w->d_cals, cals.data(), cals.size() * sizeof(FrustumCal), hipMemcpyHostToDevice, h->stream);
+        if (w->stride == 4)
+          hipLaunchKernelGGL(frustum_test_kernel<4>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_fjobs, w->d_cals, w->d_counts);
+        else
+          hipLaunchKernelGGL(frustum_test_kernel<3>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_fjobs, w->d_cals, w->d_counts);
+      },
+      [&](unsigned items) {
+        if (w->stride == 4)
+          hipLaunchKernelGGL(frustum_scatter_kernel<4>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_fjobs, w->d_cals,
+                             w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
+        else
+          hipLaunchKernelGGL(frustum_scatter_kernel<3>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_fjobs, w->d_cals,
+                             w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
+      },
+      offsets);
 }
 
 extern "C" int alignnet_tracklet_read(alignnet_handle* h, float* points1, float* points2)

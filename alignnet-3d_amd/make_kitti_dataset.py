@@ -14,7 +14,11 @@ evaluation.py, icp_global.py and icp_global_fast.py run on it as it is.
 Which frame pairs the reference used is unpublished (its pairing script is not part of the release, the selection of the `Hard` variants
 included): --gap (a track's frames f and f + gap form a pair) and --min-points (both crops hold at least that many points) are this
 project's options.  --val-seqs lists the sequences whose pairs go to split/val.txt.  --vo-dir DIR reads vo_%04d_%06d.txt pose files for the
-meta's vo1 / vo2 (the identity without it).  One sequence's frames are uploaded per engine call.  No colour columns are written."""
+meta's vo1 / vo2 (the identity without it).  One sequence's frames are uploaded per engine call.  No colour columns are written.
+--from-bbox2d takes the reference's other crop (extract_pointcloud's from_bbox2d branch): every return whose image projection falls inside
+the label's 2D box, the object together with ground and background.  It reads --calib-dir/%04d.txt (default ROOT/training/calib) and, for
+each frame's image size, the header of --image-dir/%04d/%06d.png (default ROOT/training/image_02) unless --image-size W,H gives it;
+--clip is the reference's clip_distance (2.0).  Meta, labels, transform and split files are the same as without it."""
 import argparse
 import json
 import os
@@ -35,6 +39,11 @@ def build_parser():
     ap.add_argument("--min-points", type=int, default=1, help="keep a pair only when both crops hold at least this many points")
     ap.add_argument("--val-seqs", default="", help="comma-separated sequence numbers whose pairs form split/val.txt")
     ap.add_argument("--vo-dir", default=None, help="directory of vo_%%04d_%%06d.txt visual-odometry poses (meta vo1 / vo2)")
+    ap.add_argument("--from-bbox2d", action="store_true", help="crop to the image frustum of the label's 2D box instead of the 3D box")
+    ap.add_argument("--calib-dir", default=None, help="with --from-bbox2d: directory of %%04d.txt calibration files (default <kitti>/training/calib)")
+    ap.add_argument("--image-dir", default=None, help="with --from-bbox2d: directory of %%04d/%%06d.png, read for their size only (default <kitti>/training/image_02)")
+    ap.add_argument("--image-size", default=None, metavar="W,H", help="with --from-bbox2d: the image size of every frame; no image is read")
+    ap.add_argument("--clip", type=float, default=2.0, help="with --from-bbox2d: keep points with x > clip (the reference's clip_distance)")
     ap.add_argument("--device", type=int, default=0)
     return ap
 
@@ -53,6 +62,18 @@ def parse_args(argv=None):
         args.val_seqs = sorted({int(s) for s in args.val_seqs.split(",") if s})
     except ValueError:
         ap.error("--val-seqs: comma-separated integers")
+    if args.image_size is not None:
+        try:
+            w, h = (float(s) for s in args.image_size.split(","))
+        except ValueError:
+            ap.error("--image-size: W,H")
+        if not (w > 0 and h > 0):
+            ap.error("--image-size: W and H must be > 0")
+        args.image_size = (w, h)
+    if not np.isfinite(args.clip):
+        ap.error("--clip must be finite")
+    args.calib_dir = args.calib_dir or os.path.join(args.kitti, "training", "calib")
+    args.image_dir = args.image_dir or os.path.join(args.kitti, "training", "image_02")
     return args
 
 
@@ -86,7 +107,12 @@ def main(argv=None):
         if not cand:
             continue
         scans = {f: T.read_scan(args.kitti, seq, f) for f in sorted({f for p in cand for f in p.frames})}
-        off = T.extract(eng, scans, cand)
+        if args.from_bbox2d:
+            calib = T.read_calib(os.path.join(args.calib_dir, "%04d.txt" % seq))
+            size = args.image_size or {f: T.read_image_size(os.path.join(args.image_dir, "%04d" % seq, "%06d.png" % f)) for f in scans}
+            off = T.extract(eng, scans, cand, from_bbox2d=True, calib=calib, image_size=size, clip=args.clip)
+        else:
+            off = T.extract(eng, scans, cand)
         p1, p2 = eng.tracklet_read(off)
         kept, idx = T.filter_min_points(cand, off, args.min_points)
         for pair, i in zip(kept, idx):

@@ -595,6 +595,28 @@ int alignnet_tracklet_extract(alignnet_handle* h, const int32_t* frames, const d
 int alignnet_tracklet_read(alignnet_handle* h, float* points1, float* points2);
 int alignnet_tracklet_install_dataset(alignnet_handle* h, const float* labels);
 
+/* ---- the image-frustum crop (extract_pointcloud with from_bbox2d: extract_pc_in_box2d -> get_lidar_in_image_fov ->
+ * Calibration.project_velo_to_image, tp_utils/pointcloud.py:781-801, 41-202) ----
+ * Every LiDAR return of an uploaded scan whose image projection falls inside an object's 2D box: the crop a tracker has before
+ * any 3D box exists (a detector's rectangle plus the calibration).  DEFINED by tests/frustum_ref.py (fp64):
+ *   a frame has a projection M [3][4] = P (R0 padded to 4 x 4) (V2C padded to 4 x 4), multiplied ONCE by the caller in fp64
+ *   (alignnet3d.tracklets.projection), and an image size (W, H); a point p = (x, y, z) float32, widened to fp64, has
+ *   w_i = ((M[i][0] x + M[i][1] y) + M[i][2] z) + M[i][3], every product and sum rounded as written (no fused multiply-add),
+ *   and u = w_0 / w_2, v = w_1 / w_2 (IEEE fp64 divisions).  A job's rectangle (xmin, ymin, xmax, ymax) keeps the point iff its
+ *   coordinates are finite, x > clip (the reference's clip_distance, 2.0), 0 <= u < W, 0 <= v < H, xmin <= u < xmax and
+ *   ymin <= v < ymax.  The intervals are HALF-OPEN, the reference's.  A comparison with a NaN or infinite u / v is false, so a
+ *   point with w_2 == 0 is in no crop; the sign of w_2 is not tested (the reference's front test is x > clip).
+ *   Order, bits and dz: as for alignnet_tracklet_extract.  No colour columns.
+ * alignnet_tracklet_extract_frustum: B >= 0 pairs; frames [B][2] and dz [B][2] as for alignnet_tracklet_extract; rects [B][2][4]
+ *   fp64 = xmin ymin xmax ymax; proj [F][12] (M row-major) and image [F][2] = W, H for EVERY uploaded frame (F of
+ *   alignnet_tracklet_upload_scans); clip one value for the call.  The result replaces, and is read and installed like, a box
+ *   extraction's (alignnet_tracklet_read, alignnet_tracklet_install_dataset).  No scans uploaded, a frame index out of range, a
+ *   non-finite rect, proj, image, clip or dz value, W or H <= 0 or a null argument fail before any device work and leave the
+ *   previous result and the uploaded scans as they were.  xmin >= xmax or ymin >= ymax is no error: an empty crop.
+ *   (Added without moving ALIGNNET_ABI_VERSION, as alignnet_register was.) */
+int alignnet_tracklet_extract_frustum(alignnet_handle* h, const int32_t* frames, const double* rects, const float* dz, int32_t B,
+                                      const double* proj, const double* image, double clip, int64_t* offsets);
+
 /* ---- run-time options with no counterpart in the reference's config surface --------
  * "train_matmul_bf16" (0/1, default 0): training only -- the two MFMA convs of every backbone (the hidden 1x1 conv
  *   and the -> C3 feature lift, 96 % of the step's FLOPs, models/tp8.py:55-57), in the forward and in the backward's
@@ -718,7 +740,7 @@ int alignnet_profile_read(alignnet_handle* h, double* backbone_ms, int64_t* back
  * "allreduce" (what the compute stream waits for), "optimizer", and the stages of alignnet_scene_generate: "scene_window" (azimuth windows),
  * "scene_cast" ("scene_band" instead when "scene_rows" is 1), "scene_compact" (counts, scan, scatter + noise), and of the ICP grid search: "icp_grid_build", "icp_grid" (the iterations), and of
  * point-to-plane ICP: "icp_plane_normals" (the ordering of the second grid's buckets + the normals), "icp_plane" (the iterations; its two grid builds
- * count under "icp_grid_build"), and of alignnet_tracklet_extract: "tracklet_test" (membership + counts), "tracklet_compact" (scan + scatter). */
+ * count under "icp_grid_build"), and of alignnet_tracklet_extract and alignnet_tracklet_extract_frustum: "tracklet_test" (membership + counts), "tracklet_compact" (scan + scatter). */
 int alignnet_profile_read_kernel(alignnet_handle* h, const char* name, double* ms, int64_t* launches);
 
 #ifdef __cplusplus
