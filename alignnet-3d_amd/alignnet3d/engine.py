@@ -914,6 +914,37 @@ class Engine:
             out["loss_cls"] = [get(4, 0, (2, B)), get(4, 1, (2, B)), get(4, 2, (2, B, B))]
         return out
 
+    def debug_loss(self, o2, s1c, o3, labels, num_bins, accept_inverted=True, early_stage_factor=0.5, angle_factor=1.0, want_grad=True,
+                   want_classes=True):
+        """The loss kernels alone on given head outputs (include/alignnet_hip.h: alignnet_debug_loss): o2 [2B, 3 + 2 nb], s1c [2B, 3], o3 [B, 3 + 2 nb],
+        towers outermost; labels as for eval_loss.  Nothing of the engine's own configuration or state enters.  dict: "out" [17] (loss, 16 summaries),
+        "s2c" [2B, 3], "theta" [2B], "pcls" int32 [2B]; want_classes: "cls" = [[2, B], [2, B], [2, B, B]] (tower 1, tower 2, pair); want_grad:
+        "d_s1c", "d_s2c", "d_o2", "d_o3" as the loss kernels leave them, in front of the glue backward."""
+        nb = int(num_bins)
+        ld = 3 + 2 * nb
+        o3 = np.ascontiguousarray(o3, np.float32)
+        B = o3.shape[0] if o3.ndim == 2 else 0
+        o2, s1c = np.ascontiguousarray(o2, np.float32), np.ascontiguousarray(s1c, np.float32)
+        if B >= 1 and nb >= 1 and (o2.shape != (2 * B, ld) or s1c.shape != (2 * B, 3) or o3.shape != (B, ld)):
+            raise ValueError(f"debug_loss: o2 {o2.shape}, s1c {s1c.shape}, o3 {o3.shape} do not fit B = {B}, num_bins = {nb}")
+        n = max(B, 0)
+        keep, L = self._labels(labels, n)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        res = {"out": np.empty(17, np.float32), "s2c": np.empty((2 * n, 3), np.float32), "theta": np.empty(2 * n, np.float32), "pcls": np.empty(2 * n, np.int32)}
+        cls = [np.empty((2, n), np.int32), np.empty((2, n), np.int32), np.empty((2, n, n), np.int32)] if want_classes else None
+        grads = {k: np.empty((2 * n, w), np.float32) for k, w in (("d_s1c", 3), ("d_s2c", 3), ("d_o2", ld))} if want_grad else {}
+        if want_grad:
+            grads["d_o3"] = np.empty((n, ld), np.float32)
+        gp = [_fp(grads[k]) if want_grad else None for k in ("d_s1c", "d_s2c", "d_o2", "d_o3")]
+        cp = [ip(c) if want_classes else None for c in (cls or [None] * 3)]
+        self._check(self._lib.alignnet_debug_loss(self._h, B, nb, int(bool(accept_inverted)), float(early_stage_factor), float(angle_factor), int(bool(want_grad)),
+                                                  _fp(o2), _fp(s1c), _fp(o3), C.byref(L), _fp(res["out"]), _fp(res["s2c"]), _fp(res["theta"]), ip(res["pcls"]),
+                                                  cp[0], cp[1], cp[2], gp[0], gp[1], gp[2], gp[3]))
+        if want_classes:
+            res["cls"] = cls
+        res.update(grads)
+        return res
+
     def debug_train_rounded(self, B):
         """bf16 step, fused PointNet stages: the bf16-rounded h1 / h2 the step's MFMA convs multiplied (alignnet_debug_train_rounded), keyed like the relu masks
         by the conv layer that CONSUMES them: "<tower>:<scope>/conv2" -> h1 as float32 [B*N, C1], "<tower>:<scope>/conv3" -> h2 [B*N, C2]."""

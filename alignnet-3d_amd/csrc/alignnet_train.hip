@@ -2147,6 +2147,73 @@ int alignnet_eval_loss_launch(alignnet_handle* h, const alignnet_labels* d_label
   return 0;
 }
 
+// test hook (include/alignnet_hip.h): the loss kernels on GIVEN head outputs.  Everything the loss depends on is an argument and every buffer is
+// staged here (one allocation, freed before returning), so the call reads and writes nothing of the handle's workspaces: stage2_finish_kernel
+// (decode), launch_loss (ff_net == nullptr) and dbg_angle_class_kernel are the product's, on the handle's stream.
+extern "C" int alignnet_debug_loss(alignnet_handle* h, int32_t B, int32_t nb, int32_t accept_inverted, float early_stage_factor, float angle_factor,
+                                   int32_t want_grad, const float* o2, const float* s1c, const float* o3, const alignnet_labels* labels, float* out,
+                                   float* s2c, float* theta, int32_t* pcls, int32_t* cls1, int32_t* cls2, int32_t* cls_pair, float* d_s1c, float* d_s2c,
+                                   float* d_o2, float* d_o3)
+{
+  if (!h) return 1;
+  if (B < 1 || nb < 1) return fail(h, "alignnet_debug_loss: B and nb must be >= 1");
+  if (!o2 || !s1c || !o3 || !labels) return fail(h, "alignnet_debug_loss: null argument");
+  const float* src[6] = {labels->translations, labels->rel_angles, labels->pc1_centers, labels->pc2_centers, labels->pc1_angles, labels->pc2_angles};
+  for (int i = 0; i < 6; ++i)
+    if (!src[i]) return fail(h, "alignnet_debug_loss: all six label tensors are required");
+  HIP_TRY(h, hipSetDevice(h->cfg.device));
+  const size_t Bz = (size_t)B, B2 = 2 * Bz, ld = 3 + 2 * (size_t)nb;
+  auto r64 = [](size_t n) { return (n + 63) & ~(size_t)63; };
+  // carve: inputs | labels | decode | out | gradients | scratch | classes
+  size_t off = 0;
+  auto take = [&](size_t n) { const size_t o = off; off += r64(n); return o; };
+  const size_t o_o2 = take(B2 * ld), o_s1c = take(B2 * 3), o_o3 = take(Bz * ld);
+  const int lw[6] = {3, 1, 3, 3, 1, 1};
+  size_t o_lab[6];
+  for (int i = 0; i < 6; ++i) o_lab[i] = take(Bz * lw[i]);
+  const size_t o_s2c = take(B2 * 3), o_xf = take(B2 * 12), o_th = take(B2), o_pc = take(B2), o_out = take(32);
+  const size_t o_g0 = off;
+  const size_t o_ds1 = take(B2 * 3), o_ds2 = take(B2 * 3), o_do2 = take(B2 * ld), o_do3 = take(Bz * ld), o_scr = take(loss_scratch_floats(B));
+  const size_t o_g1 = off;
+  const size_t o_c1 = take(B2), o_c2 = take(B2), o_cp = take(2 * Bz * Bz);
+  float* base = nullptr;
+  HIP_TRY(h, hipMalloc(&base, off * sizeof(float)));
+  // gradients and scratch start as all-ones bytes (NaN as floats): an element the kernels leave unwritten, or read before writing, shows
+  hipMemsetAsync(base + o_g0, 0xff, (o_g1 - o_g0) * sizeof(float), h->stream);
+  hipMemcpyAsync(base + o_o2, o2, B2 * ld * sizeof(float), hipMemcpyHostToDevice, h->stream);
+  hipMemcpyAsync(base + o_s1c, s1c, B2 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream);
+  hipMemcpyAsync(base + o_o3, o3, Bz * ld * sizeof(float), hipMemcpyHostToDevice, h->stream);
+  for (int i = 0; i < 6; ++i) hipMemcpyAsync(base + o_lab[i], src[i], Bz * lw[i] * sizeof(float), hipMemcpyHostToDevice, h->stream);
+  int* d_pcls = reinterpret_cast<int*>(base + o_pc);
+  hipLaunchKernelGGL(stage2_finish_kernel, dim3((unsigned)((B2 + 3) / 4)), dim3(256), 0, h->stream, base + o_o2, (int)ld, base + o_s1c, B, nb, base + o_s2c,
+                     base + o_xf, base + o_th, d_pcls, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+  LossArgs la{};
+  la.B = B; la.nb = nb; la.esf = early_stage_factor; la.af = angle_factor; la.accept_inverted = accept_inverted ? 1 : 0;
+  la.s1c = base + o_s1c; la.s2c = base + o_s2c; la.o2 = base + o_o2; la.ldo2 = (int)ld; la.o3 = base + o_o3; la.ldo3 = (int)ld;
+  la.theta = base + o_th; la.pcls = d_pcls;
+  la.tr = base + o_lab[0]; la.c1 = base + o_lab[2]; la.c2 = base + o_lab[3]; la.a1 = base + o_lab[4]; la.a2 = base + o_lab[5];
+  la.out = base + o_out; la.d_s1c = base + o_ds1; la.d_s2c = base + o_ds2; la.d_o2 = base + o_do2; la.d_o3 = base + o_do3;
+  la.scratch = base + o_scr; la.want_grad = want_grad ? 1 : 0;
+  launch_loss(h, la);
+  int32_t* hc[3] = {cls1, cls2, cls_pair};
+  const size_t oc[3] = {o_c1, o_c2, o_cp};
+  for (int t = 0; t < 3; ++t) {
+    if (!hc[t]) continue;
+    const size_t n = 2 * Bz * (t == 2 ? Bz : 1);
+    int* d = reinterpret_cast<int*>(base + oc[t]);
+    hipLaunchKernelGGL(dbg_angle_class_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, la.a1, la.a2, la.theta, B, nb, t, d);
+    hipMemcpyAsync(hc[t], d, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+  }
+  auto back = [&](void* dst, size_t o, size_t n) { if (dst) hipMemcpyAsync(dst, base + o, n * sizeof(float), hipMemcpyDeviceToHost, h->stream); };
+  back(out, o_out, 17); back(s2c, o_s2c, B2 * 3); back(theta, o_th, B2); back(pcls, o_pc, B2);
+  if (want_grad) { back(d_s1c, o_ds1, B2 * 3); back(d_s2c, o_ds2, B2 * 3); back(d_o2, o_do2, B2 * ld); back(d_o3, o_do3, Bz * ld); }
+  hipError_t e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) e = hipGetLastError();
+  hipFree(base);
+  if (e != hipSuccess) return fail(h, std::string("alignnet_debug_loss: ") + hipGetErrorString(e));
+  return 0;
+}
+
 extern "C" int alignnet_grad_buffer(alignnet_handle* h, float** d_grad, size_t* count)
 {
   if (!h) return 1;

@@ -501,7 +501,7 @@ struct LossArgs {
   float* d_s1c; float* d_s2c;                  // [2B][3]   (direct loss terms; d_s2c includes the pred_translations path)
   float* d_o2;                                 // [2B][3+2nb]: only the logits part is written ([3:]); [:3] zeroed
   float* d_o3;                                 // [B][3+2nb]
-  float* scratch;                              // >= 8*B floats + 4*B ints worth of space
+  float* scratch;                              // loss_scratch_floats(B) floats (alignnet_train.hip), carved by loss_scratch() below
   int want_grad;
   // the pair head's output glue (kernels_infer.h: final_finish_kernel -- pred_translations = head[:, :3] + (s2c2 - s2c1), remaining-angle logits), spread over
   // loss_prep_kernel's threads: elementwise on values the loss reads anyway, a 5 us launch of its own before.  ff_net == nullptr: not folded.
@@ -548,7 +548,11 @@ __device__ __forceinline__ float huberf(float e, float d)
 }
 __device__ __forceinline__ float clipf(float e, float d) { return fminf(fmaxf(e, -d), d); }
 
-// tf_angle2class (tp8.py:181-199), scalar
+// tf_angle2class (tp8.py:181-199), scalar.  Out-of-range rule: just below the wrap the float32 quotient sh / apc can round
+// up to nb itself (nb = 17, 19, 34, 35, 38, 45, 90, 180, 360 of the counts probed; none of the shipped 10, 12, 36, 50).  TF has no answer there (a
+// one-hot of depth nb at index nb).  Here class nb IS class 0: the residual stays as computed against centre nb (about -1 in units of pi / nb), so that
+// (class, residual) still names the label's angle modulo 2 pi.  Every caller takes the class from here: the loss, its gradient and the debug read-back
+// stay in step.
 __device__ __forceinline__ void angle2class(float angle, int nb, int* cls, float* res)
 {
   const float twopi = 6.28318548202514648f;   // np.float32(2*np.pi)
@@ -556,7 +560,7 @@ __device__ __forceinline__ void angle2class(float angle, int nb, int* cls, float
   const float apc = twopi / (float)nb;
   const float sh = floor_modf(a + apc * 0.5f, twopi);
   const int c = (int)(sh / apc);
-  *cls = c;
+  *cls = c >= nb ? c - nb : c;
   *res = sh - ((float)c * apc + apc * 0.5f);
 }
 
@@ -568,8 +572,8 @@ __device__ __forceinline__ void angle2class(float angle, int nb, int* cls, float
 // Scratch layout (floats unless noted): see LossScratch.
 struct LossScratch {
   float* lse;      // [3][B]
-  float* pick;     // [3][2][B]
-  float* lab;      // [2][2][B]      stage-2 labels per tower / variant
+  float* pick;     // [3][2][B]      unused: loss_pairs_body re-derives the picked residual logit and the labels from the inputs; the two
+  float* lab;      // [2][2][B]      slots keep their place so that the layout (and loss_scratch_floats) stays as every caller sizes it
   int* cls;        // [3][2][B]
   float* sjf;      // [3][B]         S_j of the chosen variant (reduced over the G partials)
   float* hub;      // [8]            the five Huber means
@@ -604,7 +608,7 @@ __global__ __launch_bounds__(1024) void loss_prep_kernel(const LossArgs a, int G
 {
   __shared__ double red[16 * 6];
   const int B = a.B, nb = a.nb, tid = threadIdx.x, nt = blockDim.x;
-  const float pi = 3.14159274101257324f, pinb = (float)(3.141592653589793 / (double)nb);
+  const float pi = 3.14159274101257324f;
   const LossScratch S = loss_scratch(a.scratch, B, G);
   if (a.ff_net) {
     const int w = 3 + 2 * nb;
@@ -670,8 +674,6 @@ __global__ __launch_bounds__(1024) void loss_prep_kernel(const LossArgs a, int G
         angle2class(tgt + (v ? pi : 0.f), nb, &c, &r);
         const int cc = min(max(c, 0), nb - 1);
         S.cls[(term * 2 + v) * B + i] = cc;
-        S.pick[(term * 2 + v) * B + i] = lg[nb + cc];
-        if (term < 2) S.lab[(term * 2 + v) * B + i] = r / pinb;
         const double d = (double)(l - lg[cc]);
         if (term == 0) ce[0][v] += d; else if (term == 1) ce[1][v] += d; else ce[2][v] += d;
       }

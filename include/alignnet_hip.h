@@ -235,6 +235,24 @@ int alignnet_debug_train_relu_mask(alignnet_handle* h, int32_t kind, int32_t sta
  * `bf16_lift`) and takes THESE rounded values -- after checking each is one of the two bf16 neighbours of its own value -- is a smooth function of its inputs,
  * as with the decisions and signs above.  Same calling window as alignnet_debug_train_relu_mask. */
 int alignnet_debug_train_rounded(alignnet_handle* h, int32_t stage, int32_t layer, uint16_t* dst, size_t count);
+/* Test hook: the loss kernels ALONE, on given head outputs (tests/test_loss_gpu.py).  Everything the loss depends on is an argument -- B pairs, nb angle
+ * bins, accept_inverted, the two factors -- so one handle serves any parametrisation, whatever its own configuration; the call stages its own buffers and
+ * touches no state of the handle's workspaces.  It runs, unchanged and on the handle's stream, the decode of the stage-2 heads (models/tp8.py:117,294-301),
+ * the loss with its gradient (:304-354) and the read-back of the label classes.  Host arrays, float32, towers outermost (tower 1's B rows, then tower 2's):
+ *   in   o2 [2B][3 + 2 nb]  stage-2 head outputs (centre offset, class logits, residual logits), s1c [2B][3] stage-1 centres,
+ *        o3 [B][3 + 2 nb]   pair head outputs; labels: all six tensors of alignnet_labels
+ *   out  out[17]            the loss and the 16 summaries (order of alignnet_step_result.summaries)
+ *        s2c [2B][3], theta [2B], pcls [2B]   stage-2 centres, decoded yaw and its arg-max class (first maximum wins)
+ *        cls1, cls2 [2][B], cls_pair [2][B][B]   the class of every target angle (target, target + pi), as ALIGNNET_DECISION_ANGLE_CLASS lays them out.
+ *                           Always in [0, nb): where the float32 quotient of tf_angle2class rounds up to nb (labels just below the wrap, some nb only)
+ *                           the class is 0 and the residual stays as computed, so that (class, residual) names the label's angle modulo 2 pi.
+ *        want_grad != 0:    d_s1c, d_s2c [2B][3], d_o2 [2B][3 + 2 nb], d_o3 [B][3 + 2 nb]: the gradient as the loss kernels leave it, in front of the
+ *                           glue backward (d_s2c holds the pred_translations path; d_o2[:, :3] is zero)
+ * Any output pointer may be NULL.  B < 1, nb < 1 or a NULL input or label tensor: error, nothing is launched. */
+int alignnet_debug_loss(alignnet_handle* h, int32_t B, int32_t nb, int32_t accept_inverted, float early_stage_factor, float angle_factor,
+                        int32_t want_grad, const float* o2, const float* s1c, const float* o3, const alignnet_labels* labels, float* out,
+                        float* s2c, float* theta, int32_t* pcls, int32_t* cls1, int32_t* cls2, int32_t* cls_pair, float* d_s1c, float* d_s2c,
+                        float* d_o2, float* d_o3);
 
 /* ---- multi-GPU (not in the reference, which is single-device: train.py:189).
  *      One process per GPU; RCCL communicator over xGMI for the gradient all-reduce. */

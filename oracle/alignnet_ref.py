@@ -413,7 +413,10 @@ def huber(err, delta):
 
 
 def angle2class(angle, nb):
-    """models/tp8.py:181-199.  angle [B,1] (or [B,B]) -> (class_id[:,0] [B], residual same shape)."""
+    """models/tp8.py:181-199.  angle [B,1] (or [B,B]) -> (class_id[:,0] [B], residual same shape).
+    Out-of-range rule (the project's choice; TF has none: a one-hot of depth nb at index nb): in float32 the quotient
+    sh / apc of a label just below the wrap can round up to nb itself (nb = 17, 19, 34, 35, 38, 45, 90, 180, 360; not 10, 12, 36, 50).
+    Class nb is class 0, and the residual stays as computed against centre nb, so that (class, residual) names the angle modulo 2 pi."""
     dt = angle.dtype.type
     twopi = dt(np.float32(2.0 * np.pi))
     a = floor_mod(angle, twopi)
@@ -421,6 +424,7 @@ def angle2class(angle, nb):
     sh = floor_mod(a + apc / dt(2.0), twopi)
     cls = (sh / apc).astype(np.int32)  # tf.to_int32 truncates; sh/apc >= 0
     res = sh - (cls.astype(angle.dtype) * apc + apc / dt(2.0))
+    cls = np.where(cls >= nb, cls - np.int32(nb), cls)
     return cls[:, 0], res
 
 
@@ -436,8 +440,7 @@ def angle_loss(logits, target_angles, nb):
     broadcasts to [B,B] -- reference behaviour, reproduced as is."""
     dt = logits.dtype.type
     cls, res = angle2class(target_angles, nb)
-    # an out-of-range class id would make TF's sparse CE return NaN; clamp never triggers
-    # for finite angles except sh/apc == nb by rounding, kept as-is (index error if so).
+    # (a class id of nb, which rounding can produce just below the wrap, has been wrapped to 0 by angle2class)
     ce = softmax_ce(logits[:, :nb], cls).mean()
     onehot_pick = logits[:, nb:][np.arange(logits.shape[0]), cls]  # [B]
     label = res / dt(np.float32(np.pi / nb))  # [B,1] or [B,B]; the Python float np.pi / nb enters the graph as a float32 constant

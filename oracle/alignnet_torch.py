@@ -334,6 +334,7 @@ class TorchTp8:
             res = res - twopi * torch.round(res / twopi)
         else:
             res = sh - (cls.to(logits.dtype) * apc + apc / 2)
+            cls = torch.where(cls >= nb, cls - nb, cls)   # class nb (rounding, just below the wrap) is class 0, residual as computed: alignnet_ref.angle2class
         cls0 = cls[:, 0].long()
         ce = F.cross_entropy(logits[:, :nb], cls0)
         pick = (logits[:, nb:] * F.one_hot(cls0, nb).to(logits.dtype)).sum(1)  # [B]
