@@ -2,6 +2,7 @@
 // eval-mode forward orchestration.  gfx950 only; no CPU fallback by design -- every entry
 // point fails with an error when HIP is unavailable.
 #include "engine.h"
+#include "host_util.h"
 #include "kernels_infer.h"
 #include "kernels_dgcnn.h"
 #include "kernels_infer_split.h"
@@ -16,21 +17,6 @@
 using namespace alignnet;
 
 static thread_local std::string g_create_err;
-
-#define HIP_TRY(h, expr)                                                                         \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) {                                                                      \
-      (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                              \
-      return 1;                                                                                  \
-    }                                                                                            \
-  } while (0)
-
-static int fail(const alignnet_handle* h, const std::string& m)
-{
-  h->err = m;
-  return 1;
-}
 
 // ---------------------------------------------------------------------------------
 // graph description -> layer + parameter tables (models/tp8.py:101-158; names SURVEY 8.A2)

@@ -11,18 +11,21 @@
 //  - the crop keeps the points in scan order with their float32 bits unchanged (the reference's pc[inds]); dz is subtracted from z in ONE
 //    float32 subtraction (pc2[:, 2] -= z_difference on a float32 array under the NumPy of the reference's time).  No colour columns.
 //
-// Stages of one alignnet_tracklet_extract (B pairs = 2 B crop jobs against the uploaded scans); the host groups the jobs by frame:
-//  1. tracklet_test_kernel, one workgroup of four waves per (frame, chunk of kTrackletChunk points): the chunk's points are loaded once (stride 4:
-//     one 16-byte load per point) and held in registers, four per thread, a wave holding 64 consecutive points per quarter.  The frame's jobs go
-//     through LDS in passes of kTrackletJobsPerPass.  Per job: a float32 pre-test, then (only where some lane of the wave passed it) the fp64
-//     test; ballot + popcount gives the wave's count, the four waves' counts go to counts[job][chunk].
+// Stages of one extraction (B pairs = 2 B crop jobs against the uploaded scans); the host groups the jobs by frame.  The two kernels that test
+// points are templates on a crop policy C (BoxCrop here, FrustumCrop below: the membership test and what it needs per job, frame and point) and
+// on the scans' stride; everything else of them is written once:
+//  1. crop_test_kernel<C>, one workgroup of four waves per (frame, chunk of kTrackletChunk points): the chunk's points are loaded once (stride 4:
+//     one 16-byte load per point) and held in registers, four per thread, a wave holding 64 consecutive points per quarter; C::prepare then
+//     derives what the policy keeps per point.  The frame's jobs go through LDS in passes of kTrackletJobsPerPass.  Per job and quarter
+//     C::ballot gives the wave's membership mask; its popcount is the wave's count, the four waves' counts go to counts[job][chunk].
+//     BoxCrop::ballot: a float32 pre-test, then (only where some lane of the wave passed it) the fp64 test.
 //     The pre-test is CONSERVATIVE: with bf = float(b) and df = q (-) bf in float32, |df| <= (|d| + 2^-24 |b|)(1 + 2^-24); an inside point has
 //     |dx|, |dz| <= hypot(l / 2, w / 2) and |dy| <= h, so a point is rejected only when |df| exceeds that bound enlarged by (|b| 6e-8) and a factor
 //     1 + 1e-6, rounded up to the next float.  A NaN compares false and is never rejected here (the fp64 test refuses it).
 //  2. tracklet_jobscan_kernel, one workgroup per job: the exclusive scan of the job's counts in chunk order -> the position of every (job, chunk)
 //     inside the job's crop, and the job's total; tracklet_scan_kernel, one workgroup: the exclusive scan of the totals in pair order per cloud
 //     index -> the offsets table [B + 1][2].  It goes to the host (the one small copy of a call), which sizes the blobs from its last row.
-//  3. tracklet_scatter_kernel, the grid of stage 1: a workgroup reads its chunk's counts of 64 jobs at once (a lane each) and skips every job whose
+//  3. crop_scatter_kernel<C>, the grid of stage 1: a workgroup reads its chunk's counts of 64 jobs at once (a lane each) and skips every job whose
 //     count is zero (typically under 2 % of a frame's points are in any box: most chunks load no point at all), repeats the test of stage 1
 //     for the others (the same function on the same numbers) and writes the members at offsets[pair][cloud] + position + ballot prefix.
 //     Counts, a scan, a scatter: no atomics that could reorder points.
@@ -39,13 +42,11 @@
 //    intervals, the reference's.  A comparison with a NaN or infinite u / v is false (w_2 == 0 needs no special case); the sign of w_2 is not
 //    tested (the reference's front test is x > clip);
 //  - order, bits and dz as for the box crop.
-// The calibration belongs to the FRAME: frustum_test_kernel has the grid and the registers of tracklet_test_kernel, projects each of its four
-// points ONCE (u, v and an "in the image and in front" flag: the two divisions are paid per chunk, not per job) and runs the frame's jobs,
-// staged through LDS in the same passes, over those registers: four fp64 compares, a ballot and a popcount per quarter and job.  There is no
-// float32 pre-test.  tracklet_jobscan_kernel and tracklet_scan_kernel are shared; frustum_scatter_kernel is tracklet_scatter_kernel with the
-// same projection (the same function on the same numbers) when a chunk has a member at all.  alignnet_tracklet_extract_frustum shares the
-// host's tables, buffers and result blobs with alignnet_tracklet_extract (run_extract below).
+// The calibration belongs to the FRAME: FrustumCrop::prepare projects each of a thread's four points ONCE (u, v and an "in the image and in
+// front" flag: the two divisions are paid per chunk, not per job), and FrustumCrop::ballot is four fp64 compares on those registers.  There is
+// no float32 pre-test.  alignnet_tracklet_extract_frustum shares everything else with alignnet_tracklet_extract (run_extract below).
 #include "engine.h"
+#include "host_util.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -53,14 +54,6 @@
 #include <vector>
 
 namespace {
-
-int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1; }
-
-#define HIP_TRY(h, expr)                                                                         \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return fail(h, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
 
 constexpr int kChunk = alignnet::kTrackletChunk, kJobsPerPass = alignnet::kTrackletJobsPerPass;
 constexpr int kThreads = 256, kQuarters = kChunk / kThreads;
@@ -94,13 +87,27 @@ __device__ __forceinline__ bool crop_inside(const CropJob& j, const Pt& p)
   return fabs(lx) <= j.hl && -j.h <= dy && dy <= 0.0 && fabs(lz) <= j.hw;
 }
 
-// the membership of the wave's 64 points of one quarter: the pre-test first, the fp64 test only where some lane passed it
-__device__ __forceinline__ unsigned long long crop_ballot(const CropJob& j, const Pt& p, bool valid)
-{
-  const bool pre = valid && crop_pre(j, p);
-  if (__ballot(pre) == 0ull) return 0ull;
-  return __ballot(pre && crop_inside(j, p));
-}
+// A crop policy C is what crop_test_kernel and crop_scatter_kernel are compiled for (static functions only: nothing is chosen at run time):
+//  - C::Job, a job as the kernels read it (dz, cbase, which, pair and what the test needs); C::Cal, what the test needs per frame (void: nothing);
+//  - C::Prep, what a thread keeps per point besides the point; C::prepare fills it for the thread's kQuarters points, once per chunk;
+//  - C::ballot, the membership of the wave's 64 points of one quarter in one job.
+struct BoxCrop {
+  typedef CropJob Job;
+  typedef void Cal;
+  typedef bool Prep;   // the point exists (the chunk's tail)
+  static __device__ __forceinline__ void prepare(const Cal*, const CropFrame&, const Pt*, const bool* valid, Prep* q)
+  {
+#pragma unroll
+    for (int i = 0; i < kQuarters; ++i) q[i] = valid[i];
+  }
+  // the pre-test first, the fp64 test only where some lane passed it
+  static __device__ __forceinline__ unsigned long long ballot(const Job& j, const Pt& p, const Prep& valid)
+  {
+    const bool pre = valid && crop_pre(j, p);
+    if (__ballot(pre) == 0ull) return 0ull;
+    return __ballot(pre && crop_inside(j, p));
+  }
+};
 
 template <int STRIDE>
 __device__ __forceinline__ void load_points(const float* __restrict__ scans, const CropFrame& f, int chunk, Pt* p, bool* valid)
@@ -123,31 +130,37 @@ __device__ __forceinline__ void load_points(const float* __restrict__ scans, con
 }
 
 // grid: the (frame, chunk) items
-template <int STRIDE>
-__global__ __launch_bounds__(kThreads) void tracklet_test_kernel(const float* __restrict__ scans, const CropFrame* __restrict__ frames,
-                                                                 const int2* __restrict__ items, const CropJob* __restrict__ jobs,
-                                                                 int* __restrict__ counts)
+template <class C, int STRIDE>
+__global__ __launch_bounds__(kThreads) void crop_test_kernel(const float* __restrict__ scans, const CropFrame* __restrict__ frames,
+                                                             const int2* __restrict__ items, const typename C::Job* __restrict__ jobs,
+                                                             const typename C::Cal* __restrict__ cals, int* __restrict__ counts)
 {
-  __shared__ CropJob sj[kJobsPerPass];
+  typedef typename C::Job Job;
+  static_assert(sizeof(Job) % 4 == 0, "jobs are staged dword by dword");
+  __shared__ Job sj[kJobsPerPass];
   __shared__ int wcnt[kJobsPerPass][4];
   const int2 it = items[blockIdx.x];
   const CropFrame f = frames[it.x];
   const int chunk = it.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  Pt p[kQuarters]; bool valid[kQuarters];
-  load_points<STRIDE>(scans, f, chunk, p, valid);
+  Pt p[kQuarters]; typename C::Prep q[kQuarters];
+  {
+    bool valid[kQuarters];
+    load_points<STRIDE>(scans, f, chunk, p, valid);
+    C::prepare(cals, f, p, valid, q);
+  }
   for (int j0 = 0; j0 < f.njobs; j0 += kJobsPerPass) {
     const int nj = min(kJobsPerPass, f.njobs - j0);
     {
-      // stage the pass's jobs: 26 dwords each
+      // stage the pass's jobs, dword by dword
       const int* src = reinterpret_cast<const int*>(jobs + f.job0 + j0);
       int* dst = reinterpret_cast<int*>(sj);
-      for (int e = tid; e < nj * (int)(sizeof(CropJob) / 4); e += kThreads) dst[e] = src[e];
+      for (int e = tid; e < nj * (int)(sizeof(Job) / 4); e += kThreads) dst[e] = src[e];
     }
     __syncthreads();
     for (int j = 0; j < nj; ++j) {
       int n = 0;
 #pragma unroll
-      for (int i = 0; i < kQuarters; ++i) n += __popcll(crop_ballot(sj[j], p[i], valid[i]));
+      for (int i = 0; i < kQuarters; ++i) n += __popcll(C::ballot(sj[j], p[i], q[i]));
       if (lane == 0) wcnt[j][wave] = n;
     }
     __syncthreads();
@@ -209,17 +222,18 @@ __global__ __launch_bounds__(1024) void tracklet_scan_kernel(const int* __restri
 }
 
 // grid: the (frame, chunk) items
-template <int STRIDE>
-__global__ __launch_bounds__(kThreads) void tracklet_scatter_kernel(const float* __restrict__ scans, const CropFrame* __restrict__ frames,
-                                                                    const int2* __restrict__ items, const CropJob* __restrict__ jobs,
-                                                                    const int* __restrict__ counts, const int* __restrict__ pos,
-                                                                    const long long* __restrict__ offsets, float* __restrict__ out0, float* __restrict__ out1)
+template <class C, int STRIDE>
+__global__ __launch_bounds__(kThreads) void crop_scatter_kernel(const float* __restrict__ scans, const CropFrame* __restrict__ frames,
+                                                                const int2* __restrict__ items, const typename C::Job* __restrict__ jobs,
+                                                                const typename C::Cal* __restrict__ cals, const int* __restrict__ counts,
+                                                                const int* __restrict__ pos, const long long* __restrict__ offsets,
+                                                                float* __restrict__ out0, float* __restrict__ out1)
 {
   __shared__ int wcnt[kQuarters][4];
   const int2 it = items[blockIdx.x];
   const CropFrame f = frames[it.x];
   const int chunk = it.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  Pt p[kQuarters]; bool valid[kQuarters];
+  Pt p[kQuarters]; typename C::Prep q[kQuarters];
   bool loaded = false;
   for (int j0 = 0; j0 < f.njobs; j0 += 64) {
     // the counts of 64 jobs at once, a lane each: every wave reads the same numbers, so `hit` is the same in the whole workgroup
@@ -229,18 +243,21 @@ __global__ __launch_bounds__(kThreads) void tracklet_scatter_kernel(const float*
     while (hit) {
       const int jj = j0 + __ffsll((long long)hit) - 1;
       hit &= hit - 1;
-      const CropJob& gj = jobs[f.job0 + jj];
-      const long long slot = gj.cbase + chunk;
-      if (!loaded) { load_points<STRIDE>(scans, f, chunk, p, valid); loaded = true; }
-      const CropJob j = gj;
+      if (!loaded) {
+        bool valid[kQuarters];
+        load_points<STRIDE>(scans, f, chunk, p, valid);
+        C::prepare(cals, f, p, valid, q);
+        loaded = true;
+      }
+      const typename C::Job j = jobs[f.job0 + jj];
       unsigned long long m[kQuarters];
 #pragma unroll
       for (int i = 0; i < kQuarters; ++i) {
-        m[i] = crop_ballot(j, p[i], valid[i]);
+        m[i] = C::ballot(j, p[i], q[i]);
         if (lane == 0) wcnt[i][wave] = __popcll(m[i]);
       }
       __syncthreads();
-      float* out = (j.which ? out1 : out0) + (offsets[(long long)j.pair * 2 + j.which] + pos[slot]) * 3;
+      float* out = (j.which ? out1 : out0) + (offsets[(long long)j.pair * 2 + j.which] + pos[j.cbase + chunk]) * 3;
       int before = 0;   // members of this (job, chunk) ahead of the wave's 64 points of quarter i: scan order is (quarter, wave, lane)
 #pragma unroll
       for (int i = 0; i < kQuarters; ++i) {
@@ -289,100 +306,19 @@ __device__ __forceinline__ bool frustum_inside(const FrustumJob& j, const Px& q)
   return q.ok && j.xmin <= q.u && q.u < j.xmax && j.ymin <= q.v && q.v < j.ymax;
 }
 
-// grid: the (frame, chunk) items
-template <int STRIDE>
-__global__ __launch_bounds__(kThreads) void frustum_test_kernel(const float* __restrict__ scans, const CropFrame* __restrict__ frames,
-                                                                const int2* __restrict__ items, const FrustumJob* __restrict__ jobs,
-                                                                const FrustumCal* __restrict__ cals, int* __restrict__ counts)
-{
-  __shared__ FrustumJob sj[kJobsPerPass];
-  __shared__ int wcnt[kJobsPerPass][4];
-  const int2 it = items[blockIdx.x];
-  const CropFrame f = frames[it.x];
-  const FrustumCal cal = cals[f.frame];
-  const int chunk = it.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  Px q[kQuarters];
+struct FrustumCrop {
+  typedef FrustumJob Job;
+  typedef FrustumCal Cal;
+  typedef Px Prep;
+  // the calibration belongs to the frame: a point is projected once per chunk, not per job
+  static __device__ __forceinline__ void prepare(const Cal* __restrict__ cals, const CropFrame& f, const Pt* p, const bool* valid, Prep* q)
   {
-    Pt p[kQuarters]; bool valid[kQuarters];
-    load_points<STRIDE>(scans, f, chunk, p, valid);
+    const FrustumCal cal = cals[f.frame];
 #pragma unroll
     for (int i = 0; i < kQuarters; ++i) q[i] = frustum_project(cal, p[i], valid[i]);
   }
-  for (int j0 = 0; j0 < f.njobs; j0 += kJobsPerPass) {
-    const int nj = min(kJobsPerPass, f.njobs - j0);
-    {
-      // stage the pass's jobs: 14 dwords each
-      const int* src = reinterpret_cast<const int*>(jobs + f.job0 + j0);
-      int* dst = reinterpret_cast<int*>(sj);
-      for (int e = tid; e < nj * (int)(sizeof(FrustumJob) / 4); e += kThreads) dst[e] = src[e];
-    }
-    __syncthreads();
-    for (int j = 0; j < nj; ++j) {
-      int n = 0;
-#pragma unroll
-      for (int i = 0; i < kQuarters; ++i) n += __popcll(__ballot(frustum_inside(sj[j], q[i])));
-      if (lane == 0) wcnt[j][wave] = n;
-    }
-    __syncthreads();
-    for (int j = tid; j < nj; j += kThreads) counts[sj[j].cbase + chunk] = wcnt[j][0] + wcnt[j][1] + wcnt[j][2] + wcnt[j][3];
-    __syncthreads();
-  }
-}
-
-// grid: the (frame, chunk) items; tracklet_scatter_kernel with the frustum's test
-template <int STRIDE>
-__global__ __launch_bounds__(kThreads) void frustum_scatter_kernel(const float* __restrict__ scans, const CropFrame* __restrict__ frames,
-                                                                   const int2* __restrict__ items, const FrustumJob* __restrict__ jobs,
-                                                                   const FrustumCal* __restrict__ cals, const int* __restrict__ counts,
-                                                                   const int* __restrict__ pos, const long long* __restrict__ offsets,
-                                                                   float* __restrict__ out0, float* __restrict__ out1)
-{
-  __shared__ int wcnt[kQuarters][4];
-  const int2 it = items[blockIdx.x];
-  const CropFrame f = frames[it.x];
-  const int chunk = it.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  Pt p[kQuarters]; Px q[kQuarters];
-  bool loaded = false;
-  for (int j0 = 0; j0 < f.njobs; j0 += 64) {
-    // the counts of 64 jobs at once, a lane each: every wave reads the same numbers, so `hit` is the same in the whole workgroup
-    const int mine_job = j0 + lane;
-    const int cnt = mine_job < f.njobs ? counts[jobs[f.job0 + mine_job].cbase + chunk] : 0;
-    unsigned long long hit = __ballot(cnt != 0);
-    while (hit) {
-      const int jj = j0 + __ffsll((long long)hit) - 1;
-      hit &= hit - 1;
-      if (!loaded) {
-        bool valid[kQuarters];
-        const FrustumCal cal = cals[f.frame];
-        load_points<STRIDE>(scans, f, chunk, p, valid);
-#pragma unroll
-        for (int i = 0; i < kQuarters; ++i) q[i] = frustum_project(cal, p[i], valid[i]);
-        loaded = true;
-      }
-      const FrustumJob j = jobs[f.job0 + jj];
-      unsigned long long m[kQuarters];
-#pragma unroll
-      for (int i = 0; i < kQuarters; ++i) {
-        m[i] = __ballot(frustum_inside(j, q[i]));
-        if (lane == 0) wcnt[i][wave] = __popcll(m[i]);
-      }
-      __syncthreads();
-      float* out = (j.which ? out1 : out0) + (offsets[(long long)j.pair * 2 + j.which] + pos[j.cbase + chunk]) * 3;
-      int before = 0;   // members of this (job, chunk) ahead of the wave's 64 points of quarter i: scan order is (quarter, wave, lane)
-#pragma unroll
-      for (int i = 0; i < kQuarters; ++i) {
-        int mine = before;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { const int n = wcnt[i][w]; if (w < wave) mine += n; before += n; }
-        if ((m[i] >> lane) & 1ull) {
-          float* o = out + (size_t)(mine + __popcll(m[i] & ((1ull << lane) - 1ull))) * 3;
-          o[0] = p[i].x; o[1] = p[i].y; o[2] = p[i].z - j.dz;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
+  static __device__ __forceinline__ unsigned long long ballot(const Job& j, const Pt&, const Prep& q) { return __ballot(frustum_inside(j, q)); }
+};
 
 // ---- host state ------------------------------------------------------------------------------------------------------------------------------
 struct TrackletWS {
@@ -391,8 +327,7 @@ struct TrackletWS {
   std::vector<long long> foff;              // [F + 1] first point of every frame
   float* d_scans = nullptr;
   // work buffers, grown on demand
-  CropJob* d_jobs = nullptr; size_t cap_jobs = 0;
-  FrustumJob* d_fjobs = nullptr; size_t cap_fjobs = 0;
+  char* d_jobs = nullptr; size_t cap_jobs = 0;   // the call's C::Job table, in bytes
   FrustumCal* d_cals = nullptr; size_t cap_cals = 0;
   CropFrame* d_frames = nullptr; size_t cap_frames = 0;
   int2* d_items = nullptr; size_t cap_items = 0;
@@ -408,18 +343,6 @@ struct TrackletWS {
 
 TrackletWS* tws(alignnet_handle* h) { return static_cast<TrackletWS*>(h->tracklet_ws); }
 
-template <typename T>
-int grow(alignnet_handle* h, T** p, size_t* cap, size_t need)
-{
-  if (need <= *cap && *p) return 0;
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (*p) hipFree(*p);
-  *p = nullptr; *cap = 0;
-  HIP_TRY(h, hipMalloc(p, std::max<size_t>(need, 1) * sizeof(T)));
-  *cap = std::max<size_t>(need, 1);
-  return 0;
-}
-
 // the float32 bound of the pre-test: (r + |b| 6e-8)(1 + 1e-6) rounded up (the header of this file); not finite -> nothing is rejected
 float pre_bound(double r, double b)
 {
@@ -428,15 +351,49 @@ float pre_bound(double r, double b)
   return std::nextafter((float)t, INFINITY);
 }
 
-// What the box and the frustum extraction share, after their arguments are checked: the tables (entries of the counts table in (pair, cloud,
-// chunk) order; jobs sorted by frame), the three stages and the swap of the result blobs.  fill(job, j) sets what the test of job j = 2 pair +
-// cloud needs; test(items) and scatter(items) launch the two kernels over the (frame, chunk) items with the jobs at *d_jobs.
-template <typename Job, typename Fill, typename Test, typename Scatter>
-int run_extract(alignnet_handle* h, const std::string& name, const int32_t* frames, const float* dz, int32_t B, Job** d_jobs, size_t* cap_jobs,
-                Fill fill, Test test, Scatter scatter, int64_t* offsets)
+std::string job_where(int j) { return " (pair " + std::to_string(j / 2) + ", cloud " + std::to_string(j % 2 + 1) + ")"; }
+
+// the two kernels of policy C over the (frame, chunk) items, for the stride of the uploaded scans
+template <class C>
+void launch_test(alignnet_handle* h, const TrackletWS* w, unsigned items, const typename C::Job* jobs, const typename C::Cal* cals)
 {
+  if (w->stride == 4)
+    hipLaunchKernelGGL((crop_test_kernel<C, 4>), dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, jobs, cals, w->d_counts);
+  else
+    hipLaunchKernelGGL((crop_test_kernel<C, 3>), dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, jobs, cals, w->d_counts);
+}
+
+template <class C>
+void launch_scatter(alignnet_handle* h, const TrackletWS* w, unsigned items, const typename C::Job* jobs, const typename C::Cal* cals)
+{
+  if (w->stride == 4)
+    hipLaunchKernelGGL((crop_scatter_kernel<C, 4>), dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, jobs, cals, w->d_counts,
+                       w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
+  else
+    hipLaunchKernelGGL((crop_scatter_kernel<C, 3>), dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, jobs, cals, w->d_counts,
+                       w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
+}
+
+// What the box (C = BoxCrop) and the frustum (FrustumCrop) extraction share: the checks of the call and of every job's frame and dz, the tables
+// (entries of the counts table in (pair, cloud, chunk) order; jobs sorted by frame), the three stages and the swap of the result blobs.
+// check(F) and check_job(j) are the entry point's checks of its own arguments, of the call against the F uploaded frames and of job j = 2 pair +
+// cloud (they return fail()'s 1), called where the entry points made them before the checks were shared; the frustum's check(F) fills `cals`,
+// the calibration of every uploaded frame, which stays empty for the box.  fill(job, j) sets what the test of job j needs.
+template <class C, typename Check, typename CheckJob, typename Fill>
+int run_extract(alignnet_handle* h, const std::string& name, const int32_t* frames, const float* dz, int32_t B, const std::vector<FrustumCal>& cals,
+                Check check, CheckJob check_job, Fill fill, int64_t* offsets)
+{
+  typedef typename C::Job Job;
+  if (!h->tracklet_ws || tws(h)->F < 0) return fail(h, name + ": no scans uploaded");
+  if (B < 0 || B > (1 << 24)) return fail(h, name + ": B out of range");
   TrackletWS* w = tws(h);
   const int J = 2 * B;
+  if (check(w->F)) return 1;
+  for (int j = 0; j < J; ++j) {
+    if (frames[j] < 0 || frames[j] >= w->F) return fail(h, name + ": frame " + std::to_string(frames[j]) + " out of range" + job_where(j));
+    if (check_job(j)) return 1;
+    if (!std::isfinite(dz[j])) return fail(h, name + ": non-finite dz" + job_where(j));
+  }
   HIP_TRY(h, hipSetDevice(h->cfg.device));
   std::vector<JobSpan> spans(J);
   long long entries_ll = 0;
@@ -468,19 +425,23 @@ int run_extract(alignnet_handle* h, const std::string& name, const int32_t* fram
   if (items.size() > 0x7fffffffull) return fail(h, name + ": too many (frame, chunk) work items");
   std::vector<long long> off((size_t)(B + 1) * 2, 0);
   if (J > 0) {
-    if (grow(h, d_jobs, cap_jobs, jobs.size()) || grow(h, &w->d_frames, &w->cap_frames, groups.size()) ||
-        grow(h, &w->d_items, &w->cap_items, items.size()) || grow(h, &w->d_counts, &w->cap_counts, entries) ||
-        grow(h, &w->d_pos, &w->cap_pos, entries) || grow(h, &w->d_spans, &w->cap_spans, spans.size()) ||
-        grow(h, &w->d_total, &w->cap_total, spans.size()) ||
+    if ((!cals.empty() && grow(h, &w->d_cals, &w->cap_cals, cals.size())) || grow(h, &w->d_jobs, &w->cap_jobs, jobs.size() * sizeof(Job)) ||
+        grow(h, &w->d_frames, &w->cap_frames, groups.size()) || grow(h, &w->d_items, &w->cap_items, items.size()) ||
+        grow(h, &w->d_counts, &w->cap_counts, entries) || grow(h, &w->d_pos, &w->cap_pos, entries) ||
+        grow(h, &w->d_spans, &w->cap_spans, spans.size()) || grow(h, &w->d_total, &w->cap_total, spans.size()) ||
         grow(h, &w->d_offsets, &w->cap_off, off.size()))
       return 1;
-    HIP_TRY(h, hipMemcpyAsync(*d_jobs, jobs.data(), jobs.size() * sizeof(Job), hipMemcpyHostToDevice, h->stream));
+    const typename C::Cal* d_cals = cals.empty() ? nullptr : w->d_cals;
+    const Job* d_jobs = reinterpret_cast<const Job*>(w->d_jobs);   // an allocation's base: aligned for either kind
+    HIP_TRY(h, hipMemcpyAsync(w->d_jobs, jobs.data(), jobs.size() * sizeof(Job), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(w->d_frames, groups.data(), groups.size() * sizeof(CropFrame), hipMemcpyHostToDevice, h->stream));
     if (!items.empty()) HIP_TRY(h, hipMemcpyAsync(w->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(w->d_spans, spans.data(), spans.size() * sizeof(JobSpan), hipMemcpyHostToDevice, h->stream));
     if (!items.empty()) {
       alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_TEST);
-      test((unsigned)items.size());
+      // with the other tables: the stream is synchronised before the caller's `cals` goes (an error of the copy is the next hipGetLastError's)
+      if (d_cals) (void)hipMemcpyAsync(w->d_cals, cals.data(), cals.size() * sizeof(FrustumCal), hipMemcpyHostToDevice, h->stream);
+      launch_test<C>(h, w, (unsigned)items.size(), d_jobs, d_cals);
     }
     {
       alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_COMPACT);
@@ -494,7 +455,7 @@ int run_extract(alignnet_handle* h, const std::string& name, const int32_t* fram
       if (grow(h, &w->d_next[k], &w->cap_next[k], (size_t)off[(size_t)B * 2 + k] * 3)) return 1;
     if (!items.empty() && off[(size_t)B * 2] + off[(size_t)B * 2 + 1] > 0) {
       alignnet::ProfScope prof_scope(h, alignnet::PK_TRACKLET_COMPACT);
-      scatter((unsigned)items.size());
+      launch_scatter<C>(h, w, (unsigned)items.size(), d_jobs, d_cals);
     }
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -524,7 +485,7 @@ extern "C" void alignnet_tracklet_free(alignnet_handle* h)
   if (!h || !h->tracklet_ws) return;
   TrackletWS* w = tws(h);
   if (h->stream) hipStreamSynchronize(h->stream);
-  void* const ptrs[] = {w->d_scans, w->d_jobs, w->d_fjobs, w->d_cals, w->d_frames, w->d_items, w->d_counts, w->d_pos, w->d_spans, w->d_total, w->d_offsets,
+  void* const ptrs[] = {w->d_scans, w->d_jobs, w->d_cals, w->d_frames, w->d_items, w->d_counts, w->d_pos, w->d_spans, w->d_total, w->d_offsets,
                         w->d_pts[0], w->d_pts[1], w->d_next[0], w->d_next[1]};
   for (void* p : ptrs) if (p) hipFree(p);
   delete w;
@@ -563,20 +524,14 @@ extern "C" int alignnet_tracklet_extract(alignnet_handle* h, const int32_t* fram
 {
   if (!h) return 1;
   const std::string name("alignnet_tracklet_extract");
-  if (!h->tracklet_ws || tws(h)->F < 0) return fail(h, name + ": no scans uploaded");
-  if (B < 0 || B > (1 << 24)) return fail(h, name + ": B out of range");
-  if (B > 0 && (!frames || !boxes || !dz)) return fail(h, name + ": null argument");
-  TrackletWS* w = tws(h);
-  const int J = 2 * B;
-  for (int j = 0; j < J; ++j) {
-    const std::string where = " (pair " + std::to_string(j / 2) + ", cloud " + std::to_string(j % 2 + 1) + ")";
-    if (frames[j] < 0 || frames[j] >= w->F) return fail(h, name + ": frame " + std::to_string(frames[j]) + " out of range" + where);
-    for (int k = 0; k < 7; ++k) if (!std::isfinite(boxes[(size_t)j * 7 + k])) return fail(h, name + ": non-finite box value" + where);
-    for (int k = 3; k < 6; ++k) if (boxes[(size_t)j * 7 + k] < 0.0) return fail(h, name + ": negative box extent" + where);
-    if (!std::isfinite(dz[j])) return fail(h, name + ": non-finite dz" + where);
-  }
-  return run_extract(
-      h, name, frames, dz, B, &w->d_jobs, &w->cap_jobs,
+  return run_extract<BoxCrop>(
+      h, name, frames, dz, B, std::vector<FrustumCal>(),
+      [&](int) { return B > 0 && (!frames || !boxes || !dz) ? fail(h, name + ": null argument") : 0; },
+      [&](int j) {
+        for (int k = 0; k < 7; ++k) if (!std::isfinite(boxes[(size_t)j * 7 + k])) return fail(h, name + ": non-finite box value" + job_where(j));
+        for (int k = 3; k < 6; ++k) if (boxes[(size_t)j * 7 + k] < 0.0) return fail(h, name + ": negative box extent" + job_where(j));
+        return 0;
+      },
       [&](CropJob& c, int j) {
         const double* b = boxes + (size_t)j * 7;
         c.bx = b[0]; c.by = b[1]; c.bz = b[2];
@@ -587,20 +542,6 @@ extern "C" int alignnet_tracklet_extract(alignnet_handle* h, const int32_t* fram
         c.txz = pre_bound(rxz, std::max(std::fabs(b[0]), std::fabs(b[2])));
         c.ty = pre_bound(c.h, b[1]);
       },
-      [&](unsigned items) {
-        if (w->stride == 4)
-          hipLaunchKernelGGL(tracklet_test_kernel<4>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs, w->d_counts);
-        else
-          hipLaunchKernelGGL(tracklet_test_kernel<3>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs, w->d_counts);
-      },
-      [&](unsigned items) {
-        if (w->stride == 4)
-          hipLaunchKernelGGL(tracklet_scatter_kernel<4>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs,
-                             w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
-        else
-          hipLaunchKernelGGL(tracklet_scatter_kernel<3>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_jobs,
-                             w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
-      },
       offsets);
 }
 
@@ -609,58 +550,37 @@ extern "C" int alignnet_tracklet_extract_frustum(alignnet_handle* h, const int32
 {
   if (!h) return 1;
   const std::string name("alignnet_tracklet_extract_frustum");
-  if (!h->tracklet_ws || tws(h)->F < 0) return fail(h, name + ": no scans uploaded");
-  if (B < 0 || B > (1 << 24)) return fail(h, name + ": B out of range");
-  TrackletWS* w = tws(h);
-  if ((B > 0 && (!frames || !rects || !dz)) || (w->F > 0 && (!proj || !image))) return fail(h, name + ": null argument");
-  if (!std::isfinite(clip)) return fail(h, name + ": non-finite clip");
-  for (int f = 0; f < w->F; ++f) {
-    const std::string where = " (frame " + std::to_string(f) + ")";
-    for (int k = 0; k < 12; ++k) if (!std::isfinite(proj[(size_t)f * 12 + k])) return fail(h, name + ": non-finite proj value" + where);
-    for (int k = 0; k < 2; ++k) {
-      if (!std::isfinite(image[(size_t)f * 2 + k])) return fail(h, name + ": non-finite image size" + where);
-      if (image[(size_t)f * 2 + k] <= 0.0) return fail(h, name + ": image size <= 0" + where);
-    }
-  }
-  const int J = 2 * B;
-  for (int j = 0; j < J; ++j) {
-    const std::string where = " (pair " + std::to_string(j / 2) + ", cloud " + std::to_string(j % 2 + 1) + ")";
-    if (frames[j] < 0 || frames[j] >= w->F) return fail(h, name + ": frame " + std::to_string(frames[j]) + " out of range" + where);
-    for (int k = 0; k < 4; ++k) if (!std::isfinite(rects[(size_t)j * 4 + k])) return fail(h, name + ": non-finite rect value" + where);
-    if (!std::isfinite(dz[j])) return fail(h, name + ": non-finite dz" + where);
-  }
   std::vector<FrustumCal> cals;   // lives until run_extract has synchronised the stream
-  if (J > 0) {
-    // the calibration of every uploaded frame (120 bytes each), indexed by CropFrame::frame
-    cals.resize(w->F);
-    for (int f = 0; f < w->F; ++f) {
-      std::copy(proj + (size_t)f * 12, proj + (size_t)f * 12 + 12, cals[f].m);
-      cals[f].W = image[(size_t)f * 2]; cals[f].H = image[(size_t)f * 2 + 1]; cals[f].clip = clip;
-    }
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (grow(h, &w->d_cals, &w->cap_cals, cals.size())) return 1;
-  }
-  return run_extract(
-      h, name, frames, dz, B, &w->d_fjobs, &w->cap_fjobs,
+  return run_extract<FrustumCrop>(
+      h, name, frames, dz, B, cals,
+      [&](int F) {
+        if ((B > 0 && (!frames || !rects || !dz)) || (F > 0 && (!proj || !image))) return fail(h, name + ": null argument");
+        if (!std::isfinite(clip)) return fail(h, name + ": non-finite clip");
+        for (int f = 0; f < F; ++f) {
+          const std::string where = " (frame " + std::to_string(f) + ")";
+          for (int k = 0; k < 12; ++k) if (!std::isfinite(proj[(size_t)f * 12 + k])) return fail(h, name + ": non-finite proj value" + where);
+          for (int k = 0; k < 2; ++k) {
+            if (!std::isfinite(image[(size_t)f * 2 + k])) return fail(h, name + ": non-finite image size" + where);
+            if (image[(size_t)f * 2 + k] <= 0.0) return fail(h, name + ": image size <= 0" + where);
+          }
+        }
+        if (B > 0) {
+          // the calibration of every uploaded frame (120 bytes each), indexed by CropFrame::frame
+          cals.resize(F);
+          for (int f = 0; f < F; ++f) {
+            std::copy(proj + (size_t)f * 12, proj + (size_t)f * 12 + 12, cals[f].m);
+            cals[f].W = image[(size_t)f * 2]; cals[f].H = image[(size_t)f * 2 + 1]; cals[f].clip = clip;
+          }
+        }
+        return 0;
+      },
+      [&](int j) {
+        for (int k = 0; k < 4; ++k) if (!std::isfinite(rects[(size_t)j * 4 + k])) return fail(h, name + ": non-finite rect value" + job_where(j));
+        return 0;
+      },
       [&](FrustumJob& c, int j) {
         const double* r = rects + (size_t)j * 4;
         c.xmin = r[0]; c.ymin = r[1]; c.xmax = r[2]; c.ymax = r[3]; c.pad = 0;
-      },
-      [&](unsigned items) {
-        // with the other tables: the stream is synchronised before `cals` goes (an error of the copy is the next hipGetLastError's)
-        (void)hipMemcpyAsync(w->d_cals, cals.data(), cals.size() * sizeof(FrustumCal), hipMemcpyHostToDevice, h->stream);
-        if (w->stride == 4)
-          hipLaunchKernelGGL(frustum_test_kernel<4>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_fjobs, w->d_cals, w->d_counts);
-        else
-          hipLaunchKernelGGL(frustum_test_kernel<3>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_fjobs, w->d_cals, w->d_counts);
-      },
-      [&](unsigned items) {
-        if (w->stride == 4)
-          hipLaunchKernelGGL(frustum_scatter_kernel<4>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_fjobs, w->d_cals,
-                             w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
-        else
-          hipLaunchKernelGGL(frustum_scatter_kernel<3>, dim3(items), dim3(kThreads), 0, h->stream, w->d_scans, w->d_frames, w->d_items, w->d_fjobs, w->d_cals,
-                             w->d_counts, w->d_pos, w->d_offsets, w->d_next[0], w->d_next[1]);
       },
       offsets);
 }

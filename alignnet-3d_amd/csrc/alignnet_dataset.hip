@@ -10,6 +10,7 @@
 // straight into the buffers the forward / training step reads.  The random stream is a counter hash of
 // (seed, example row, tower, point): reproducible, independent of the batch composition, NOT np.random's.
 #include "engine.h"
+#include "host_util.h"
 #include <cstdio>
 
 namespace {
@@ -26,14 +27,6 @@ struct DatasetWS {
   int* d_rows = nullptr;
   float* d_out[8] = {};
 };
-
-int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1; }
-
-#define HIP_TRY(h, expr)                                                                         \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return fail(h, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
 
 DatasetWS* dws(alignnet_handle* h) { return static_cast<DatasetWS*>(h->dataset_ws); }
 

@@ -24,19 +24,12 @@
 // Fast global registration (FGR, the reference's `o3_gicp_fast`, icp.py:121-143; DEFINED by tests/fgr_ref.py) shares stages 1-5 and the grid:
 // section 8 below (gr_match_kernel<true>, fgr_tuple_kernel, fgr_optimise_kernel, fgr_score_kernel) and alignnet_fgr_register*.
 #include "engine.h"
+#include "host_util.h"
 #include "icp_estimate.h"
 #include <cmath>
 #include <vector>
 
 namespace {
-
-int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1; }
-
-#define HIP_TRY(h, expr)                                                                         \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return fail(h, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
 
 constexpr int kThreads = 1024, kWaves = kThreads / 64;
 constexpr double kVoxel = 0.05;
@@ -1183,11 +1176,7 @@ int run_global(alignnet_handle* h, const std::string& name, const float* d_p0, c
   const size_t per_pair = carve(a, nullptr, 1, cap, P2);
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, kWsBudget / per_pair));
   const size_t need = carve(a, nullptr, chunk, cap, P2) + align_up((size_t)chunk * 8);
-  if (h->globalreg_ws_bytes < need) {
-    if (h->globalreg_ws) { HIP_TRY(h, hipStreamSynchronize(h->stream)); hipFree(h->globalreg_ws); h->globalreg_ws = nullptr; h->globalreg_ws_bytes = 0; }
-    HIP_TRY(h, hipMalloc(&h->globalreg_ws, need));
-    h->globalreg_ws_bytes = need;
-  }
+  if (grow_bytes(h, &h->globalreg_ws, &h->globalreg_ws_bytes, need)) return 1;
   const size_t used = carve(a, static_cast<char*>(h->globalreg_ws), chunk, cap, P2);
   int* d_ids = reinterpret_cast<int*>(static_cast<char*>(h->globalreg_ws) + used);   // [chunk] rows | [chunk] streams
   a.pts[0] = d_p0; a.pts[1] = d_p1; a.off = d_off;
@@ -1265,26 +1254,11 @@ int global_host(alignnet_handle* h, const char* fn, const float* points1, const 
   const std::string name(fn);
   bool full = false;
   if (gr_flags(h, name, flags, &full)) return 1;
-  if (!offsets || B < 1) return fail(h, name + ": null offsets or B < 1");
-  HIP_TRY(h, hipSetDevice(h->cfg.device));
-  std::vector<long long> n1(B), n2(B);
-  for (int i = 0; i < B; ++i) {
-    n1[i] = offsets[(i + 1) * 2] - offsets[i * 2]; n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1];
-    if (n1[i] < 0 || n2[i] < 0) return fail(h, name + ": offsets must be non-decreasing");
-  }
-  const size_t t0 = (size_t)offsets[B * 2], t1 = (size_t)offsets[B * 2 + 1];
-  if ((t0 && !points1) || (t1 && !points2)) return fail(h, name + ": null point blob");
-  float *d0 = nullptr, *d1 = nullptr; long long* doff = nullptr;
-  HIP_TRY(h, hipMalloc(&d0, std::max<size_t>(t0, 1) * 3 * sizeof(float)));
-  HIP_TRY(h, hipMalloc(&d1, std::max<size_t>(t1, 1) * 3 * sizeof(float)));
-  HIP_TRY(h, hipMalloc(&doff, (size_t)(B + 1) * 2 * sizeof(long long)));
-  if (t0) HIP_TRY(h, hipMemcpyAsync(d0, points1, t0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (t1) HIP_TRY(h, hipMemcpyAsync(d1, points2, t1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(doff, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  const int rc = run_global(h, name, d0, d1, doff, nullptr, n1, n2, B, full, seed, streams, max_iteration, max_validation, out_T, out_fit, out_rmse,
-                            out_iters, out_vals, dbg);
-  hipStreamSynchronize(h->stream);
-  hipFree(d0); hipFree(d1); hipFree(doff);
+  PairUpload u;
+  if (upload_pairs(h, name, points1, points2, offsets, B, &u)) return 1;
+  const int rc = run_global(h, name, u.pts[0].p, u.pts[1].p, u.off.p, nullptr, u.n1, u.n2, B, full, seed, streams, max_iteration,
+                            max_validation, out_T, out_fit, out_rmse, out_iters, out_vals, dbg);
+  hipStreamSynchronize(h->stream);   // before the uploaded clouds go
   return rc;
 }
 
@@ -1352,11 +1326,7 @@ int run_fgr(alignnet_handle* h, const std::string& name, const float* d_p0, cons
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, kWsBudget / per_pair));
   const size_t shared_bytes = carve(a, nullptr, chunk, cap, P2);
   const size_t need = shared_bytes + carve_fgr(a, f, nullptr, chunk, cap, p.max_tuples, trace_its) + align_up((size_t)chunk * 8);
-  if (h->globalreg_ws_bytes < need) {
-    if (h->globalreg_ws) { HIP_TRY(h, hipStreamSynchronize(h->stream)); hipFree(h->globalreg_ws); h->globalreg_ws = nullptr; h->globalreg_ws_bytes = 0; }
-    HIP_TRY(h, hipMalloc(&h->globalreg_ws, need));
-    h->globalreg_ws_bytes = need;
-  }
+  if (grow_bytes(h, &h->globalreg_ws, &h->globalreg_ws_bytes, need)) return 1;
   char* ws = static_cast<char*>(h->globalreg_ws);
   carve(a, ws, chunk, cap, P2);
   const size_t used = shared_bytes + carve_fgr(a, f, ws + shared_bytes, chunk, cap, p.max_tuples, trace_its);
@@ -1437,25 +1407,10 @@ int run_fgr(alignnet_handle* h, const std::string& name, const float* d_p0, cons
 int fgr_host(alignnet_handle* h, const std::string& name, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
              const FgrParams& p, double* out_T, double* out_fit, double* out_rmse, int32_t* out_corr, int64_t* out_trials, const FgrDebugOut* dbg)
 {
-  if (!offsets || B < 1) return fail(h, name + ": null offsets or B < 1");
-  HIP_TRY(h, hipSetDevice(h->cfg.device));
-  std::vector<long long> n1(B), n2(B);
-  for (int i = 0; i < B; ++i) {
-    n1[i] = offsets[(i + 1) * 2] - offsets[i * 2]; n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1];
-    if (n1[i] < 0 || n2[i] < 0) return fail(h, name + ": offsets must be non-decreasing");
-  }
-  const size_t t0 = (size_t)offsets[B * 2], t1 = (size_t)offsets[B * 2 + 1];
-  if ((t0 && !points1) || (t1 && !points2)) return fail(h, name + ": null point blob");
-  float *d0 = nullptr, *d1 = nullptr; long long* doff = nullptr;
-  HIP_TRY(h, hipMalloc(&d0, std::max<size_t>(t0, 1) * 3 * sizeof(float)));
-  HIP_TRY(h, hipMalloc(&d1, std::max<size_t>(t1, 1) * 3 * sizeof(float)));
-  HIP_TRY(h, hipMalloc(&doff, (size_t)(B + 1) * 2 * sizeof(long long)));
-  if (t0) HIP_TRY(h, hipMemcpyAsync(d0, points1, t0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (t1) HIP_TRY(h, hipMemcpyAsync(d1, points2, t1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(doff, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  const int rc = run_fgr(h, name, d0, d1, doff, nullptr, n1, n2, B, p, out_T, out_fit, out_rmse, out_corr, out_trials, dbg);
-  hipStreamSynchronize(h->stream);
-  hipFree(d0); hipFree(d1); hipFree(doff);
+  PairUpload u;
+  if (upload_pairs(h, name, points1, points2, offsets, B, &u)) return 1;
+  const int rc = run_fgr(h, name, u.pts[0].p, u.pts[1].p, u.off.p, nullptr, u.n1, u.n2, B, p, out_T, out_fit, out_rmse, out_corr, out_trials, dbg);
+  hipStreamSynchronize(h->stream);   // before the uploaded clouds go
   return rc;
 }
 

@@ -29,6 +29,7 @@
 // ICP baseline evaluation mode (icp.py:150-213): the same scan, 17 sums instead of 10 (count, sum a, sum b, the nine entries of sum b a^T, sum of
 // distances, all about the same pivot), then the 3x3 Umeyama rotation in fp64 on one lane (icp_umeyama_rotation: one-sided Jacobi SVD).
 #include "engine.h"
+#include "host_util.h"
 #include "icp_estimate.h"
 #include <algorithm>
 #include <cmath>
@@ -36,14 +37,6 @@
 #include <vector>
 
 namespace {
-
-int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1; }
-
-#define HIP_TRY(h, expr)                                                                         \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return fail(h, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
 
 constexpr int kIcpThreads = 1024, kIcpSums = 12, kIcpSplit = 4;   // threads per pair; sums of the z-constrained estimate; lanes per source point
 constexpr int kIcpSumsFull = 19;     // sums of the full-rotation estimate: count, a (3), b (3), b a^T (9), distance, |a|^2, |b|^2
@@ -502,44 +495,20 @@ Args icp_args_from(const Args& a, int lo)   // the arguments of pairs lo.. as a 
   return r;
 }
 
-// a device allocation of one call: freed on every way out of it
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n * sizeof(T)); }
-};
-
 // the clouds of a call as the kernels address them, with whatever this call uploaded of them (the dataset's tables stay the handle's)
 struct IcpClouds {
   const float* pts[2] = {nullptr, nullptr}; const long long* off = nullptr; const int* rows = nullptr;
   std::vector<long long> n2;   // the target sizes of the B pairs as the host knows them
-  DevBuf<float> up_pts[2]; DevBuf<long long> up_off; DevBuf<int> up_rows;
+  PairUpload up; DevBuf<int> up_rows;
 };
 
 // clouds passed from the host (alignnet_icp_refine / _register / _plane_register and the read-backs); `name` is the entry point's in the messages
 int stage_host(alignnet_handle* h, const std::string& name, const float* points1, const float* points2, const int64_t* offsets, int32_t B, IcpClouds* c)
 {
   if (!h) return 1;
-  if (!offsets || B < 1) return fail(h, name + ": null offsets or B < 1");
-  HIP_TRY(h, hipSetDevice(h->cfg.device));
-  c->n2.resize(B);
-  for (int i = 0; i < B; ++i) {
-    if (offsets[(i + 1) * 2] < offsets[i * 2] || offsets[(i + 1) * 2 + 1] < offsets[i * 2 + 1]) return fail(h, name + ": offsets must be non-decreasing");
-    c->n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1];
-  }
-  const size_t n0 = (size_t)offsets[B * 2], n1 = (size_t)offsets[B * 2 + 1];
-  if ((n0 && !points1) || (n1 && !points2)) return fail(h, name + ": null point blob");
-  HIP_TRY(h, c->up_pts[0].alloc(std::max<size_t>(n0, 1) * 3));
-  HIP_TRY(h, c->up_pts[1].alloc(std::max<size_t>(n1, 1) * 3));
-  HIP_TRY(h, c->up_off.alloc((size_t)(B + 1) * 2));
-  if (n0) HIP_TRY(h, hipMemcpyAsync(c->up_pts[0].p, points1, n0 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (n1) HIP_TRY(h, hipMemcpyAsync(c->up_pts[1].p, points2, n1 * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(c->up_off.p, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  c->pts[0] = c->up_pts[0].p; c->pts[1] = c->up_pts[1].p; c->off = c->up_off.p;
+  if (upload_pairs(h, name, points1, points2, offsets, B, &c->up)) return 1;
+  c->n2.swap(c->up.n2);
+  c->pts[0] = c->up.pts[0].p; c->pts[1] = c->up.pts[1].p; c->off = c->up.off.p;
   return 0;
 }
 
@@ -589,11 +558,7 @@ struct IcpResults {
 // the handle's workspace, grown to `need` bytes (the chunks of a call carve it in stream order)
 int reserve_grid_ws(alignnet_handle* h, size_t need)
 {
-  if (h->icp_grid_ws_bytes < need) {
-    if (h->icp_grid_ws) { HIP_TRY(h, hipStreamSynchronize(h->stream)); hipFree(h->icp_grid_ws); h->icp_grid_ws = nullptr; h->icp_grid_ws_bytes = 0; }
-    HIP_TRY(h, hipMalloc(&h->icp_grid_ws, need));
-    h->icp_grid_ws_bytes = need;
-  }
+  if (grow_bytes(h, &h->icp_grid_ws, &h->icp_grid_ws_bytes, need)) return 1;
   h->icp_grid_ws_used = need;
   return 0;
 }

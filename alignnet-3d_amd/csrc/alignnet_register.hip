@@ -9,19 +9,12 @@
 // they do), so a steady-state call allocates nothing.  The two kernels here are a few hundred flops per pair; what matters is that they are two
 // launches between two latency-critical stages and that their fp64 arithmetic is NumPy's to the last bit (no contraction).
 #include "engine.h"
+#include "host_util.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 namespace {
-
-int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1; }
-
-#define HIP_TRY(h, expr)                                                                         \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return fail(h, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
 
 struct RegisterWS {
   int cap = 0;                       // pairs the buffers below hold

@@ -60,20 +60,13 @@
 //     scene_scatter_kernel (per (cloud, row): columns in ascending COLUMN order -- a wrapped window starts at column 0 -- ballot prefix, location = t d in
 //     fp64 rounded to float, + noise).  Counts, a scan, a scatter: no atomics that could reorder points.
 #include "engine.h"
+#include "host_util.h"
 #include <cmath>
 #include <cstring>
 #include <limits>
 #include <vector>
 
 namespace {
-
-int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1; }
-
-#define HIP_TRY(h, expr)                                                                         \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) return fail(h, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
 
 constexpr int kRows = 64, kCols = 4500, kRays = kRows * kCols;
 constexpr int kTileCols = 8, kCastThreads = 256, kColsPerWave = kTileCols / (kCastThreads / 64);
@@ -926,18 +919,6 @@ struct SceneWS {
 };
 
 SceneWS* sws(alignnet_handle* h) { return static_cast<SceneWS*>(h->scene_ws); }
-
-template <typename T>
-int grow(alignnet_handle* h, T** p, size_t* cap, size_t need)
-{
-  if (need <= *cap && *p) return 0;
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  if (*p) hipFree(*p);
-  *p = nullptr; *cap = 0;
-  HIP_TRY(h, hipMalloc(p, std::max<size_t>(need, 1) * sizeof(T)));
-  *cap = std::max<size_t>(need, 1);
-  return 0;
-}
 
 void default_sensor(std::vector<double>& dir)
 {

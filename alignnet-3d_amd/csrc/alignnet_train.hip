@@ -1,6 +1,7 @@
 // Training side of the C ABI (include/alignnet_hip.h): the train-mode sess.run of the reference
 // (train.py:368) = forward with batch statistics + loss + backward + optimiser + EMA + step++.
 #include "engine.h"
+#include "host_util.h"
 #include "kernels_train_fwd.h"
 #include "kernels_train_fwd_wide.h"
 #include "kernels_train_head.h"
@@ -17,17 +18,6 @@
 #include <dlfcn.h>
 
 using namespace alignnet;
-
-#define HIP_TRY(h, expr)                                                                         \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess) {                                                                      \
-      (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                              \
-      return 1;                                                                                  \
-    }                                                                                            \
-  } while (0)
-
-static int fail(const alignnet_handle* h, const std::string& m) { h->err = m; return 1; }
 
 // sync_bn (alignnet_set_option): every batch sum behind a BatchNorm -- forward moments, backward (dbeta, dgamma) totals, the Gram /
 // column-sum matrices the layer identities use -- is added over the data-parallel ranks between the kernel that forms this rank's

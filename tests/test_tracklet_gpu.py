@@ -120,6 +120,9 @@ def _edge_case(eng):
     while 2 * len(boxes) < per_pass + 1:   # more jobs on frame 0 than one LDS pass stages
         b = C.draw_box(g); b[:3] = box[:3] + g.uniform(-1.5, 1.5, 3)
         boxes.append([b, box + [0, 0, 0, 0, 0, 0, g.uniform(-3, 3)]]); frames.append([0, 0])
+    k = 0
+    while sum(f.count(0) for f in frames) < 2 * per_pass + 1:   # ... and more than the 64 whose counts the scatter reads at once: the first pairs again
+        boxes.append(boxes[k]); frames.append(frames[k]); k += 1
     dz = np.zeros((len(boxes), 2), np.float32); dz[:, 1] = g.uniform(-0.3, 0.3, len(boxes))
     return dict(scans=[C.pad_stride(scan, 4, g), C.pad_stride(other, 4, g), C.pad_stride(third, 4, g)], frames=np.array(frames, np.int32),
                 boxes=np.array(boxes), dz=dz)
@@ -127,9 +130,10 @@ def _edge_case(eng):
 
 def test_job_list_edges(eng):
     case = _edge_case(eng)
-    assert 2 * len(case["frames"]) >= eng.get_option("tracklet_jobs_per_pass") + 1 and (case["frames"] == 0).sum() >= eng.get_option("tracklet_jobs_per_pass") + 1
+    assert 2 * len(case["frames"]) >= eng.get_option("tracklet_jobs_per_pass") + 1 and (case["frames"] == 0).sum() >= 2 * eng.get_option("tracklet_jobs_per_pass") + 1
     off, p1, p2 = _check(eng, case, "job-list edges", exact=True)   # the zero-extent box ON a point: gap == 0, decided by exact arithmetic
     n = np.diff(off, axis=0)
+    assert n.reshape(-1)[np.flatnonzero(case["frames"].reshape(-1) == 0)[64:]].all()   # frame 0's jobs past the 64th (they are in job order) are not empty
     scan = case["scans"][0]
     assert n[0, 0] == n[0, 1] > 20                                   # the same box twice
     assert np.array_equal(_bits(p1[off[0, 0]:off[1, 0]]), _bits(p1[off[1, 0]:off[2, 0]]))

@@ -15,7 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, 'tools'), os.path.join(ROOT, 'alignnet-3d_amd'), ROOT):
     sys.path.insert(0, p)
 from tracklet_rate import COPY_PEAK, STAGES, make_frames, med, pair_args  # noqa: E402
-KERNELS = ("frustum_test_kernelILi4", "frustum_test_kernelILi3", "frustum_scatter_kernelILi4", "frustum_scatter_kernelILi3")
+KERNELS = ("crop_test_kernelINS_11FrustumCropELi4", "crop_test_kernelINS_11FrustumCropELi3", "crop_scatter_kernelINS_11FrustumCropELi4",
+           "crop_scatter_kernelINS_11FrustumCropELi3")
 
 
 def resources():

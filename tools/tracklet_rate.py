@@ -55,8 +55,8 @@ def resources():
     for line in open(path):
         m = re.search(r"Function Name: (\S+)", line)
         if m:
-            name = next((k for k in ("tracklet_test_kernelILi4", "tracklet_test_kernelILi3", "tracklet_scan_kernel", "tracklet_scatter_kernelILi4",
-                                     "tracklet_scatter_kernelILi3") if k in m.group(1)), None)
+            name = next((k for k in ("crop_test_kernelINS_7BoxCropELi4", "crop_test_kernelINS_7BoxCropELi3", "tracklet_scan_kernel",
+                                     "crop_scatter_kernelINS_7BoxCropELi4", "crop_scatter_kernelINS_7BoxCropELi3") if k in m.group(1)), None)
             if name:
                 out[name] = {}
             continue
