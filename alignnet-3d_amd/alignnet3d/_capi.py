@@ -67,6 +67,15 @@ class RegisterOutputs(C.Structure):
                 ("loss", FP)]
 
 
+class GoicpParams(C.Structure):
+    _fields_ = [("yaw_half", C.c_double), ("t_half", C.c_double * 3), ("yaw_res", C.c_double), ("t_res", C.c_double), ("trunc", C.c_double),
+                ("mse_thresh", C.c_double), ("start_radius", C.c_double), ("fitness_radius", C.c_double), ("max_source", C.c_int32), ("max_target", C.c_int32),
+                ("max_frontier", C.c_int32), ("max_levels", C.c_int32), ("starts", C.c_int32), ("start_its", C.c_int32),
+                ("stage_points", C.c_int32), ("flags", C.c_int32)]
+
+
+GOICP_MAX_LEVELS = 24
+
 H = C.c_void_p
 
 # every symbol include/alignnet_hip.h declares: name -> (restype, argtypes)
@@ -159,6 +168,12 @@ SYMBOLS = {
                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "alignnet_goicp_register": (C.c_int, [H, FP, FP, C.POINTER(C.c_int64), C.c_int32, C.POINTER(GoicpParams), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "alignnet_goicp_register_dataset": (C.c_int, [H, C.POINTER(C.c_int32), C.c_int32, C.POINTER(GoicpParams), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "alignnet_debug_goicp_nodes": (C.c_int, [H, FP, C.c_int64, FP, C.c_int64, C.POINTER(GoicpParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "alignnet_scene_set_sensor": (C.c_int, [H, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "alignnet_scene_upload_meshes": (C.c_int, [H, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32]),
     "alignnet_scene_free_meshes": (C.c_int, [H]),
@@ -187,7 +202,8 @@ SYMBOLS = {
 }
 
 # symbols added after ABI version 1 was fixed: an earlier build named by ALIGNNET_HIP_LIB loads without them
-LATE_SYMBOLS = ("alignnet_register", "alignnet_register_dataset", "alignnet_tracklet_extract_frustum")
+LATE_SYMBOLS = ("alignnet_register", "alignnet_register_dataset", "alignnet_tracklet_extract_frustum", "alignnet_goicp_register",
+                "alignnet_goicp_register_dataset")
 
 _lib = None
 
@@ -215,8 +231,8 @@ def load_library():
             # an A/B build of an EARLIER revision (ALIGNNET_HIP_LIB, tools/ab_build.sh) may predate a test hook; the in-tree library must export everything
             if os.environ.get("ALIGNNET_HIP_LIB") and name.startswith("alignnet_debug_"):
                 continue
-            # likewise the one-call registration and the frustum crop, added without moving ABI_VERSION: Engine.register* and
-            # Engine.tracklet_extract_frustum report their absence (EngineError)
+            # likewise the one-call registration, the frustum crop and the Go-ICP registration, added without moving ABI_VERSION: Engine.register* and
+            # Engine.tracklet_extract_frustum / Engine.goicp_register* report their absence (EngineError)
             if os.environ.get("ALIGNNET_HIP_LIB") and name in LATE_SYMBOLS:
                 continue
             raise

@@ -690,6 +690,97 @@ class Engine:
             out[name] = [arr[k, : counts[k]].copy() for k in range(2)]
         return out
 
+    # ---- Go-ICP: branch-and-bound over yaw and a translation box (csrc/alignnet_goicp.hip; semantics: tests/goicp_ref.py) ----
+    GOICP_STATUS = ("CERTIFIED", "RESOLUTION", "OVERFLOW", "LEVELS", "EMPTY")
+    GOICP_DEFAULTS = dict(yaw_half=np.pi, t_half=(2.0, 2.0, 0.25), yaw_res=np.pi / 256, t_res=0.02, trunc=0.5, mse_thresh=1e-4, max_source=256,
+                          max_target=2048, max_frontier=1 << 18, max_levels=_capi.GOICP_MAX_LEVELS, starts=8, start_radius=0.5, start_its=30,
+                          fitness_radius=0.10, stage_points=0)
+    GOICP_REFINE_RADIUS, GOICP_REFINE_ITS = 0.10, 30   # icp.py:188-189: refine_radius=0.10; the ICP calls' 30 iterations
+
+    @classmethod
+    def _goicp_params(cls, constrained, refine, kw):
+        if not constrained:
+            raise NotImplementedError("goicp searches yaw and translation only (with_constraint=True): there is no full-rotation form")
+        if refine not in (None, "p2p"):
+            raise ValueError("goicp: refine must be None or 'p2p', got %r" % (refine,))
+        unknown = sorted(set(kw) - set(cls.GOICP_DEFAULTS))
+        if unknown:
+            raise TypeError("goicp: unknown parameters %s" % ", ".join(unknown))
+        v = dict(cls.GOICP_DEFAULTS, **kw)
+        p = _capi.GoicpParams()
+        p.yaw_half, p.yaw_res, p.t_res, p.trunc, p.mse_thresh, p.start_radius = (float(v[k]) for k in ("yaw_half", "yaw_res", "t_res", "trunc", "mse_thresh",
+                                                                                                        "start_radius"))
+        p.fitness_radius = float(v["fitness_radius"])
+        th = [float(x) for x in v["t_half"]]
+        if len(th) != 3:
+            raise ValueError("goicp: t_half has three entries")
+        for k in range(3):
+            p.t_half[k] = th[k]
+        for k in ("max_source", "max_target", "max_frontier", "max_levels", "starts", "start_its", "stage_points"):
+            setattr(p, k, int(v[k]))
+        p.flags = 0
+        return p
+
+    @staticmethod
+    def _goicp_bufs(B):
+        L = _capi.GOICP_MAX_LEVELS
+        out, err, low, fit = np.empty((B, 16), np.float64), np.empty(B, np.float64), np.empty(B, np.float64), np.empty(B, np.float64)
+        st, ev, sv = np.empty(B, np.int32), np.empty((B, L), np.int32), np.empty((B, L), np.int32)
+        dp, ip = (lambda a: a.ctypes.data_as(C.POINTER(C.c_double))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)))
+        tail = (dp(out), dp(err), dp(low), dp(fit), ip(st), ip(ev), ip(sv))
+        return tail, lambda: dict(transforms=out.reshape(B, 4, 4), error=err, lower_bound=low, fitness=fit, status=st, evaluated=ev, survived=sv)
+
+    def goicp_register(self, sources, targets, constrained=True, refine=None, **params):
+        """Branch-and-bound registration over yaw and a translation box (the reference's `goicp`, which it leaves unimplemented): the pose
+        with the lowest truncated nearest-neighbour error E on subsampled working sets, independent of any start, with a certificate.
+        sources / targets: lists of [n, 3] arrays; params: GOICP_DEFAULTS keys.  Returns dict(transforms [B, 4, 4] about the origin, error,
+        lower_bound (no pose of the domain has a smaller E), fitness (share of the source working set within
+        fitness_radius of a target at the returned pose), status (index into GOICP_STATUS), evaluated / survived [B, 24] nodes per
+        level).  refine="p2p": icp_refine on the FULL clouds (radius 0.10, 30 iterations) from the search's pose follows; `transforms` is
+        then the refined estimate, `search_transforms` the search's, and fitness / rmse / iterations are the refinement's.
+        constrained=False raises NotImplementedError before anything reaches the device."""
+        p = self._goicp_params(constrained, refine, params)
+        fn = self._register_fn("alignnet_goicp_register")
+        B = len(sources)
+        if len(targets) != B:
+            raise ValueError("goicp_register: %d sources and %d targets" % (B, len(targets)))
+        off = np.zeros((B + 1, 2), np.int64)
+        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
+        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
+        p1, p2 = cat(sources), cat(targets)
+        tail, result = self._goicp_bufs(B)
+        self._check(fn(self._h, _fp(p1), _fp(p2), off.ctypes.data_as(C.POINTER(C.c_int64)), B, C.byref(p), *tail))
+        res = result()
+        if refine == "p2p":
+            ref = self.icp_refine(sources, targets, res["transforms"], radius=self.GOICP_REFINE_RADIUS, its=self.GOICP_REFINE_ITS)
+            res.update(search_transforms=res["transforms"], **ref)
+        return res
+
+    def goicp_register_rows(self, rows, constrained=True, refine=None, **params):
+        """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows."""
+        p = self._goicp_params(constrained, refine, params)
+        fn = self._register_fn("alignnet_goicp_register_dataset")
+        r, rp = self._rows(rows)
+        tail, result = self._goicp_bufs(r.size)
+        self._check(fn(self._h, rp, r.size, C.byref(p), *tail))
+        res = result()
+        if refine == "p2p":
+            ref = self.icp_refine_rows(r, res["transforms"], radius=self.GOICP_REFINE_RADIUS, its=self.GOICP_REFINE_ITS)
+            res.update(search_transforms=res["transforms"], **ref)
+        return res
+
+    def debug_goicp_nodes(self, source, target, depth, coords, **params):
+        """Test hook: (ub [K], lb [K]) of K nodes of one pair, given as integer coordinates coords [K, 4] at the halvings depth [4] of
+        (theta, x, y, z), by the search's own evaluation kernel."""
+        p = self._goicp_params(True, None, params)
+        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+        d = np.ascontiguousarray(depth, np.int32).reshape(4)
+        c = np.ascontiguousarray(coords, np.int32).reshape(-1, 4)
+        ub, lb = np.empty(len(c), np.float64), np.empty(len(c), np.float64)
+        dp, ip = (lambda a: a.ctypes.data_as(C.POINTER(C.c_double))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._check(self._lib.alignnet_debug_goicp_nodes(self._h, _fp(p1), len(p1), _fp(p2), len(p2), C.byref(p), ip(d), ip(c), len(c), dp(ub), dp(lb)))
+        return ub, lb
+
     # ---- spinning-LiDAR scene generator (csrc/alignnet_scene.hip; alignnet3d/scenes.py builds the arguments) ----
     def scene_upload_meshes(self, meshes, sensor=None):
         """meshes: list of (vertices [nv, 3] float64 normalised as scenes.normalise_mesh does, faces [nf, 3] int, centroid [3]); sensor: (dir_x [4500],

@@ -185,6 +185,7 @@ extern "C" void alignnet_globalreg_free(alignnet_handle* h);
 extern "C" void alignnet_scene_free(alignnet_handle* h);
 extern "C" void alignnet_tracklet_free(alignnet_handle* h);
 extern "C" void alignnet_icp_free(alignnet_handle* h);
+extern "C" void alignnet_goicp_free(alignnet_handle* h);
 
 namespace { void pipe_free(alignnet_handle* h); hipStream_t pipe_stream(alignnet_handle* h, int which); }   // pipelined host path, defined with alignnet_forward_submit below
 
@@ -200,6 +201,7 @@ extern "C" void alignnet_destroy(alignnet_handle* h)
   alignnet_scene_free(h);
   alignnet_tracklet_free(h);
   alignnet_icp_free(h);
+  alignnet_goicp_free(h);
   alignnet_register_free(h);
   pipe_free(h);
   free_ws(h);

@@ -166,6 +166,8 @@ struct alignnet_handle {
   void* dataset_ws = nullptr;      // HBM-resident dataset + batch buffers (alignnet_dataset.hip)
   void* globalreg_ws = nullptr;    // stage arrays of the global registration (alignnet_globalreg.hip), grown on demand
   size_t globalreg_ws_bytes = 0;
+  void* goicp_ws = nullptr;        // working sets, frontiers and bounds of the branch-and-bound registration (alignnet_goicp.hip), grown on demand
+  size_t goicp_ws_bytes = 0;
   int icp_search = 0;              // alignnet_set_option("icp_search"): 0 = scan, 1 = grid, 2 = grid for pairs beyond the scan's LDS stage (alignnet_icp.hip)
   void* register_ws = nullptr;     // buffers of the one-call registration (alignnet_register.hip), grown on demand
   void* icp_grid_ws = nullptr;     // bucket-sorted targets + cell tables of the grid search (alignnet_icp.hip), grown on demand

@@ -521,6 +521,60 @@ int alignnet_debug_fgr_stages(alignnet_handle* h, const float* points1, int64_t 
                               double* out_T, double* out_fitness, double* out_rmse, int32_t* out_correspondences,
                               int64_t* out_trials);
 
+/* ---- Go-ICP: branch-and-bound over yaw and a translation box (the `goicp` baseline, icp.py:146-147, 188-189) -----
+ * The reference names the method and leaves it `assert False`; the computation is DEFINED by tests/goicp_ref.py (DESIGN.md
+ * 4.7e).  Rotation about z only.  Per pair: working sets S (the source, or its points floor(i n1 / max_source)) and Q
+ * (likewise, max_target), centred in fp64; T(theta, t): x -> Rz(theta)(x - mean S) + mean Q + t over theta in
+ * [-yaw_half, yaw_half], t_k in [-t_half[k], t_half[k]]; E = sum_i min(d_i, trunc)^2 with d_i the distance of T(s_i) to
+ * its nearest target.  A level-synchronous search halves every dimension whose half-width is above its resolution
+ * (yaw_res, t_res), keeps the nodes whose lower bound is below best - mse_thresh |S|, and stops with a status:
+ * CERTIFIED (no node left), RESOLUTION (only leaves left), OVERFLOW (survivors x children > max_frontier), LEVELS
+ * (max_levels levels evaluated), EMPTY (a cloud without points: identity, error 0).  `starts` z-constrained point-to-point
+ * ICP runs (alignnet_icp_refine's loop, radius start_radius, start_its iterations) on the working sets from yaws
+ * 2 pi k / starts give the initial bound; 0 = none.  stage_points: targets staged in LDS at once, 0 = 2048 (a test hook
+ * for the chunked path; a multiple of 16).  flags must be 0.
+ * out_T [B][16] row-major 4x4 float64 about the origin, as the other register calls return; out_error [B] = E at the
+ * returned pose; out_lower_bound [B] = min(error - mse_thresh |S|, lowest bound of the nodes still open): no pose of the
+ * domain has a smaller E; out_fitness [B]; out_status [B]; out_evaluated / out_survived [B][ALIGNNET_GOICP_MAX_LEVELS] nodes per level.
+ * Every pointer but out_T may be NULL.  A pair's result depends on its clouds and the parameters only.
+ * _dataset: the clouds of the uploaded dataset addressed by example rows.
+ * alignnet_debug_goicp_nodes (test hook, outside the stable surface): one pair, K nodes as integer coordinates
+ * coords [K][4] in [0, 2^depth[k]) at the halvings depth [4] of (theta, x, y, z), through the search's own evaluation
+ * kernel: ub [K] = E at the node's centre, lb [K] its lower bound.
+ * (Added without moving ALIGNNET_ABI_VERSION, as alignnet_register was.) */
+#define ALIGNNET_GOICP_MAX_LEVELS 24
+#define ALIGNNET_GOICP_CERTIFIED 0
+#define ALIGNNET_GOICP_RESOLUTION 1
+#define ALIGNNET_GOICP_OVERFLOW 2
+#define ALIGNNET_GOICP_LEVELS 3
+#define ALIGNNET_GOICP_EMPTY 4
+typedef struct {
+  double yaw_half;       /* [0, pi] */
+  double t_half[3];      /* >= 0; a zero-width dimension is never split */
+  double yaw_res, t_res; /* > 0 */
+  double trunc;          /* > 0, may be +inf */
+  double mse_thresh;     /* >= 0 */
+  double start_radius;   /* > 0 when starts > 0 */
+  double fitness_radius; /* >= 0: out_fitness = the share of S within it at the returned pose */
+  int32_t max_source, max_target;   /* [1, 2^16], [1, 2^20] */
+  int32_t max_frontier;  /* [1, 2^24] nodes per pair */
+  int32_t max_levels;    /* [1, ALIGNNET_GOICP_MAX_LEVELS] */
+  int32_t starts;        /* [0, 64] */
+  int32_t start_its;     /* >= 0 */
+  int32_t stage_points;  /* 0, or a multiple of 16 in [16, 2048] */
+  int32_t flags;         /* 0 */
+} alignnet_goicp_params;
+
+int alignnet_goicp_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
+                            const alignnet_goicp_params* params, double* out_T, double* out_error, double* out_lower_bound,
+                            double* out_fitness, int32_t* out_status, int32_t* out_evaluated, int32_t* out_survived);
+int alignnet_goicp_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const alignnet_goicp_params* params,
+                                    double* out_T, double* out_error, double* out_lower_bound, double* out_fitness,
+                                    int32_t* out_status, int32_t* out_evaluated, int32_t* out_survived);
+int alignnet_debug_goicp_nodes(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2,
+                               const alignnet_goicp_params* params, const int32_t* depth, const int32_t* coords, int32_t K,
+                               double* ub, double* lb);
+
 /* ---- spinning-LiDAR scene generator (the SynthCars-style datasets, tp_utils/pointcloud.py:945-971,1055-1186) -------
  * A 64 x 4500-ray sensor at the origin (ray index = row * 4500 + column, direction 120 (sin h, cos h, tan v), vfov 26.9
  * degrees, 360 degrees around) is cast against a triangle mesh at two poses per scene; the first hit of every ray is kept
