@@ -314,10 +314,11 @@ def floor_mod(x, y):
     return x - np.floor(x / y) * y
 
 
-def get_angles(logits, nb):
-    """models/tp8.py:294-301 + :202-212.  In-graph yaw decode (residual scaled by pi/nb)."""
+def get_angles(logits, nb, cls=None):
+    """models/tp8.py:294-301 + :202-212.  In-graph yaw decode (residual scaled by pi/nb).
+    cls: int array [B] used in place of the arg-max (the class another evaluation of the same graph took: tests/helpers.py compare_forward_all)."""
     dt = logits.dtype.type
-    cls = np.argmax(logits[:, :nb], axis=1)
+    cls = np.argmax(logits[:, :nb], axis=1) if cls is None else np.asarray(cls).astype(np.intp).reshape(logits.shape[0])
     res = logits[:, nb:] * (dt(np.float32(np.pi)) / dt(nb))
     per = res[np.arange(logits.shape[0]), cls]
     pi = dt(np.float32(np.pi))
@@ -333,8 +334,9 @@ def rot_z(a):
     return np.stack([c, -s, z, s, c, z, z, z, o], axis=-1).reshape(-1, 3, 3)
 
 
-def embedding_net(pcs, P, spec, tower, is_training, bn_decay, updates, dropout_u):
-    """models/tp8.py:101-132 (one tower)."""
+def embedding_net(pcs, P, spec, tower, is_training, bn_decay, updates, dropout_u, yaw_cls=None):
+    """models/tp8.py:101-132 (one tower).  yaw_cls: int array [B], the yaw class stage 3 turns by in place of the arg-max of `logits`;
+    aux["yaw_gap"] is the own top class logit minus the logit at the class used (0 when nothing is pinned)."""
     center_mean = pcs.mean(axis=1)  # :104
     x1 = pcs - center_mean[:, None, :]  # :106
     f1 = backbone(x1, P, spec, "transformer1/embedding", spec.s1_conv, tower, is_training, bn_decay, updates)
@@ -347,20 +349,24 @@ def embedding_net(pcs, P, spec, tower, is_training, bn_decay, updates, dropout_u
                   is_training, bn_decay, updates, None if dropout_u is None else dropout_u[f"s2_{tower}"])
     s2c = o2[:, :3] + s1c  # :117
     logits = o2[:, 3:]  # :118
-    ang, cls = get_angles(logits, spec.num_bins)  # :123
+    ang, cls = get_angles(logits, spec.num_bins, yaw_cls)  # :123
+    cl = logits[:, :spec.num_bins]
+    yaw_gap = cl.max(axis=1) - cl[np.arange(cl.shape[0]), cls]
     R = rot_z(-ang)  # :125
     x3 = np.einsum("bnc,bcd->bnd", pcs - s2c[:, None, :], R)  # :122,127
     emb = backbone(x3, P, spec, "embedding", spec.emb_conv, tower, is_training, bn_decay, updates)  # :130
-    aux = dict(f1=f1, f2=f2, cls=cls, ang=ang, x3=x3)
+    aux = dict(f1=f1, f2=f2, cls=cls, ang=ang, x3=x3, yaw_gap=yaw_gap)
     return emb, center_mean, s1c, s2c, logits, aux
 
 
 def get_model(P, spec: NetSpec, pcs1, pcs2, is_training=False, bn_decay=None,
-              dropout_u: Optional[Dict[str, np.ndarray]] = None, collect_updates: bool = True):
-    """models/tp8.py:135-158.  Returns (end_points, ema_updates, aux)."""
+              dropout_u: Optional[Dict[str, np.ndarray]] = None, collect_updates: bool = True, yaw_cls=None):
+    """models/tp8.py:135-158.  Returns (end_points, ema_updates, aux).  yaw_cls: None, or one entry per tower (None or an int array [B]):
+    the yaw classes to use in place of the arg-max (embedding_net)."""
     updates: Optional[Dict[str, np.ndarray]] = {} if (is_training and collect_updates) else None
-    e1, cm1, s1c1, s2c1, lg1, aux1 = embedding_net(pcs1, P, spec, 0, is_training, bn_decay, updates, dropout_u)
-    e2, cm2, s1c2, s2c2, lg2, aux2 = embedding_net(pcs2, P, spec, 1, is_training, bn_decay, updates, dropout_u)
+    yc1, yc2 = (None, None) if yaw_cls is None else yaw_cls
+    e1, cm1, s1c1, s2c1, lg1, aux1 = embedding_net(pcs1, P, spec, 0, is_training, bn_decay, updates, dropout_u, yc1)
+    e2, cm2, s1c2, s2c2, lg2, aux2 = embedding_net(pcs2, P, spec, 1, is_training, bn_decay, updates, dropout_u, yc2)
     comb = np.concatenate([e1, e2], axis=1)  # :144,153
     net = head_mlp(comb, P, "", list(spec.rem_fc) + [spec.out_s2], None, spec.rem_keep, is_training, bn_decay,
                    updates, None if dropout_u is None else dropout_u["rem"])

@@ -9,7 +9,7 @@ import pytest
 
 import alignnet3d
 from oracle import alignnet_ref as R
-from tests.helpers import oracle_params, compare_forward
+from tests.helpers import oracle_params, compare_forward, compare_forward_all
 
 pytestmark = pytest.mark.gpu
 
@@ -128,7 +128,10 @@ def test_shipped_config_against_the_oracle(gpu_required):
     spec, P32 = _params(cfg)
     d = R.synth_pairs(B, 256, seed=1234, dtype=np.float32)
     ep = _both(cfg, d)
-    ref, _, _ = R.get_model({k: v.astype(np.float64) for k, v in P32.items()}, spec, d["pcs1"].astype(np.float64), d["pcs2"].astype(np.float64))
+    ref, _, aux = R.get_model({k: v.astype(np.float64) for k, v in P32.items()}, spec, d["pcs1"].astype(np.float64), d["pcs2"].astype(np.float64))
     worst, unstable = compare_forward(ep, ref, spec.num_bins)
     print("worst abs err", worst, "unstable pairs", unstable)
     assert unstable <= 1
+    worst, pinned, left_out = compare_forward_all(ep, ref, aux, P32, spec, d["pcs1"], d["pcs2"])   # every pair, the oracle pinned to the engine's yaw class where they differ
+    print("ALL %d pairs: %d pinned to the engine's yaw class, left out %s, worst abs err %s" % (B, pinned, left_out, worst))
+    assert left_out == []

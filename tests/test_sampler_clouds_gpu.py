@@ -14,7 +14,7 @@ import alignnet3d
 from oracle import alignnet_ref as R
 from tests import knn_select_ref as KS
 from tests import sampler_cases as SC
-from tests.helpers import small_cfg, oracle_params, compare_forward
+from tests.helpers import small_cfg, oracle_params, compare_forward, compare_forward_all
 from tests.test_train_gpu import (DGCNN_GENERAL, PINNED_CASES, STD, _grad_check, _oracle, pinned_check)
 
 pytestmark = pytest.mark.gpu
@@ -96,12 +96,21 @@ def _forward_and_alone(cfg, P32, d, options):
         assert eng.get_option(k) == v
     ep = eng.forward(d["pcs1"], d["pcs2"])
     kernel = eng.last_backbone_kernel()
+    graph = eng.debug_knn_graph(len(d["pcs1"])) if cfg["model"]["backbone"] == "dgcnn" else None
     for b in range(len(d["pcs1"])):
         alone = eng.forward(d["pcs1"][b:b + 1], d["pcs2"][b:b + 1])
         for k in ep:
             np.testing.assert_array_equal(alone[k][0], ep[k][b], err_msg="pair %d alone: %s" % (b, k))
     eng.close()
-    return ep, kernel
+    return ep, kernel, graph
+
+
+def _all_pairs(what, ep, ref, aux, P32, spec, d, atol=1e-4, rtol=1e-4, graph=None):
+    """Every pair against the oracle, pinned to the engine's yaw class where the two differ (tests/helpers.py compare_forward_all): pointnet leaves no pair
+    out; DGCNN at most one pair's stage 3, with the near-tie of the fp32 kNN distances shown on it."""
+    worst, pinned, left_out = compare_forward_all(ep, ref, aux, P32, spec, d["pcs1"], d["pcs2"], atol=atol, rtol=rtol, knn_graph=graph)
+    print("%s: ALL %d pairs, %d pinned to the engine's yaw class, left out %s, worst abs err %.2e" % (what, len(d["pcs1"]), pinned, left_out, max(worst.values())))
+    assert graph is not None or left_out == []
 
 
 @pytest.fixture(scope="module")
@@ -118,8 +127,8 @@ def forward_ref():
                 cfg = small_cfg(N=N, backbone="dgcnn")
             spec, P32 = oracle_params(cfg)
             d = SC.batch(SC.MIXED, N)
-            ref, _, _ = R.get_model({k: v.astype(np.float64) for k, v in P32.items()}, spec, d["pcs1"].astype(np.float64), d["pcs2"].astype(np.float64))
-            cache[(backbone, N)] = (cfg, spec, P32, d, ref)
+            ref, _, aux = R.get_model({k: v.astype(np.float64) for k, v in P32.items()}, spec, d["pcs1"].astype(np.float64), d["pcs2"].astype(np.float64))
+            cache[(backbone, N)] = (cfg, spec, P32, d, ref, aux)
         return cache[(backbone, N)]
     return get
 
@@ -128,21 +137,23 @@ def forward_ref():
 def test_forward_pointnet_on_sampler_batch(gpu_required, forward_ref, N):
     """The mixed batch (B = 8) against the fp64 oracle at compare_forward's bars (1e-4): exact fp32 on both tile shapes, split-bf16 tile-wise and persistent
     (bit-identical to each other); every pair alone bit-identical to the pair in the batch."""
-    cfg, spec, P32, d, ref = forward_ref("pointnet", N)
+    cfg, spec, P32, d, ref, aux = forward_ref("pointnet", N)
     B = len(SC.MIXED)
     for tile, kernel in ((128, "pointnet_fused<64,128,k16>"), (64, "pointnet_fused<64,128,k16,tp64>")):
-        ep, ran = _forward_and_alone(cfg, P32, d, (("infer_tile_points", tile),))
+        ep, ran, _ = _forward_and_alone(cfg, P32, d, (("infer_tile_points", tile),))
         assert ran == kernel, ran
         worst, unstable = compare_forward(ep, ref, spec.num_bins)
         print("pointnet fp32 tile %d N=%d: worst abs err %.2e, unstable pairs %d" % (tile, N, max(worst.values()), unstable))
         assert unstable <= max(1, B // 4)
+        _all_pairs("pointnet fp32 tile %d N=%d" % (tile, N), ep, ref, aux, P32, spec, d)
     out = {}
     for tilewise, kernel in ((1, "pointnet_split<64,128>"), (0, "pointnet_split_persist")):
-        out[tilewise], ran = _forward_and_alone(cfg, P32, d, (("infer_matmul_bf16x3", 1), ("ab_split_tilewise", tilewise)))
+        out[tilewise], ran, _ = _forward_and_alone(cfg, P32, d, (("infer_matmul_bf16x3", 1), ("ab_split_tilewise", tilewise)))
         assert ran == kernel, ran
         worst, unstable = compare_forward(out[tilewise], ref, spec.num_bins)
         print("pointnet split-bf16 %s N=%d: worst abs err %.2e, unstable pairs %d" % (kernel, N, max(worst.values()), unstable))
         assert unstable <= max(1, B // 4)
+        _all_pairs("pointnet split-bf16 %s N=%d" % (kernel, N), out[tilewise], ref, aux, P32, spec, d)
     for k in out[0]:
         np.testing.assert_array_equal(out[0][k], out[1][k], err_msg=k)
 
@@ -153,11 +164,12 @@ def test_forward_dgcnn_on_sampler_batch(gpu_required, forward_ref, N, split):
     """DGCNN, exact fp32 and split-bf16, at the bars the DGCNN forward tests hold (compare_forward at 2e-4: the oracle rebuilds the graph per stage in fp64, the
     engine once in fp32).  Among copies the neighbour SET is not unique in the oracle (its sort sees 1e-16 noise between copies), but the max over the k
     neighbours does not see which copies were taken."""
-    cfg, spec, P32, d, ref = forward_ref("dgcnn", N)
-    ep, ran = _forward_and_alone(cfg, P32, d, (("infer_matmul_bf16x3", split),))
+    cfg, spec, P32, d, ref, aux = forward_ref("dgcnn", N)
+    ep, ran, graph = _forward_and_alone(cfg, P32, d, (("infer_matmul_bf16x3", split),))
     worst, unstable = compare_forward(ep, ref, spec.num_bins, atol=2e-4, rtol=2e-4)
     print("dgcnn %s N=%d (%s): worst abs err %.2e, unstable pairs %d" % ("split-bf16" if split else "fp32", N, ran, max(worst.values()), unstable))
     assert unstable <= max(1, len(SC.MIXED) // 4)
+    _all_pairs("dgcnn %s N=%d" % ("split-bf16" if split else "fp32", N), ep, ref, aux, P32, spec, d, atol=2e-4, rtol=2e-4, graph=graph)
 
 
 # ---------------------------------------------------------------- training ----------------------------------------------------------------
