@@ -14,20 +14,20 @@
 //    result never depends on the batch it was generated in.  It is NOT np.random.randn's stream (parity unpinned by construction, as for the sampler).
 //
 // Stages of one alignnet_scene_generate (B scenes x 2 clouds against the uploaded mesh library):
-//  1. scene_window_kernel, one workgroup per cloud: every triangle marks the columns its azimuth interval covers (+- 1e-6 column of margin) in an LDS
-//     difference array (integer atomics: order-free); a triangle whose xy projection holds the z axis covers all 4500.  The window is the complement of the
+//  1. scene_window_kernel, one workgroup per cloud: every triangle marks the columns its azimuth interval covers (tri_reach: +- 1e-6 column of margin) in an
+//     LDS difference array (integer atomics: order-free); a triangle whose xy projection holds the z axis (holds_axis) covers all 4500.  The window is the complement of the
 //     largest uncovered gap of the circle of columns, so it may wrap 4499 -> 0.  The windows come back to the host (one small copy), which deals
 //     (cloud, tile of 8 window columns) work items: a batch of small far objects and one near object both become hundreds of workgroups.
 //  2. scene_cast_kernel (the SCAN, alignnet_set_option "scene_cast" = 0, the default), one workgroup (four waves) per tile; lane = elevation row, a wave
 //     takes two of the tile's columns.  The cloud's triangles go through LDS in chunks of 512: each is posed (Rz(angle) (scale v) + position, fp64), culled against the tile's azimuth sector by two exact side tests
 //     with a relative margin (all three vertices strictly before the first column's half plane, or strictly behind the last one's: conservative, so what is
 //     left is decided in fp64 as above), and the survivors' ten numbers are compacted into LDS (ballot prefix: deterministic order).  The inner loop
-//     (cast_triangle per staged triangle, shared with the binned cast) reads one triangle as a broadcast and tests it against the wave's two columns.  Cost model: every tile poses and side-tests all T triangles of its cloud
+//     (cast_triangle per staged triangle, shared with the binned cast; the hit decision and the tie rule are keep_nearest, shared with the band loop) reads one triangle as a broadcast and tests it against the wave's two columns.  Cost model: every tile poses and side-tests all T triangles of its cloud
 //     (T / 256 per thread, latency-bound on the vertex gathers) and intersects 64 x 8 rays with the few that overlap its 0.64 deg sector; a car of some
 //     hundred triangles is one chunk, a 10^5-triangle model is 200 chunks per tile.  t per ray goes to a [row][window column] table (inf = miss).
 //  2b. the BINNED cast ("scene_cast" = 1: every cloud; 2: clouds of more than kSceneBinAuto triangles) removes the T / 256 term: per cloud the triangles
 //     are binned to the window's tiles once, and a tile poses only the triangles of its own list.
-//       scene_bin_tally_kernel    grid (cloud, slice of the mesh): every triangle is posed once, its tile range found (tri_reach: the WINDOW kernel's rule --
+//       scene_bin_tally_kernel    grid (cloud, slice of the mesh): every triangle is posed once, its tile range found (tri_reach, which the WINDOW kernel calls too --
 //                                 the atan2 interval of its three vertices widened by kColMargin columns; every tile when its xy projection holds the z axis
 //                                 or it spans half the circle; a zero-area triangle reaches nothing and is dropped) and counted in an LDS histogram of the
 //                                 window's tiles, which is added onto the (cloud, tile) counters (integer atomics: order-free);
@@ -42,17 +42,16 @@
 //     Why the lists are conservative: a ray of column c can only hit a triangle when its xy direction lies in the angular span of the triangle's xy
 //     projection as seen from the z axis.  When the projection does not hold the axis and spans less than half the circle, that span is the interval
 //     between the extreme vertex azimuths (the projection is convex); column c sits at column coordinate c to 1e-13, the interval is widened by 1e-6 column
-//     and rounded outwards to whole columns: the margin is seven orders of magnitude above atan2's error, and that alone makes the range conservative,
-//     whatever scene_window_kernel computed.  (It is also the rule by which the window is chosen -- a column outside every interval is cast by neither
-//     path -- but the scan culls inside the window by exact side tests, not by these intervals.)  A range that leaves the window (possible only if the
-//     two kernels rounded an interval's end differently) is clamped to it.
+//     and rounded outwards to whole columns: the margin is seven orders of magnitude above atan2's error, and that alone makes the range conservative.
+//     (It is also the function by which the window is chosen -- a column outside every interval is cast by neither path -- but the scan culls inside
+//     the window by exact side tests, not by these intervals.)  A range that leaves the window would be clamped to it.
 //     Measured (tools/scene_cast_rate.py, profiles/scene_cast_rate.json; 512 clouds, whole calls): the binned cast is NOT ahead of the scan at 516, 5,001,
 //     20,001 or 100,002 triangles (0.79 - 0.95 x).  Both casts are bound by the inner loop -- every staged triangle against all 64 x 8 rays of the tile, about
 //     0.6 - 0.8 ns of chip time per (tile, triangle) entry -- and the scan's side tests leave it the same entries; the T / 256 term that binning removes is
 //     the small one (cast kernel 13.6 -> 12.8 ms at 20,001 triangles) and the binning costs more (1.6 ms there).  Fewer rays per entry -- binning by
 //     elevation row inside a tile, for which these lists are the input -- is the step that would pay (2c).  The default stays the scan.
 //  2c. BY ELEVATION BAND ("scene_rows" = 1, orthogonal to "scene_cast"; 0, the default, is exactly the kernels above): scene_band_scan_kernel and
-//     scene_band_list_kernel keep the two stagings and replace the inner loop.  A staged triangle gets an 8-bit mask of the bands of 8 rows it can
+//     scene_band_list_kernel keep the two stagings (stage_scan_pass; stage_list_chunk, which the binned cast runs without the masks) and replace the inner loop.  A staged triangle gets an 8-bit mask of the bands of 8 rows it can
 //     reach (in SceneTri::pad; the rule and why it is conservative stand above the kernels) and is intersected only with those cells of 8 rows x 8
 //     columns, a lane being one ray; the four waves share the staged entries and merge their candidates per ray at the end.  Bit for bit the scan.
 //     Measured: tools/scene_rows_rate.py, profiles/scene_rows_rate.json, DESIGN.md 4.9c.
@@ -118,6 +117,46 @@ __device__ __forceinline__ void tri_setup(const V3& a, const V3& b, const V3& cc
 // column coordinate of a direction in the xy plane: h = atan2(x, y) in degrees, column = (h + 180) / 0.08
 __device__ __forceinline__ double col_coord(double x, double y) { return (atan2(x, y) * 57.29577951308232 + 180.0) * (kCols / 360.0); }
 
+// does the xy projection of the posed triangle (a, b, d) hold the z axis (with margin)?  o_k = cross of consecutive vertices; their sum is twice
+// the projected area.  ONE rule for the window, the tile lists and the band masks: their conservativeness arguments name the same triangles.
+__device__ __forceinline__ bool holds_axis(const V3& a, const V3& b, const V3& d)
+{
+#pragma clang fp contract(off)
+  const double o1 = a.x * b.y - a.y * b.x, o2 = b.x * d.y - b.y * d.x, o3 = d.x * a.y - d.y * a.x;
+  const double ext = fmax(fmax(fabs(a.x) + fabs(a.y), fabs(b.x) + fabs(b.y)), fabs(d.x) + fabs(d.y));
+  const double m = kSideMargin * ext * ext;
+  if (fabs(o1 + o2 + o3) > m) return (o1 >= -m && o2 >= -m && o3 >= -m) || (o1 <= m && o2 <= m && o3 <= m);
+  // the projection is a segment: it holds the axis when two vertices lie on opposite sides of it
+  return fmin(fmin(a.x * b.x + a.y * b.y, b.x * d.x + b.y * d.y), d.x * a.x + d.y * a.y) <= m;
+}
+
+// col_coord as a call: one body of fp64 atan2 per kernel instead of three inlined copies each (which spilled scalar registers in the tally and the fill)
+__device__ __attribute__((noinline)) double col_coord_call(double x, double y) { return col_coord(x, y); }
+
+// Which columns a triangle can reach: 0 = none (zero area: never hit), 1 = the n columns from column *s on (they may wrap 4499 -> 0), 2 = every
+// column (its xy projection holds the z axis, or it spans half the circle).  The window, the tally and the fill all call it on the same numbers, so
+// they see the same ranges (contraction off and one shared atan2 body: the inlined copies round alike; the fill is bounded by the tallied lengths
+// regardless).  Nothing depends on their agreeing: a range is conservative on its own, because the 1e-6 column margin is seven orders above the
+// error of fp64 atan2 (1e-13 column) -- a column outside every interval can be hit by no ray -- and a range that leaves the window is clamped to it.
+__device__ __forceinline__ int tri_reach(const SceneCloud& c, const double* __restrict__ verts, const int* __restrict__ fi, int* s, int* n)
+{
+#pragma clang fp contract(off)
+  const V3 a = pose(c, verts + (c.v0 + fi[0]) * 3), b = pose(c, verts + (c.v0 + fi[1]) * 3), d = pose(c, verts + (c.v0 + fi[2]) * 3);
+  SceneTri t;
+  tri_setup(a, b, d, t);
+  if (t.N[0] == 0.0 && t.N[1] == 0.0 && t.N[2] == 0.0) return 0;
+  if (holds_axis(a, b, d)) return 2;
+  const double c0 = col_coord_call(a.x, a.y);
+  double d1 = col_coord_call(b.x, b.y) - c0, d2 = col_coord_call(d.x, d.y) - c0;
+  d1 -= kCols * rint(d1 / kCols); d2 -= kCols * rint(d2 / kCols);   // into [-2250, 2250]
+  const double lo = c0 + fmin(0.0, fmin(d1, d2)), hi = c0 + fmax(0.0, fmax(d1, d2));
+  if (hi - lo >= kCols / 2 - 1.0) return 2;
+  const long long ca = (long long)floor(lo - kColMargin), cb = (long long)ceil(hi + kColMargin);
+  int first = (int)(ca % kCols); if (first < 0) first += kCols;
+  *s = first; *n = (int)(cb - ca + 1);
+  return 1;
+}
+
 __device__ int next_bit(const unsigned* w, int p, bool want_set)   // first position >= p whose bit is set / clear, -1 if none below kCols
 {
   constexpr int kWords = (kCols + 31) / 32;
@@ -147,36 +186,14 @@ __global__ __launch_bounds__(256) void scene_window_kernel(const SceneCloud* __r
   if (tid == 0) s_full = 0;
   __syncthreads();
   for (int f = tid; f < c.nf; f += 256) {
-    const int* fi = faces + (c.f0 + f) * 3;
-    const V3 a = pose(c, verts + (c.v0 + fi[0]) * 3), b = pose(c, verts + (c.v0 + fi[1]) * 3), d = pose(c, verts + (c.v0 + fi[2]) * 3);
-    SceneTri t;
-    tri_setup(a, b, d, t);
-    if (t.N[0] == 0.0 && t.N[1] == 0.0 && t.N[2] == 0.0) continue;   // zero area: never hit
-    // does the xy projection hold the z axis (with margin)?  o_k = cross of consecutive vertices; their sum is twice the projected area
-    const double o1 = a.x * b.y - a.y * b.x, o2 = b.x * d.y - b.y * d.x, o3 = d.x * a.y - d.y * a.x;
-    const double ext = fmax(fmax(fabs(a.x) + fabs(a.y), fabs(b.x) + fabs(b.y)), fabs(d.x) + fabs(d.y));
-    const double m = kSideMargin * ext * ext;
-    bool full;
-    if (fabs(o1 + o2 + o3) > m)
-      full = (o1 >= -m && o2 >= -m && o3 >= -m) || (o1 <= m && o2 <= m && o3 <= m);
-    else   // the projection is a segment: it holds the axis when two vertices lie on opposite sides of it
-      full = fmin(fmin(a.x * b.x + a.y * b.y, b.x * d.x + b.y * d.y), d.x * a.x + d.y * a.y) <= m;
-    if (!full) {
-      const double c0 = col_coord(a.x, a.y);
-      double d1 = col_coord(b.x, b.y) - c0, d2 = col_coord(d.x, d.y) - c0;
-      d1 -= kCols * rint(d1 / kCols); d2 -= kCols * rint(d2 / kCols);   // into [-2250, 2250]
-      const double lo = c0 + fmin(0.0, fmin(d1, d2)), hi = c0 + fmax(0.0, fmax(d1, d2));
-      if (hi - lo >= kCols / 2 - 1.0) full = true;
-      else {
-        const long long ca = (long long)floor(lo - kColMargin), cb = (long long)ceil(hi + kColMargin);
-        const int n = (int)(cb - ca + 1);
-        int s = (int)(ca % kCols); if (s < 0) s += kCols;
-        atomicAdd(&diff[s], 1);
-        if (s + n <= kCols) atomicAdd(&diff[s + n], -1);
-        else { atomicAdd(&diff[0], 1); atomicAdd(&diff[s + n - kCols], -1); }
-      }
+    int s = 0, n = 0;
+    const int kind = tri_reach(c, verts, faces + (c.f0 + f) * 3, &s, &n);
+    if (kind == 2) s_full = 1;
+    else if (kind == 1) {
+      atomicAdd(&diff[s], 1);
+      if (s + n <= kCols) atomicAdd(&diff[s + n], -1);
+      else { atomicAdd(&diff[0], 1); atomicAdd(&diff[s + n - kCols], -1); }
     }
-    if (full) s_full = 1;
   }
   __syncthreads();
   if (s_full) { if (tid == 0) { win[blockIdx.x * 2] = 0; win[blockIdx.x * 2 + 1] = kCols; } return; }
@@ -220,7 +237,22 @@ __global__ __launch_bounds__(256) void scene_window_kernel(const SceneCloud* __r
   }
 }
 
-// the arithmetic of both casts: one staged triangle against the wave's columns of one elevation row (lane)
+// ---- stage 2: the cast ---------------------------------------------------------------------------------------------------------------------
+// The hit decision of every cast, once: the signs of the numerators against den (the header's form of u >= 0, v >= 0, u + v <= 1, t > 0), one
+// division per hit, and the tie rule -- equal t goes to the lower triangle index.  Every cross-mode equality rests on there being one copy.
+__device__ __forceinline__ void keep_nearest(double cc, int id, double den, double un, double vn, double& best, int& bid)
+{
+#pragma clang fp contract(off)
+  const double sum = un + vn;
+  const bool hit = den > 0.0 ? (un >= 0.0 && vn >= 0.0 && sum <= den && cc > 0.0)
+                             : (den < 0.0 && un <= 0.0 && vn <= 0.0 && sum >= den && cc < 0.0);
+  if (hit) {
+    const double tt = cc / den;
+    if (tt > 0.0 && (tt < best || (tt == best && id < bid))) { best = tt; bid = id; }
+  }
+}
+
+// the whole-tile loop's arithmetic: one staged triangle against the wave's columns of one elevation row (dz . N2, dz . A2, dz . Bv2 formed once)
 __device__ __forceinline__ void cast_triangle(const SceneTri& t, const double (&dx)[kColsPerWave], const double (&dy)[kColsPerWave], double dz,
                                               double (&best)[kColsPerWave], int (&bid)[kColsPerWave])
 {
@@ -233,17 +265,10 @@ __device__ __forceinline__ void cast_triangle(const SceneTri& t, const double (&
     const double den = (dx[q] * N0 + dy[q] * N1) + nz;
     const double un = (dx[q] * A0 + dy[q] * A1) + az;
     const double vn = (dx[q] * B0 + dy[q] * B1) + bz;
-    const double sum = un + vn;
-    const bool hit = den > 0.0 ? (un >= 0.0 && vn >= 0.0 && sum <= den && cc > 0.0)
-                               : (den < 0.0 && un <= 0.0 && vn <= 0.0 && sum >= den && cc < 0.0);
-    if (hit) {
-      const double tt = cc / den;
-      if (tt > 0.0 && (tt < best[q] || (tt == best[q] && id < bid[q]))) { best[q] = tt; bid[q] = id; }
-    }
+    keep_nearest(cc, id, den, un, vn, best[q], bid[q]);
   }
 }
 
-// ---- stage 2: the cast ---------------------------------------------------------------------------------------------------------------------
 struct SceneCastArgs {
   const SceneCloud* clouds; const int* tiles /*[tiles][2] = cloud, tile of the window*/;
   const double* verts; const int* faces; const double* dir /*[4500] x | [4500] y | [64] z*/;
@@ -251,6 +276,30 @@ struct SceneCastArgs {
   int lds_triangles;
 };
 
+// what every cast kernel starts from: its (cloud, tile) work item
+struct SceneTile {
+  SceneCloud c; int ci, j0, ncol;   // the cloud (a copy) and its index, the tile's first window column, its columns (the last tile may be ragged)
+  double ax, ay, bx, by;            // the tile's azimuth sector, for the scan staging: the directions of its first and last column
+};
+
+template <bool kSector>
+__device__ __forceinline__ SceneTile tile_begin(const SceneCastArgs& a)
+{
+  SceneTile tl;
+  tl.ci = a.tiles[blockIdx.x * 2]; tl.j0 = a.tiles[blockIdx.x * 2 + 1] * kTileCols;
+  tl.c = a.clouds[tl.ci];
+  tl.ncol = min(kTileCols, tl.c.count - tl.j0);
+  tl.ax = tl.ay = tl.bx = tl.by = 0.0;
+  if constexpr (kSector) {
+    const int col_a = (tl.c.first + tl.j0) % kCols, col_b = (tl.c.first + tl.j0 + tl.ncol - 1) % kCols;   // (the window may wrap)
+    tl.ax = a.dir[col_a]; tl.ay = a.dir[kCols + col_a]; tl.bx = a.dir[col_b]; tl.by = a.dir[kCols + col_b];
+  }
+  return tl;
+}
+
+// the SCAN ("scene_cast" = 0, "scene_rows" = 0): the reference every other setting is tested against.  Its staging pass stays written out here (the band
+// loop's is stage_scan_pass), and the lane set-up and the store here and in scene_bincast_kernel: as functions they move this kernel's registers off
+// the 80 VGPRs the tests pin, or cost the two kernels instructions (tried piece by piece)
 template <bool kTrace>
 __global__ __launch_bounds__(kCastThreads) void scene_cast_kernel(const SceneCastArgs a)
 {
@@ -258,12 +307,10 @@ __global__ __launch_bounds__(kCastThreads) void scene_cast_kernel(const SceneCas
   SceneTri* tris = reinterpret_cast<SceneTri*>(lds_raw);
   __shared__ int wcnt[kCastThreads / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ci = a.tiles[blockIdx.x * 2], j0 = a.tiles[blockIdx.x * 2 + 1] * kTileCols;
-  const SceneCloud c = a.clouds[ci];
-  const int ncol = min(kTileCols, c.count - j0);
-  // the tile's azimuth sector: its first and last column (the window may wrap)
-  const int col_a = (c.first + j0) % kCols, col_b = (c.first + j0 + ncol - 1) % kCols;
-  const double ax = a.dir[col_a], ay = a.dir[kCols + col_a], bx = a.dir[col_b], by = a.dir[kCols + col_b];
+  const SceneTile tl = tile_begin<true>(a);
+  const SceneCloud& c = tl.c;
+  const int j0 = tl.j0, ncol = tl.ncol;
+  const double ax = tl.ax, ay = tl.ay, bx = tl.bx, by = tl.by;
   const double dz = a.dir[2 * kCols + lane];
   double dx[kColsPerWave], dy[kColsPerWave], best[kColsPerWave];
   int bid[kColsPerWave];
@@ -317,42 +364,6 @@ __global__ __launch_bounds__(kCastThreads) void scene_cast_kernel(const SceneCas
 }
 
 // ---- stage 2b: the binned cast -------------------------------------------------------------------------------------------------------------
-// Which columns a triangle can reach, by the window kernel's rule: 0 = none (zero area), 1 = the n columns from column *s on (they may wrap
-// 4499 -> 0), 2 = every column.  The tally and the fill both call it on the same numbers, so they see the same ranges (contraction off and one
-// shared atan2 body: the two inlined copies round alike; the fill is bounded by the tallied lengths regardless).  scene_window_kernel evaluates
-// the same expressions without the pragma, so its interval ends may round differently from these; nothing here depends on their agreeing: the
-// range is conservative on its own, because the 1e-6 column margin is far larger than the error of fp64 atan2 (1e-13 column), and a range that
-// leaves the window is clamped to it.
-// col_coord as a call: one body of fp64 atan2 for the tally and the fill instead of three inlined copies each (which spilled scalar registers)
-__device__ __attribute__((noinline)) double col_coord_call(double x, double y) { return col_coord(x, y); }
-
-__device__ __forceinline__ int tri_reach(const SceneCloud& c, const double* __restrict__ verts, const int* __restrict__ fi, int* s, int* n)
-{
-#pragma clang fp contract(off)
-  const V3 a = pose(c, verts + (c.v0 + fi[0]) * 3), b = pose(c, verts + (c.v0 + fi[1]) * 3), d = pose(c, verts + (c.v0 + fi[2]) * 3);
-  SceneTri t;
-  tri_setup(a, b, d, t);
-  if (t.N[0] == 0.0 && t.N[1] == 0.0 && t.N[2] == 0.0) return 0;
-  const double o1 = a.x * b.y - a.y * b.x, o2 = b.x * d.y - b.y * d.x, o3 = d.x * a.y - d.y * a.x;
-  const double ext = fmax(fmax(fabs(a.x) + fabs(a.y), fabs(b.x) + fabs(b.y)), fabs(d.x) + fabs(d.y));
-  const double m = kSideMargin * ext * ext;
-  bool full;
-  if (fabs(o1 + o2 + o3) > m)
-    full = (o1 >= -m && o2 >= -m && o3 >= -m) || (o1 <= m && o2 <= m && o3 <= m);
-  else
-    full = fmin(fmin(a.x * b.x + a.y * b.y, b.x * d.x + b.y * d.y), d.x * a.x + d.y * a.y) <= m;
-  if (full) return 2;
-  const double c0 = col_coord_call(a.x, a.y);
-  double d1 = col_coord_call(b.x, b.y) - c0, d2 = col_coord_call(d.x, d.y) - c0;
-  d1 -= kCols * rint(d1 / kCols); d2 -= kCols * rint(d2 / kCols);
-  const double lo = c0 + fmin(0.0, fmin(d1, d2)), hi = c0 + fmax(0.0, fmax(d1, d2));
-  if (hi - lo >= kCols / 2 - 1.0) return 2;
-  const long long ca = (long long)floor(lo - kColMargin), cb = (long long)ceil(hi + kColMargin);
-  int first = (int)(ca % kCols); if (first < 0) first += kCols;
-  *s = first; *n = (int)(cb - ca + 1);
-  return 1;
-}
-
 // the tiles of the cloud's window that the n columns from column s on touch: at most two runs [k0, k1] (the second when the columns pass the
 // window's column 4500, which only the all-column window allows); columns outside the window are dropped.  Returns the number of runs.
 __device__ __forceinline__ int reach_tiles(const SceneCloud& c, int s, int n, int (&k0)[2], int (&k1)[2])
@@ -443,58 +454,6 @@ struct SceneBinCastArgs {
   const int* list;
 };
 
-template <bool kTrace>
-__global__ __launch_bounds__(kCastThreads) void scene_bincast_kernel(const SceneBinCastArgs b)
-{
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  SceneTri* tris = reinterpret_cast<SceneTri*>(lds_raw);
-  const SceneCastArgs& a = b.c;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ci = a.tiles[blockIdx.x * 2], j0 = a.tiles[blockIdx.x * 2 + 1] * kTileCols;
-  const SceneCloud c = a.clouds[ci];
-  const int ncol = min(kTileCols, c.count - j0);
-  const double dz = a.dir[2 * kCols + lane];
-  double dx[kColsPerWave], dy[kColsPerWave], best[kColsPerWave];
-  int bid[kColsPerWave];
-#pragma unroll
-  for (int q = 0; q < kColsPerWave; ++q) {
-    const int j = j0 + wave * kColsPerWave + q;
-    const int col = (c.first + min(j, c.count - 1)) % kCols;   // (a column past the tile's end runs along on the last one; never stored)
-    dx[q] = a.dir[col]; dy[q] = a.dir[kCols + col];
-    best[q] = INFINITY; bid[q] = -1;
-  }
-  const long long e0 = b.off[blockIdx.x], e1 = b.off[(long long)blockIdx.x + 1];
-  const int L = a.lds_triangles;
-  for (long long s0 = e0; s0 < e1; s0 += L) {
-    const int n = (int)min((long long)L, e1 - s0);
-    for (int k = tid; k < n; k += kCastThreads) {
-      const int f = b.list[s0 + k];
-      SceneTri tr;
-      if ((unsigned)f < (unsigned)c.nf) {
-        const int* fi = a.faces + (c.f0 + f) * 3;
-        const V3 p = pose(c, a.verts + (c.v0 + fi[0]) * 3), q = pose(c, a.verts + (c.v0 + fi[1]) * 3), r = pose(c, a.verts + (c.v0 + fi[2]) * 3);
-        tri_setup(p, q, r, tr);
-      } else {   // (not a face of this mesh: a triangle that no ray hits)
-        tr.N[0] = tr.N[1] = tr.N[2] = tr.A[0] = tr.A[1] = tr.A[2] = tr.Bv[0] = tr.Bv[1] = tr.Bv[2] = tr.c = 0.0;
-      }
-      tr.id = f; tr.pad = 0;
-      tris[k] = tr;
-    }
-    __syncthreads();
-    for (int k = 0; k < n; ++k) cast_triangle(tris[k], dx, dy, dz, best, bid);   // every lane reads the same address: a broadcast
-    __syncthreads();   // the stage is rewritten by the next chunk
-  }
-#pragma unroll
-  for (int q = 0; q < kColsPerWave; ++q) {
-    const int j = j0 + wave * kColsPerWave + q;
-    if (j < j0 + ncol) {
-      const long long o = c.tbase + (long long)lane * c.count + j;
-      a.t[o] = best[q];
-      if constexpr (kTrace) a.tri[o] = bid[q];
-    }
-  }
-}
-
 // ---- stage 2c: both casts by elevation band ("scene_rows" = 1) --------------------------------------------------------------------------------
 // The tile and the workgroup stay (8 window columns x 64 rows, 256 threads); the unit of work becomes a CELL, one band of 8 consecutive rows x the
 // tile's 8 columns = 64 rays = one wave.  A lane is a ray: column lane & 7 of the tile, row 8 b + (lane >> 3) in band b.  A staged triangle carries
@@ -539,15 +498,7 @@ __device__ __forceinline__ void band_interval(const V3& a, const V3& b, const V3
 #pragma clang fp contract(off)
   if (t.N[0] == 0.0 && t.N[1] == 0.0 && t.N[2] == 0.0) { *lo = INFINITY; *hi = -INFINITY; return; }   // zero area: no band
   *lo = -INFINITY; *hi = INFINITY;   // every band, unless all of the following holds
-  const double o1 = a.x * b.y - a.y * b.x, o2 = b.x * d.y - b.y * d.x, o3 = d.x * a.y - d.y * a.x;
-  const double ext = fmax(fmax(fabs(a.x) + fabs(a.y), fabs(b.x) + fabs(b.y)), fabs(d.x) + fabs(d.y));
-  const double m = kSideMargin * ext * ext;
-  bool full;
-  if (fabs(o1 + o2 + o3) > m)
-    full = (o1 >= -m && o2 >= -m && o3 >= -m) || (o1 <= m && o2 <= m && o3 <= m);
-  else
-    full = fmin(fmin(a.x * b.x + a.y * b.y, b.x * d.x + b.y * d.y), d.x * a.x + d.y * a.y) <= m;
-  if (full) return;
+  if (holds_axis(a, b, d)) return;
   const double ra = a.x * a.x + a.y * a.y, rb = b.x * b.x + b.y * b.y, rd = d.x * d.x + d.y * d.y;
   const double rmax2 = fmax(fmax(ra, rb), rd), rmin2 = fmin(fmin(seg_dist2(a, b), seg_dist2(b, d)), seg_dist2(d, a));
   if (!(rmin2 > 1e-12 * rmax2)) return;
@@ -586,19 +537,8 @@ __device__ __forceinline__ int band_masks(bool have, double lo, double hi, doubl
 __device__ __forceinline__ void cast_ray(const SceneTri& t, double xn, double xa, double xb, double dz, double& best, int& bid)
 {
 #pragma clang fp contract(off)
-  const double cc = t.c;
-  const int id = t.id;
   const double nz = dz * t.N[2], az = dz * t.A[2], bz = dz * t.Bv[2];
-  const double den = xn + nz;
-  const double un = xa + az;
-  const double vn = xb + bz;
-  const double sum = un + vn;
-  const bool hit = den > 0.0 ? (un >= 0.0 && vn >= 0.0 && sum <= den && cc > 0.0)
-                             : (den < 0.0 && un <= 0.0 && vn <= 0.0 && sum >= den && cc < 0.0);
-  if (hit) {
-    const double tt = cc / den;
-    if (tt > 0.0 && (tt < best || (tt == best && id < bid))) { best = tt; bid = id; }
-  }
+  keep_nearest(t.c, t.id, xn + nz, xa + az, xb + bz, best, bid);
 }
 
 struct SceneBandArgs {
@@ -681,7 +621,116 @@ __device__ __forceinline__ void band_merge_store(const SceneCastArgs& a, const S
   }
 }
 
-// the scan's staging (scene_cast_kernel's, with the mask; a triangle of no band is not staged)
+// ---- the shared stagings and their kernels: the binned cast (list staging, whole-tile loop) and the two band kernels ---------------------------
+// what the band masks need of the tile: the extreme column norms, and dir_z of the row of the lane's own number (band_masks: lane = row)
+struct BandRule { double n_lo, n_hi, dzl; };
+
+// THE SCAN STAGING of the band loop, one pass: faces r0 .. r0 + 255 (below fend) of the cloud are posed, culled against the tile's sector and given
+// their band masks (a triangle of no band is not staged); the survivors' ten numbers are compacted behind the n triangles already staged (ballot
+// prefix: the order is the faces').  Returns the new count, the same in every thread.  scene_cast_kernel keeps its own copy of this pass
+// without the masks: its registers and instructions, which tests pin, change as soon as any part of the pass is a function.
+__device__ __forceinline__ int stage_scan_pass(const SceneCastArgs& a, const SceneTile& tl, const BandRule& br, int r0, int fend, int n, SceneTri* tris,
+                                               int* wcnt)
+{
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const SceneCloud& c = tl.c;
+  const int f = r0 + tid;
+  bool keep = false;
+  SceneTri tr;
+  double lo = 0.0, hi = 0.0;
+  if (f < fend) {
+    const int* fi = a.faces + (c.f0 + f) * 3;
+    const V3 p = pose(c, a.verts + (c.v0 + fi[0]) * 3), q = pose(c, a.verts + (c.v0 + fi[1]) * 3), v = pose(c, a.verts + (c.v0 + fi[2]) * 3);
+    // side of a column's half plane: s = dir_x y - dir_y x = |p| sin(column azimuth - point azimuth) (> 0: the point lies before the column)
+    const double mp = kSideMargin * 120.0 * (fabs(p.x) + fabs(p.y)), mq = kSideMargin * 120.0 * (fabs(q.x) + fabs(q.y)), mv = kSideMargin * 120.0 * (fabs(v.x) + fabs(v.y));
+    const bool before = tl.ax * p.y - tl.ay * p.x > mp && tl.ax * q.y - tl.ay * q.x > mq && tl.ax * v.y - tl.ay * v.x > mv;
+    const bool behind = tl.bx * p.y - tl.by * p.x < -mp && tl.bx * q.y - tl.by * q.x < -mq && tl.bx * v.y - tl.by * v.x < -mv;
+    keep = !before && !behind;
+    if (keep) { tri_setup(p, q, v, tr); tr.id = f; band_interval(p, q, v, tr, br.n_lo, br.n_hi, &lo, &hi); }
+  }
+  tr.pad = band_masks(keep, lo, hi, br.dzl, lane);
+  keep = keep && tr.pad != 0;
+  const unsigned long long m = __ballot(keep);
+  if (lane == 0) wcnt[wave] = __popcll(m);
+  __syncthreads();
+  int base = n, total = 0;
+#pragma unroll
+  for (int w = 0; w < kCastThreads / 64; ++w) { const int k = wcnt[w]; if (w < wave) base += k; total += k; }
+  if (keep) tris[base + __popcll(m & ((1ull << lane) - 1ull))] = tr;
+  __syncthreads();
+  return n + total;
+}
+
+// THE LIST STAGING, one chunk: the n entries from list on are posed (re-posing per entry: a table of posed triangles would be 88 B x T x clouds)
+// and staged in the list's order; an entry that is not a face of this mesh becomes a triangle that no ray hits.  kBand: with the band mask (no
+// face: no band); whole waves go round, because band_masks ballots.
+template <bool kBand>
+__device__ __forceinline__ void stage_list_chunk(const SceneCastArgs& a, const SceneCloud& c, const int* __restrict__ list, int n, SceneTri* tris,
+                                                 const BandRule& br = BandRule())
+{
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int k0 = 0; (kBand ? k0 : k0 + tid) < n; k0 += kCastThreads) {   // (kBand: whole waves go round)
+    const int k = k0 + tid;
+    const int f = k < n ? list[k] : -1;
+    const bool face = (unsigned)f < (unsigned)c.nf;
+    SceneTri tr;
+    double lo = 0.0, hi = 0.0;
+    if (face) {
+      const int* fi = a.faces + (c.f0 + f) * 3;
+      const V3 p = pose(c, a.verts + (c.v0 + fi[0]) * 3), q = pose(c, a.verts + (c.v0 + fi[1]) * 3), v = pose(c, a.verts + (c.v0 + fi[2]) * 3);
+      tri_setup(p, q, v, tr);
+      if constexpr (kBand) band_interval(p, q, v, tr, br.n_lo, br.n_hi, &lo, &hi);
+    } else {
+      tr.N[0] = tr.N[1] = tr.N[2] = tr.A[0] = tr.A[1] = tr.A[2] = tr.Bv[0] = tr.Bv[1] = tr.Bv[2] = tr.c = 0.0;
+    }
+    tr.id = f; tr.pad = 0;
+    if constexpr (kBand) tr.pad = band_masks(face, lo, hi, br.dzl, lane);
+    if (k < n) tris[k] = tr;
+  }
+}
+
+// the binned cast: the tile's list in chunks of lds_triangles
+template <bool kTrace>
+__global__ __launch_bounds__(kCastThreads) void scene_bincast_kernel(const SceneBinCastArgs b)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  SceneTri* tris = reinterpret_cast<SceneTri*>(lds_raw);
+  const SceneCastArgs& a = b.c;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const SceneTile tl = tile_begin<false>(a);
+  const SceneCloud& c = tl.c;
+  const int j0 = tl.j0, ncol = tl.ncol;
+  const double dz = a.dir[2 * kCols + lane];
+  double dx[kColsPerWave], dy[kColsPerWave], best[kColsPerWave];
+  int bid[kColsPerWave];
+#pragma unroll
+  for (int q = 0; q < kColsPerWave; ++q) {
+    const int j = j0 + wave * kColsPerWave + q;
+    const int col = (c.first + min(j, c.count - 1)) % kCols;   // (a column past the tile's end runs along on the last one; never stored)
+    dx[q] = a.dir[col]; dy[q] = a.dir[kCols + col];
+    best[q] = INFINITY; bid[q] = -1;
+  }
+  const long long e0 = b.off[blockIdx.x], e1 = b.off[(long long)blockIdx.x + 1];
+  const int L = a.lds_triangles;
+  for (long long s0 = e0; s0 < e1; s0 += L) {
+    const int n = (int)min((long long)L, e1 - s0);
+    stage_list_chunk<false>(a, c, b.list + s0, n, tris);
+    __syncthreads();
+    for (int k = 0; k < n; ++k) cast_triangle(tris[k], dx, dy, dz, best, bid);   // every lane reads the same address: a broadcast
+    __syncthreads();   // the stage is rewritten by the next chunk
+  }
+#pragma unroll
+  for (int q = 0; q < kColsPerWave; ++q) {
+    const int j = j0 + wave * kColsPerWave + q;
+    if (j < j0 + ncol) {
+      const long long o = c.tbase + (long long)lane * c.count + j;
+      a.t[o] = best[q];
+      if constexpr (kTrace) a.tri[o] = bid[q];
+    }
+  }
+}
+
+// the scan's staging under the band loop
 template <bool kTrace>
 __global__ __launch_bounds__(kCastThreads) void scene_band_scan_kernel(const SceneBandArgs s)
 {
@@ -692,55 +741,26 @@ __global__ __launch_bounds__(kCastThreads) void scene_band_scan_kernel(const Sce
   __shared__ int mi[kCastThreads / 64][2][64];
   const SceneCastArgs& a = s.b.c;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ci = a.tiles[blockIdx.x * 2], j0 = a.tiles[blockIdx.x * 2 + 1] * kTileCols;
-  const SceneCloud c = a.clouds[ci];
-  const int ncol = min(kTileCols, c.count - j0);
-  const int col_a = (c.first + j0) % kCols, col_b = (c.first + j0 + ncol - 1) % kCols;
-  const double ax = a.dir[col_a], ay = a.dir[kCols + col_a], bx = a.dir[col_b], by = a.dir[kCols + col_b];
-  const double dzl = a.dir[2 * kCols + lane];
+  const SceneTile tl = tile_begin<true>(a);
   BandLane r;
-  double n_lo, n_hi;
-  band_begin(a, c, j0, ncol, lane, r, &n_lo, &n_hi);
+  BandRule br;
+  br.dzl = a.dir[2 * kCols + lane];
+  band_begin(a, tl.c, tl.j0, tl.ncol, lane, r, &br.n_lo, &br.n_hi);
   int cells = 0;
   const int L = a.lds_triangles;
-  for (int f0 = 0; f0 < c.nf; f0 += L) {
-    const int fend = min(c.nf, f0 + L);
+  for (int f0 = 0; f0 < tl.c.nf; f0 += L) {
+    const int fend = min(tl.c.nf, f0 + L);
     int n = 0;   // triangles staged so far (the same in every thread)
-    for (int r0 = f0; r0 < fend; r0 += kCastThreads) {
-      const int f = r0 + tid;
-      bool keep = false;
-      SceneTri tr;
-      double lo = 0.0, hi = 0.0;
-      if (f < fend) {
-        const int* fi = a.faces + (c.f0 + f) * 3;
-        const V3 p = pose(c, a.verts + (c.v0 + fi[0]) * 3), q = pose(c, a.verts + (c.v0 + fi[1]) * 3), v = pose(c, a.verts + (c.v0 + fi[2]) * 3);
-        const double mp = kSideMargin * 120.0 * (fabs(p.x) + fabs(p.y)), mq = kSideMargin * 120.0 * (fabs(q.x) + fabs(q.y)), mv = kSideMargin * 120.0 * (fabs(v.x) + fabs(v.y));
-        const bool before = ax * p.y - ay * p.x > mp && ax * q.y - ay * q.x > mq && ax * v.y - ay * v.x > mv;
-        const bool behind = bx * p.y - by * p.x < -mp && bx * q.y - by * q.x < -mq && bx * v.y - by * v.x < -mv;
-        keep = !before && !behind;
-        if (keep) { tri_setup(p, q, v, tr); tr.id = f; band_interval(p, q, v, tr, n_lo, n_hi, &lo, &hi); }
-      }
-      tr.pad = band_masks(keep, lo, hi, dzl, lane);
-      keep = keep && tr.pad != 0;
-      const unsigned long long m = __ballot(keep);
-      if (lane == 0) wcnt[wave] = __popcll(m);
-      __syncthreads();
-      int base = n, total = 0;
-#pragma unroll
-      for (int w = 0; w < kCastThreads / 64; ++w) { const int k = wcnt[w]; if (w < wave) base += k; total += k; }
-      if (keep) tris[base + __popcll(m & ((1ull << lane) - 1ull))] = tr;
-      n += total;
-      __syncthreads();
-    }
+    for (int r0 = f0; r0 < fend; r0 += kCastThreads) n = stage_scan_pass(a, tl, br, r0, fend, n, tris, wcnt);
     band_cast(tris, n, wave, r);
     if constexpr (kTrace) if (tid < kBands) cells += band_tally(tris, n, tid);
     __syncthreads();   // the stage is rewritten by the next chunk
   }
-  band_merge_store<kTrace>(a, c, j0, ncol, r, mt, mi);
+  band_merge_store<kTrace>(a, tl.c, tl.j0, tl.ncol, r, mt, mi);
   if constexpr (kTrace) if (tid < kBands) s.cells[(long long)blockIdx.x * kBands + tid] = cells;
 }
 
-// the list staging (scene_bincast_kernel's, with the mask)
+// the list staging under the band loop
 template <bool kTrace>
 __global__ __launch_bounds__(kCastThreads) void scene_band_list_kernel(const SceneBandArgs s)
 {
@@ -750,41 +770,23 @@ __global__ __launch_bounds__(kCastThreads) void scene_band_list_kernel(const Sce
   __shared__ int mi[kCastThreads / 64][2][64];
   const SceneCastArgs& a = s.b.c;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ci = a.tiles[blockIdx.x * 2], j0 = a.tiles[blockIdx.x * 2 + 1] * kTileCols;
-  const SceneCloud c = a.clouds[ci];
-  const int ncol = min(kTileCols, c.count - j0);
-  const double dzl = a.dir[2 * kCols + lane];
+  const SceneTile tl = tile_begin<false>(a);
   BandLane r;
-  double n_lo, n_hi;
-  band_begin(a, c, j0, ncol, lane, r, &n_lo, &n_hi);
+  BandRule br;
+  br.dzl = a.dir[2 * kCols + lane];
+  band_begin(a, tl.c, tl.j0, tl.ncol, lane, r, &br.n_lo, &br.n_hi);
   int cells = 0;
   const long long e0 = s.b.off[blockIdx.x], e1 = s.b.off[(long long)blockIdx.x + 1];
   const int L = a.lds_triangles;
   for (long long s0 = e0; s0 < e1; s0 += L) {
     const int n = (int)min((long long)L, e1 - s0);
-    for (int k0 = 0; k0 < n; k0 += kCastThreads) {   // (whole waves: band_masks ballots)
-      const int k = k0 + tid;
-      const int f = k < n ? s.b.list[s0 + k] : -1;
-      const bool face = (unsigned)f < (unsigned)c.nf;
-      SceneTri tr;
-      double lo = 0.0, hi = 0.0;
-      if (face) {
-        const int* fi = a.faces + (c.f0 + f) * 3;
-        const V3 p = pose(c, a.verts + (c.v0 + fi[0]) * 3), q = pose(c, a.verts + (c.v0 + fi[1]) * 3), v = pose(c, a.verts + (c.v0 + fi[2]) * 3);
-        tri_setup(p, q, v, tr);
-        band_interval(p, q, v, tr, n_lo, n_hi, &lo, &hi);
-      } else {   // (not a face of this mesh: a triangle that no ray hits, no band)
-        tr.N[0] = tr.N[1] = tr.N[2] = tr.A[0] = tr.A[1] = tr.A[2] = tr.Bv[0] = tr.Bv[1] = tr.Bv[2] = tr.c = 0.0;
-      }
-      tr.id = f; tr.pad = band_masks(face, lo, hi, dzl, lane);
-      if (k < n) tris[k] = tr;
-    }
+    stage_list_chunk<true>(a, tl.c, s.b.list + s0, n, tris, br);
     __syncthreads();
     band_cast(tris, n, wave, r);
     if constexpr (kTrace) if (tid < kBands) cells += band_tally(tris, n, tid);
     __syncthreads();   // the stage is rewritten by the next chunk
   }
-  band_merge_store<kTrace>(a, c, j0, ncol, r, mt, mi);
+  band_merge_store<kTrace>(a, tl.c, tl.j0, tl.ncol, r, mt, mi);
   if constexpr (kTrace) if (tid < kBands) s.cells[(long long)blockIdx.x * kBands + tid] = cells;
 }
 
@@ -904,7 +906,8 @@ struct SceneWS {
   double* d_verts = nullptr; int* d_faces = nullptr;
   double* d_dir = nullptr;                  // sensor tables
   // work buffers, grown on demand
-  SceneCloud* d_clouds = nullptr; int* d_win = nullptr; int* d_rowcount = nullptr; long long* d_rowoff = nullptr; size_t cap_clouds = 0;
+  SceneCloud* d_clouds = nullptr; int* d_win = nullptr; int* d_rowcount = nullptr; long long* d_rowoff = nullptr;   // per cloud
+  size_t cap_clouds = 0, cap_win = 0, cap_rowcount = 0, cap_rowoff = 0;
   int* d_tiles = nullptr; size_t cap_tiles = 0;
   double* d_t = nullptr; int* d_tri = nullptr; size_t cap_t = 0, cap_tri = 0;
   // binned cast: list lengths / fill cursors and offsets per (cloud, tile) of the binned clouds, the triangle lists
@@ -949,6 +952,13 @@ struct SceneTrace {
   bool rows; int32_t* cell_counts /*[kMaxTiles][8]*/; int64_t* cells;    // the band read-back
 };
 
+// one cast launch: one workgroup per tile, none for no tiles; the traced instantiation writes the read-backs' records
+template <class Args>
+void launch_cast(void (*plain)(Args), void (*traced)(Args), bool trace, size_t tiles, size_t lds, hipStream_t stream, const Args& args)
+{
+  if (tiles > 0) hipLaunchKernelGGL(trace ? traced : plain, dim3((unsigned)tiles), dim3(kCastThreads), lds, stream, args);
+}
+
 // B scenes x 2 clouds (or, traced: ONE cloud, pose [4]); results stay on the device
 int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const double* scale, const double* poses, const int64_t* scene_ids, int nclouds,
               uint64_t seed, double sigma, double clip, const SceneTrace* trace)
@@ -979,17 +989,9 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
     }
   }
   HIP_TRY(h, hipSetDevice(h->cfg.device));
-  const size_t nc = (size_t)std::max(nclouds, 1);
-  if (nc > w->cap_clouds || !w->d_clouds) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (w->d_clouds) { hipFree(w->d_clouds); hipFree(w->d_win); hipFree(w->d_rowcount); hipFree(w->d_rowoff); }
-    w->d_clouds = nullptr; w->cap_clouds = 0;
-    HIP_TRY(h, hipMalloc(&w->d_clouds, nc * sizeof(SceneCloud)));
-    HIP_TRY(h, hipMalloc(&w->d_win, nc * 2 * sizeof(int)));
-    HIP_TRY(h, hipMalloc(&w->d_rowcount, nc * kRows * sizeof(int)));
-    HIP_TRY(h, hipMalloc(&w->d_rowoff, nc * kRows * sizeof(long long)));
-    w->cap_clouds = nc;
-  }
+  const size_t nc = (size_t)nclouds;
+  if (grow(h, &w->d_clouds, &w->cap_clouds, nc) || grow(h, &w->d_win, &w->cap_win, nc * 2)) return 1;
+  if (grow(h, &w->d_rowcount, &w->cap_rowcount, nc * kRows) || grow(h, &w->d_rowoff, &w->cap_rowoff, nc * kRows)) return 1;
   if (grow(h, &w->d_offsets, &w->cap_off, (size_t)(B + 1) * 2)) return 1;
   w->B = -1;   // no result until this call has finished
   w->offsets.assign((size_t)(B + 1) * 2, 0);
@@ -1065,39 +1067,19 @@ int run_scene(alignnet_handle* h, const char* fn, const int32_t* mesh, const dou
       a.lds_triangles = L;
       const size_t lds = (size_t)L * sizeof(SceneTri);
       alignnet::ProfScope prof_scope(h, rows ? alignnet::PK_SCENE_BAND : alignnet::PK_SCENE_CAST);
+      // the list staging's tiles come behind the scan staging's; by elevation band the grids, the stage and the tile order are the same, and the cell
+      // counts of the list tiles follow those of the scan tiles, as the tiles do
+      const bool traced = trace != nullptr;
+      const SceneBinCastArgs scan = {a, w->d_binoff, w->d_binlist};
+      SceneBinCastArgs list = scan;
+      list.c.tiles = w->d_tiles + nscan * 2;
       if (rows) {
-        // by elevation band: the same grids, stage and tile order; the cell counts of the list tiles follow those of the scan tiles, as the tiles do
-        SceneBandArgs s;
-        s.b.c = a; s.b.off = w->d_binoff; s.b.list = w->d_binlist; s.cells = w->d_cells;
-        if (nscan > 0) {
-          if (trace)
-            hipLaunchKernelGGL(scene_band_scan_kernel<true>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, s);
-          else
-            hipLaunchKernelGGL(scene_band_scan_kernel<false>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, s);
-        }
-        if (nbt > 0) {
-          s.b.c.tiles = w->d_tiles + nscan * 2;
-          if (trace) {
-            s.cells = w->d_cells + nscan * kBands;
-            hipLaunchKernelGGL(scene_band_list_kernel<true>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, s);
-          } else
-            hipLaunchKernelGGL(scene_band_list_kernel<false>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, s);
-        }
+        launch_cast(scene_band_scan_kernel<false>, scene_band_scan_kernel<true>, traced, nscan, lds, h->stream, SceneBandArgs{scan, w->d_cells});
+        launch_cast(scene_band_list_kernel<false>, scene_band_list_kernel<true>, traced, nbt, lds, h->stream,
+                    SceneBandArgs{list, traced ? w->d_cells + nscan * kBands : nullptr});
       } else {
-        if (nscan > 0) {
-          if (trace)
-            hipLaunchKernelGGL(scene_cast_kernel<true>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, a);
-          else
-            hipLaunchKernelGGL(scene_cast_kernel<false>, dim3((unsigned)nscan), dim3(kCastThreads), lds, h->stream, a);
-        }
-        if (nbt > 0) {
-          SceneBinCastArgs b;
-          b.c = a; b.c.tiles = w->d_tiles + nscan * 2; b.off = w->d_binoff; b.list = w->d_binlist;
-          if (trace)
-            hipLaunchKernelGGL(scene_bincast_kernel<true>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, b);
-          else
-            hipLaunchKernelGGL(scene_bincast_kernel<false>, dim3((unsigned)nbt), dim3(kCastThreads), lds, h->stream, b);
-        }
+        launch_cast(scene_cast_kernel<false>, scene_cast_kernel<true>, traced, nscan, lds, h->stream, a);
+        launch_cast(scene_bincast_kernel<false>, scene_bincast_kernel<true>, traced, nbt, lds, h->stream, list);
       }
     }
     HIP_TRY(h, hipGetLastError());
@@ -1272,45 +1254,42 @@ extern "C" int alignnet_scene_install_dataset(alignnet_handle* h, const float* l
                                   "alignnet_scene_install_dataset");
 }
 
+// what the three read-backs share; bad: what the entry point's own checks found (null: nothing), reported in its place between the common ones
+static int debug_cast(alignnet_handle* h, const char* fn, const char* bad, int32_t mesh, double scale, const double* pose, const SceneTrace& tr)
+{
+  if (!h) return 1;
+  const std::string name(fn);
+  if (!h->scene_ws || sws(h)->M < 0) return fail(h, name + ": no meshes uploaded");
+  if (bad) return fail(h, name + ": " + bad);
+  if (tr.lds_triangles < 0 || tr.lds_triangles > kLdsTriangles)
+    return fail(h, name + ": lds_triangles must be in [0, " + std::to_string(kLdsTriangles) + "] (0 = as shipped)");
+  return run_scene(h, fn, &mesh, &scale, pose, nullptr, 1, 0, 0.0, 0.0, &tr);
+}
+
 extern "C" int alignnet_debug_scene_cast(alignnet_handle* h, int32_t mesh, double scale, const double* pose, int32_t lds_triangles, double* t, int32_t* triangle,
                                          int32_t* window, int32_t* lds_triangles_used)
 {
-  if (!h) return 1;
-  const std::string name("alignnet_debug_scene_cast");
-  if (!h->scene_ws || sws(h)->M < 0) return fail(h, name + ": no meshes uploaded");
-  if (!pose || !t || !triangle || !window || !lds_triangles_used) return fail(h, name + ": null argument");
-  if (lds_triangles < 0 || lds_triangles > kLdsTriangles)
-    return fail(h, name + ": lds_triangles must be in [0, " + std::to_string(kLdsTriangles) + "] (0 = as shipped)");
+  const char* bad = !pose || !t || !triangle || !window || !lds_triangles_used ? "null argument" : nullptr;
   const SceneTrace tr = {lds_triangles, t, triangle, window, lds_triangles_used, false, nullptr, nullptr};
-  return run_scene(h, name.c_str(), &mesh, &scale, pose, nullptr, 1, 0, 0.0, 0.0, &tr);
+  return debug_cast(h, "alignnet_debug_scene_cast", bad, mesh, scale, pose, tr);
 }
 
 extern "C" int alignnet_debug_scene_cast_binned(alignnet_handle* h, int32_t mesh, double scale, const double* pose, int32_t lds_triangles, double* t,
                                                 int32_t* triangle, int32_t* window, int32_t* lds_triangles_used, int32_t* tile_counts, int64_t* entries)
 {
-  if (!h) return 1;
-  const std::string name("alignnet_debug_scene_cast_binned");
-  if (!h->scene_ws || sws(h)->M < 0) return fail(h, name + ": no meshes uploaded");
-  if (!pose || !t || !triangle || !window || !lds_triangles_used || !tile_counts || !entries) return fail(h, name + ": null argument");
-  if (lds_triangles < 0 || lds_triangles > kLdsTriangles)
-    return fail(h, name + ": lds_triangles must be in [0, " + std::to_string(kLdsTriangles) + "] (0 = as shipped)");
+  const char* bad = !pose || !t || !triangle || !window || !lds_triangles_used || !tile_counts || !entries ? "null argument" : nullptr;
   const SceneTrace tr = {lds_triangles, t, triangle, window, lds_triangles_used, true, tile_counts, entries};
-  return run_scene(h, name.c_str(), &mesh, &scale, pose, nullptr, 1, 0, 0.0, 0.0, &tr);
+  return debug_cast(h, "alignnet_debug_scene_cast_binned", bad, mesh, scale, pose, tr);
 }
 
 extern "C" int alignnet_debug_scene_cast_rows(alignnet_handle* h, int32_t mesh, double scale, const double* pose, int32_t lds_triangles, int32_t binned,
                                               int32_t* window, double* t, int32_t* triangle, int32_t* lds_triangles_used, int32_t* cell_counts,
                                               int64_t* cells)
 {
-  if (!h) return 1;
-  const std::string name("alignnet_debug_scene_cast_rows");
-  if (!h->scene_ws || sws(h)->M < 0) return fail(h, name + ": no meshes uploaded");
-  if (!pose || !t || !triangle || !window || !lds_triangles_used || !cell_counts || !cells) return fail(h, name + ": null argument");
-  if (binned != 0 && binned != 1) return fail(h, name + ": binned must be 0 or 1");
-  if (lds_triangles < 0 || lds_triangles > kLdsTriangles)
-    return fail(h, name + ": lds_triangles must be in [0, " + std::to_string(kLdsTriangles) + "] (0 = as shipped)");
+  const char* bad = !pose || !t || !triangle || !window || !lds_triangles_used || !cell_counts || !cells ? "null argument"
+                    : binned != 0 && binned != 1 ? "binned must be 0 or 1" : nullptr;
   std::vector<int32_t> tile_counts(kMaxTiles);
   int64_t entries = 0;
   const SceneTrace tr = {lds_triangles, t, triangle, window, lds_triangles_used, binned != 0, tile_counts.data(), &entries, true, cell_counts, cells};
-  return run_scene(h, name.c_str(), &mesh, &scale, pose, nullptr, 1, 0, 0.0, 0.0, &tr);
+  return debug_cast(h, "alignnet_debug_scene_cast_rows", bad, mesh, scale, pose, tr);
 }
