@@ -1155,6 +1155,11 @@ class Engine:
         """Name of the backbone kernel instantiation the most recent eval forward launched."""
         return KERNEL_NAMES.get(self.get_option("last_backbone_kernel"), "none")
 
+    def last_backbone_wg_waves(self):
+        """Waves per workgroup of that launch: the shipped shape runs as four-wave workgroups, two per CU, on grids that fill the
+        chip twice over, as eight-wave ones below (set_option("infer_wg_waves", 0 / 4 / 8)); both report the same kernel name."""
+        return self.get_option("last_backbone_wg_waves")
+
     def profile_enable(self, on=True):
         self._check(self._lib.alignnet_profile_enable(self._h, int(on)))
 

@@ -427,6 +427,19 @@ static int infer_tile_pts(const alignnet_handle* h, int B)
   return tiles128 <= 128 ? 64 : 128;
 }
 
+// compute units of the handle's device (asked once per device)
+static int device_cus(const alignnet_handle* h)
+{
+  static std::atomic<int> cus[64];
+  const int d = h->cfg.device & 63;
+  int n = cus[d].load(std::memory_order_relaxed);
+  if (n <= 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess || n <= 0) n = 256;
+    cus[d].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
 static size_t backbone_lds_bytes(const alignnet_handle* h, const Stack& st, int ld[2], int B)
 {
   const int kTilePts = infer_tile_pts(h, B);
@@ -465,6 +478,7 @@ static int run_backbone(alignnet_handle* h, const Stack& st, const float* p1, co
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused<128, 68, 132>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused<128, 68, 132, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused_stream<128, 68, 132, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused_duo<128, 132, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_fused<64, 68, 132, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set.mark(h->cfg.device);
@@ -477,6 +491,9 @@ static int run_backbone(alignnet_handle* h, const Stack& st, const float* p1, co
   if (h->ab_tiles_per_wg > 0) per = std::min(ntiles, h->ab_tiles_per_wg);
   a.tiles_per_wg = per;
   const dim3 grid((ntiles + per - 1) / per, 2 * B);
+  const void* bb_func = nullptr;   // what "backbone_wgs_per_cu" / "last_backbone_wg_waves" report (the split-bf16 kernels: eight waves, no occupancy query)
+  int bb_block = kWaves * 64;
+  size_t bb_lds = lds;
   {
   ProfScope prof_scope(h, PK_BACKBONE, true);
   const int sc1 = h->layers[st.first].cout, sc2 = st.n == 3 ? h->layers[st.first + 1].cout : 0;
@@ -538,8 +555,9 @@ static int run_backbone(alignnet_handle* h, const Stack& st, const float* p1, co
     }
   } else if (TP == 64 && !(h->ab & AB_INFER_TILE64) && a.ld[0] == 68 && a.ld[1] == 132 && st.n == 3 && h->layers[st.first + 2].cin == 128 && !(h->ab & AB_NO_LD_CONST)) {
     TIMED_LAUNCH((pointnet_fused<64, 68, 132, 16>), grid, dim3(kWaves * 64), lds, a);   // the shipped shape on 64-point tiles (small batches)
+    bb_func = reinterpret_cast<const void*>(pointnet_fused<64, 68, 132, 16>);
     h->last_kernel = ALIGNNET_KERNEL_POINTNET_FUSED_64_128_K16_TP64;
-  } else if (TP == 64) { TIMED_LAUNCH(pointnet_fused<64>, grid, dim3(kWaves * 64), lds, a); h->last_kernel = ALIGNNET_KERNEL_POINTNET_FUSED_TP64; }
+  } else if (TP == 64) { TIMED_LAUNCH(pointnet_fused<64>, grid, dim3(kWaves * 64), lds, a); bb_func = reinterpret_cast<const void*>(pointnet_fused<64>); h->last_kernel = ALIGNNET_KERNEL_POINTNET_FUSED_TP64; }
   else if (a.ld[0] == 68 && a.ld[1] == 132 && st.n == 3 && h->layers[st.first + 2].cin == 128 && !(h->ab & AB_NO_LD_CONST)) {
     // row-serial last layer by default; the weight-stream schedule it replaced under "ab_last_layer_stream" (and in the cycle-stamp build, whose stamps it carries)
 #ifdef ALIGNNET_KSTAMP
@@ -547,14 +565,27 @@ static int run_backbone(alignnet_handle* h, const Stack& st, const float* p1, co
 #else
     const bool stream = h->ab & AB_LAST_LAYER_STREAM;
 #endif
-    if (stream) { TIMED_LAUNCH((pointnet_fused_stream<128, 68, 132, 16>), grid, dim3(kWaves * 64), lds, a); }
-    else { TIMED_LAUNCH((pointnet_fused<128, 68, 132, 16>), grid, dim3(kWaves * 64), lds, a); }
+    // Four-wave workgroups, two per CU (pointnet_fused_duo), once the grid brings every CU its two: 2 * CUs workgroups or more ("infer_wg_waves" 0;
+    // 4 / 8 fix the form).  A smaller grid keeps the eight-wave kernel: a four-wave workgroup alone on a CU has half the waves.  The tile walk above
+    // already cuts a batch into >= 512 workgroups where it can, so at N = 1024 this is B >= 32.  Measured against the parent's library at N = 1024
+    // (profiles/r08_duo_ab.txt): B = 32 +2.5 %, 40 (640 workgroups: one full round and a quarter) +2.7 %, 64 +2.3 %, 128 +1.6 %, 256 +1.4 %, 1024 +2.5 %;
+    // B = 16 (256 workgroups) stays on eight waves and measures as the parent.
+    const long wgs = (long)grid.x * grid.y;
+    const bool duo = !stream && (h->infer_wg_waves_opt ? h->infer_wg_waves_opt == kDuoWaves : wgs >= 2L * device_cus(h));
+    if (stream) { TIMED_LAUNCH((pointnet_fused_stream<128, 68, 132, 16>), grid, dim3(kWaves * 64), lds, a); bb_func = reinterpret_cast<const void*>(pointnet_fused_stream<128, 68, 132, 16>); }
+    else if (duo) {
+      bb_block = kDuoWaves * 64; bb_lds = ((size_t)128 * 4 + (size_t)128 * 132) * sizeof(float);
+      TIMED_LAUNCH((pointnet_fused_duo<128, 132, 16>), grid, dim3(bb_block), bb_lds, a);
+      bb_func = reinterpret_cast<const void*>(pointnet_fused_duo<128, 132, 16>);
+    } else { TIMED_LAUNCH((pointnet_fused<128, 68, 132, 16>), grid, dim3(kWaves * 64), lds, a); bb_func = reinterpret_cast<const void*>(pointnet_fused<128, 68, 132, 16>); }
     h->last_kernel = ALIGNNET_KERNEL_POINTNET_FUSED_64_128_K16;
   } else if (a.ld[0] == 68 && a.ld[1] == 132 && !(h->ab & AB_NO_LD_CONST)) {   // the shipped widths 64, 128
     TIMED_LAUNCH((pointnet_fused<128, 68, 132>), grid, dim3(kWaves * 64), lds, a);
+    bb_func = reinterpret_cast<const void*>(pointnet_fused<128, 68, 132>);
     h->last_kernel = ALIGNNET_KERNEL_POINTNET_FUSED_64_128;
-  } else { TIMED_LAUNCH(pointnet_fused<128>, grid, dim3(kWaves * 64), lds, a); h->last_kernel = ALIGNNET_KERNEL_POINTNET_FUSED; }
+  } else { TIMED_LAUNCH(pointnet_fused<128>, grid, dim3(kWaves * 64), lds, a); bb_func = reinterpret_cast<const void*>(pointnet_fused<128>); h->last_kernel = ALIGNNET_KERNEL_POINTNET_FUSED; }
   }
+  h->last_bb_func = bb_func; h->last_bb_block = bb_block; h->last_bb_lds = bb_lds; h->last_wg_waves = bb_block / 64;
   HIP_TRY(h, hipGetLastError());
 #ifdef ALIGNNET_KSTAMP
   if (st.first == h->emb_conv.first && true) {
@@ -576,6 +607,7 @@ static int run_backbone_dgcnn(alignnet_handle* h, const Stack& st, const float* 
 {
   DgcnnArgs a;
   a.stamps = nullptr;
+  h->last_bb_func = nullptr; h->last_wg_waves = kWaves;   // ("backbone_wgs_per_cu" is kept for the PointNet kernels)
   a.pcs[0] = p1; a.pcs[1] = p2; a.xform = h->ws.xform; a.nn = h->ws.d_nn; a.pooled = pooled;
   a.tower_stride = tower_stride; a.row_stride = row_stride;
   a.B = B; a.N = h->cfg.num_points; a.k = 20; a.nlayers = st.n;   // k = 20 is hard-coded in the reference (tp8.py:33)
@@ -987,6 +1019,7 @@ extern "C" int alignnet_set_option(alignnet_handle* h, const char* key, int64_t 
   }
   if (k == "ab_tiles_per_wg") { if (value < 0) return fail(h, "ab_tiles_per_wg must be >= 0"); h->ab_tiles_per_wg = (int)value; return 0; }
   if (k == "infer_tile_points") { if (value != 0 && value != 64 && value != 128) return fail(h, "infer_tile_points must be 0 (automatic), 64 or 128"); h->infer_tile_opt = (int)value; return 0; }
+  if (k == "infer_wg_waves") { if (value != 0 && value != 4 && value != 8) return fail(h, "infer_wg_waves must be 0 (automatic), 4 or 8"); h->infer_wg_waves_opt = (int)value; return 0; }
   if (k == "dg_cloud_parts") { if (value < 0 || value > 8) return fail(h, "dg_cloud_parts must be 0 (automatic) .. 8"); h->dg_parts_opt = (int)value; return 0; }
   if (k == "pn_cloud_parts") { if (value < 0 || value > 8) return fail(h, "pn_cloud_parts must be 0 (automatic) .. 8"); h->pn_parts_opt = (int)value; return 0; }
   if (k == "icp_search") { if (value < 0 || value > 2) return fail(h, "icp_search must be 0 (scan), 1 (grid) or 2 (automatic)"); h->icp_search = (int)value; return 0; }
@@ -1029,6 +1062,14 @@ extern "C" int alignnet_get_option(alignnet_handle* h, const char* key, int64_t*
   if (k == "dg_cloud_parts") { *value = h->dg_parts_opt; return 0; }
   if (k == "infer_tile_points") { *value = h->infer_tile_opt; return 0; }
   if (k == "pn_cloud_parts") { *value = h->pn_parts_opt; return 0; }
+  if (k == "infer_wg_waves") { *value = h->infer_wg_waves_opt; return 0; }
+  if (k == "last_backbone_wg_waves") { *value = h->last_wg_waves; return 0; }
+  if (k == "backbone_wgs_per_cu") {
+    int n = 0;
+    if (h->last_bb_func) HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, h->last_bb_func, h->last_bb_block, h->last_bb_lds));
+    *value = n;
+    return 0;
+  }
   if (k == "icp_search") { *value = h->icp_search; return 0; }
   if (k == "icp_plane_ws_budget") { *value = (int64_t)h->icp_plane_ws_budget; return 0; }
   if (k == "icp_plane_chunks") { *value = h->icp_plane_chunks; return 0; }

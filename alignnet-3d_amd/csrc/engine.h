@@ -198,6 +198,11 @@ struct alignnet_handle {
   int dw_side = 0;                 // alignnet_set_option("train_dw_side_stream"): 0 = off, 1 = every stage, 2 = stage 3 only
   unsigned ab = 0;                 // AbBit mask (alignnet_set_option "ab_*")
   int infer_tile_opt = 0;          // "infer_tile_points": eval PointNet backbone tile (0 = from the batch: alignnet_api.hip infer_tile_pts; 64 / 128 fixed)
+  int infer_wg_waves_opt = 0;      // "infer_wg_waves": waves per workgroup of the shipped-shape eval PointNet backbone on 128-point tiles (0 = from the grid: alignnet_api.hip run_backbone; 4 / 8 fixed)
+  int last_wg_waves = 0;           // "last_backbone_wg_waves" (read-only): waves per workgroup of the last eval backbone launch
+  const void* last_bb_func = nullptr;   // "backbone_wgs_per_cu" (read-only): that launch's kernel, block size and dynamic LDS, for the occupancy query
+  int last_bb_block = 0;
+  size_t last_bb_lds = 0;
   int dg_parts_opt = 0;            // "dg_cloud_parts": dgcnn training, workgroups per cloud of the edge kernels (0 = chosen from the batch: alignnet_train.hip dg_parts)
   int pn_parts_opt = 0;            // "pn_cloud_parts": PointNet training, workgroups per cloud of phase 2 / passes B2, B1 (0 = chosen from the batch: alignnet_train.hip pn_parts)
   int ab_tiles_per_wg = 0;         // "ab_tiles_per_wg": eval PointNet backbone, point tiles per workgroup (0 = chosen from the grid size)

@@ -379,6 +379,80 @@ __device__ __forceinline__ void rowserial_chain(const float* arow, int lda, f32x
   }
 }
 
+// The row-serial last layer of one point tile for a workgroup of NW waves: wave w owns channel tiles w, w + NW, ...; arow = this lane's A
+// fragment row of the [128][LD] input buffer.  bw[] holds the image of the wave's first channel tile on entry and, when more_tiles, again on
+// exit.  The first POOL channel tiles of a wave keep their running maximum in pool[] (published once per workgroup: publish_pool); wider last
+// layers publish the rest per tile.
+template <int KGL, int LD, int NW, int POOL>
+__device__ __forceinline__ void rowserial_last_layer(const ConvLayerDev& L, const float* arow, float* dst, int tower, int wave, int lane, bool more_tiles,
+                                                     f32x4 (&bw)[KGL], float (&pool)[POOL])
+{
+  const int CT = (L.cout + 31) >> 5;
+  // a channel tile's maximum is complete when its last row tile's epilogue has run -- under the NEXT channel tile's first chain; only
+  // the wave's last channel tile of a point tile has that epilogue exposed (below the loop)
+  auto retire = [&](float m, int q, bool live, int col) {
+    if (q < POOL) {
+#pragma unroll
+      for (int u = 0; u < POOL; ++u)
+        if (u == q) pool[u] = fmaxf(pool[u], m);
+    } else {   // very wide last layers: beyond the register slots, publish per tile
+      m = fmaxf(m, __shfl_xor(m, 32));
+      if (lane < 32 && live) atomicMax(reinterpret_cast<int*>(dst + col), __float_as_int(m));   // >= 0: monotone bit pattern
+    }
+  };
+  f32x16 acc0, acc1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc1[r] = 0.f;   // nothing pending yet: with scale = shift = 0 the first spliced epilogue yields max(0, 0)
+  float scp = 0.f, shp = 0.f, mx = 0.f;
+  int qp = 0, colp = 0;
+  bool livep = false;
+  for (int ct = wave; ct < CT; ct += NW) {
+    // scale / shift are requested BEFORE the chains: first used a whole chain later
+    const int col = ct * 32 + (lane & 31);
+    const bool live = col < L.cout;
+    const float sc = live ? L.scale[tower * L.cout + col] : 0.f;
+    const float sh = live ? L.shift[tower * L.cout + col] : 0.f;
+    // the channel tile this wave touches next: ct + NW, else its first one on the next point tile; no reload when that is the
+    // resident one (one channel tile per wave) or when the workgroup has no further point tile
+    const int nct = ct + NW < CT ? ct + NW : wave;
+    const bool reload = nct != ct && (ct + NW < CT || more_tiles);
+    const f32x4* wnext = reinterpret_cast<const f32x4*>(L.w) + (size_t)nct * KGL * 64 + lane;
+    f32x4 av[3];
+    av[0] = *reinterpret_cast<const f32x4*>(arow);
+    av[1] = *reinterpret_cast<const f32x4*>(arow + 8);
+    asm volatile("" ::: "memory");
+    rowserial_chain<KGL, 0, false>(arow, LD, bw, wnext, av, acc0, acc1, scp, shp, mx);
+    retire(mx, qp, livep, colp);   // the previous channel tile (first one: max(pool[0], 0), a no-op)
+    mx = 0.f;   // relu folded into the max: max_n relu(v_n) = max(0, max_n v_n)
+    rowserial_chain<KGL, 1, false>(arow, LD, bw, wnext, av, acc1, acc0, sc, sh, mx);
+    rowserial_chain<KGL, 2, false>(arow, LD, bw, wnext, av, acc0, acc1, sc, sh, mx);
+    if (reload) rowserial_chain<KGL, 3, true>(arow, LD, bw, wnext, av, acc1, acc0, sc, sh, mx);
+    else rowserial_chain<KGL, 3, false>(arow, LD, bw, wnext, av, acc1, acc0, sc, sh, mx);
+    scp = sc; shp = sh; qp = (ct - wave) / NW; colp = col; livep = live;
+  }
+  if (wave < CT) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, fmaf(acc1[r], scp, shp));
+    retire(mx, qp, livep, colp);
+  }
+}
+
+// the workgroup's pooled maxima (pool[u] = channel tile wave + u * NW), one atomicMax per (workgroup, channel)
+template <int NW, int POOL>
+__device__ __forceinline__ void publish_pool(const ConvLayerDev& L, float* dst, int wave, int lane, const float (&pool)[POOL])
+{
+  const int CT = (L.cout + 31) >> 5;
+#pragma unroll
+  for (int u = 0; u < POOL; ++u) {
+    const int ct = wave + u * NW, col = ct * 32 + (lane & 31);
+    if (ct < CT) {
+      const float mx = fmaxf(pool[u], __shfl_xor(pool[u], 32));
+      // values are >= 0, so the IEEE bit pattern is monotone as a signed int
+      if (lane < 32 && col < L.cout) atomicMax(reinterpret_cast<int*>(dst + col), __float_as_int(mx));
+    }
+  }
+}
+
 // LD0 / LD1: compile-time LDS row strides of the two activation buffers (0 = from the arguments): immediates instead of address
 // registers in the unrolled hidden-layer epilogues
 // ROWSER: the last layer walks a channel tile's row tiles one after the other (rowserial_chain) instead of k-group outer, row tiles inner
@@ -497,56 +571,8 @@ __device__ __forceinline__ void pointnet_fused_body(const BackboneArgs& a)
   // ---- last layer + max over the tile's points (utils/tf_util.py:350-373) ----
   if constexpr (ROWSER) {
     const ConvLayerDev& L = a.L[a.nlayers - 1];   // three conv layers: input = buffer 1, stride LD1, depth KGL
-    const int CT = (L.cout + 31) >> 5;
-    const float* arow = smem + boff[1] + (lane & 31) * LD1 + (lane >> 5) * 4;
-    float* dst = a.pooled + tower * a.tower_stride + b * a.row_stride;
-    // a channel tile's maximum is complete when its last row tile's epilogue has run -- under the NEXT channel tile's first chain; only
-    // the wave's last channel tile of a point tile has that epilogue exposed (below the loop)
-    auto retire = [&](float m, int q, bool live, int col) {
-      if (q < kPoolRegs) {
-#pragma unroll
-        for (int u = 0; u < kPoolRegs; ++u)
-          if (u == q) pool[u] = fmaxf(pool[u], m);
-      } else {   // very wide last layers: beyond the register slots, publish per tile
-        m = fmaxf(m, __shfl_xor(m, 32));
-        if (lane < 32 && live) atomicMax(reinterpret_cast<int*>(dst + col), __float_as_int(m));   // >= 0: monotone bit pattern
-      }
-    };
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc1[r] = 0.f;   // nothing pending yet: with scale = shift = 0 the first spliced epilogue yields max(0, 0)
-    float scp = 0.f, shp = 0.f, mx = 0.f;
-    int qp = 0, colp = 0;
-    bool livep = false;
-    for (int ct = wave; ct < CT; ct += kWaves) {
-      // scale / shift are requested BEFORE the chains: first used a whole chain later
-      const int col = ct * 32 + (lane & 31);
-      const bool live = col < L.cout;
-      const float sc = live ? L.scale[tower * L.cout + col] : 0.f;
-      const float sh = live ? L.shift[tower * L.cout + col] : 0.f;
-      // the channel tile this wave touches next: ct + kWaves, else its first one on the next point tile; no reload when that is the
-      // resident one (C3 <= 256: one channel tile per wave) or when the workgroup has no further point tile
-      const int nct = ct + kWaves < CT ? ct + kWaves : wave;
-      const bool reload = nct != ct && (ct + kWaves < CT || tile + 1 < tile_hi);
-      const f32x4* wnext = reinterpret_cast<const f32x4*>(L.w) + (size_t)nct * KGL * 64 + lane;
-      f32x4 av[3];
-      av[0] = *reinterpret_cast<const f32x4*>(arow);
-      av[1] = *reinterpret_cast<const f32x4*>(arow + 8);
-      asm volatile("" ::: "memory");
-      rowserial_chain<KGL, 0, false>(arow, LD1, bw, wnext, av, acc0, acc1, scp, shp, mx);
-      retire(mx, qp, livep, colp);   // the previous channel tile (first one: max(pool[0], 0), a no-op)
-      mx = 0.f;   // relu folded into the max: max_n relu(v_n) = max(0, max_n v_n)
-      rowserial_chain<KGL, 1, false>(arow, LD1, bw, wnext, av, acc1, acc0, sc, sh, mx);
-      rowserial_chain<KGL, 2, false>(arow, LD1, bw, wnext, av, acc0, acc1, sc, sh, mx);
-      if (reload) rowserial_chain<KGL, 3, true>(arow, LD1, bw, wnext, av, acc1, acc0, sc, sh, mx);
-      else rowserial_chain<KGL, 3, false>(arow, LD1, bw, wnext, av, acc1, acc0, sc, sh, mx);
-      scp = sc; shp = sh; qp = (ct - wave) / kWaves; colp = col; livep = live;
-    }
-    if (wave < CT) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, fmaf(acc1[r], scp, shp));
-      retire(mx, qp, livep, colp);
-    }
+    rowserial_last_layer<KGL, LD1, kWaves, kPoolRegs>(L, smem + boff[1] + (lane & 31) * LD1 + (lane >> 5) * 4,
+                                                      a.pooled + tower * a.tower_stride + b * a.row_stride, tower, wave, lane, tile + 1 < tile_hi, bw, pool);
   } else {
     const int l = a.nlayers - 1;
     const ConvLayerDev& L = a.L[l];
@@ -589,20 +615,7 @@ __device__ __forceinline__ void pointnet_fused_body(const BackboneArgs& a)
     }
   }
   }   // tile loop
-  {
-    const ConvLayerDev& L = a.L[a.nlayers - 1];
-    const int CT = (L.cout + 31) >> 5;
-    float* dst = a.pooled + tower * a.tower_stride + b * a.row_stride;
-#pragma unroll
-    for (int u = 0; u < kPoolRegs; ++u) {
-      const int ct = wave + u * kWaves, col = ct * 32 + (lane & 31);
-      if (ct < CT) {
-        const float mx = fmaxf(pool[u], __shfl_xor(pool[u], 32));
-        // values are >= 0, so the IEEE bit pattern is monotone as a signed int
-        if (lane < 32 && col < L.cout) atomicMax(reinterpret_cast<int*>(dst + col), __float_as_int(mx));
-      }
-    }
-  }
+  publish_pool<kWaves, kPoolRegs>(a.L[a.nlayers - 1], a.pooled + tower * a.tower_stride + b * a.row_stride, wave, lane, pool);
 }
 
 // the shipped shape on 128-point tiles runs the row-serial last layer; every other instantiation the weight-stream one
@@ -616,6 +629,169 @@ template <int TP, int LD0, int LD1, int KGL>
 __global__ __launch_bounds__(kWaves * 64, 2) void pointnet_fused_stream(const BackboneArgs a)
 {
   pointnet_fused_body<TP, LD0, LD1, KGL, false>(a);
+}
+
+// ---------------------------------------------------------------------------------
+// pointnet_fused_duo: the shipped shape (64 -> 128 -> C3) on 128-point tiles as FOUR-wave workgroups, two of them per CU.  The eight-wave
+// kernel's 102 KB of LDS leaves a CU one workgroup, and while that one is in its prologue nothing on the CU has an MFMA to issue; two
+// independent workgroups put one's prologue under the other's last layer without any hand scheduling.  They fit because the h1 buffer goes:
+// one [128][LD] activation buffer + the xyz staging = 69.6 KB.  Wave w owns rows 32 w .. 32 w + 31 through lift and hidden layer:
+//   lift its 32 points into columns 0 .. 63 of its own rows; read them back as A fragments (8 k-groups, 32 registers); run the 64 -> 128
+//   layer for these rows, one 32-MFMA chain per channel tile, and write relu(acc * scale + shift) over the same rows.
+// Nothing before the hidden layer's output crosses a wave, so a tile has two workgroup barriers ("h2 complete", "readers done") instead of
+// four.  The last layer is rowserial_last_layer with ct = wave, wave + 4, ...  Per (row, column) every product is accumulated in ascending
+// k from a zero C operand and the lift keeps its expression: outputs are bit-identical to pointnet_fused<128, 68, 132, 16>.
+// ---------------------------------------------------------------------------------
+constexpr int kDuoWaves = 4;
+
+// One channel tile of the hidden layer for the wave's 32 rows: acc = ah[] * bw[] as one dependent chain (a single chain issues at the pipe's
+// rate: rowserial_chain).  PREV: the previous channel tile's accumulator goes through scale / shift / relu into outp[] under k-groups 1 .. 4,
+// four registers per k-group.  Every fragment of bw[] is re-requested right after its last use for the channel tile that follows (wnext).
+template <int KG, int LD, bool PREV>
+__device__ __forceinline__ void duo_hidden_chain(const f32x4 (&ah)[KG], f32x4 (&bw)[KG], const f32x4* __restrict__ wnext, int lane, f32x16& acc,
+                                                 const f32x16& prev, float scp, float shp, float* outp)
+{
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // the lane's byte offset is made opaque per chain: left visible, hipcc forms every fragment address of all four chains once per workgroup
+  // (loop-invariant 64-bit pairs) and spills them across the tile loop.  (The offset, not the pointer: an opaque pointer loses its address
+  // space and the loads become flat ones, which count on the LDS counter as well.)
+  unsigned voff = lane * 16u;
+  asm volatile("" : "+v"(voff));
+  const f32x4* wl = reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(wnext) + voff);
+#pragma unroll
+  for (int kg = 0; kg < KG; ++kg) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (kg == 0 && s == 0) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ah[kg][s], bw[kg][s], zero, 0, 0, 0);
+      else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ah[kg][s], bw[kg][s], acc, 0, 0, 0);
+    }
+    if (PREV && kg >= 1 && kg <= 4) {
+#pragma unroll
+      for (int r = (kg - 1) * 4; r < kg * 4; ++r) outp[((r & 3) + 8 * (r >> 2)) * LD] = fmaxf(fmaf(prev[r], scp, shp), 0.f);
+    }
+    bw[kg] = wl[kg * 64];
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+template <int TP, int LD, int KGL>
+__global__ __launch_bounds__(kDuoWaves * 64, 2) void pointnet_fused_duo(const BackboneArgs a)
+{
+  static_assert(TP == 128 && LD == 132 && KGL == 16, "the shipped shape on 128-point tiles");
+  constexpr int KGH = 8, CTH = (LD - 4) / 32;   // hidden layer: 64 -> 128
+  constexpr int kPoolRegs = 8;                  // C3 = 1024: eight channel tiles per wave, still one publish per workgroup
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int cloud = blockIdx.y;
+  const int tower = cloud >= a.B, b = cloud - tower * a.B;
+  float* xs = smem + wave * 32 * 4;            // [32][4]: this wave's points
+  float* hrows = smem + TP * 4 + wave * 32 * LD;   // this wave's rows of the [TP][LD] activation buffer
+  const ConvLayerDev& L1 = a.L[1];
+  const ConvLayerDev& L2 = a.L[2];
+  float* dst = a.pooled + tower * a.tower_stride + b * a.row_stride;
+  float pool[kPoolRegs];
+#pragma unroll
+  for (int u = 0; u < kPoolRegs; ++u) pool[u] = 0.f;
+  const int ntiles_all = (a.N + TP - 1) / TP;
+  const int tile_lo = blockIdx.x * a.tiles_per_wg, tile_hi = min(ntiles_all, tile_lo + a.tiles_per_wg);
+  // xyz of the tile to come (lanes 0 .. 31: one point of the wave's rows each), requested one tile ahead
+  float nx = 0.f, ny = 0.f, nz = 0.f;
+  auto request_xyz = [&](int t) {
+    if (lane < 32) {
+      const int n = min(t * TP + wave * 32 + lane, a.N - 1);   // tail rows repeat the last point: max unaffected
+      const float* p = a.pcs[tower] + ((size_t)b * a.N + n) * 3;
+      nx = p[0]; ny = p[1]; nz = p[2];
+    }
+  };
+  request_xyz(tile_lo);
+  // once per workgroup: the cloud's frame, the lift's weights / scale / shift of this lane's two channels, the hidden layer's scale / shift
+  // of its four, and the first weight images of both MFMA layers (the first tile's prologue covers their round trips)
+  float xf[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) xf[i] = a.xform[(size_t)cloud * 12 + i];
+  float l0w[2][5];
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    const ConvLayerDev& L0 = a.L[0];
+    const int c = (lane & 31) + 32 * g;
+    const bool live = c < L0.cout;
+    l0w[g][0] = live ? L0.w[c] : 0.f; l0w[g][1] = live ? L0.w[L0.cout + c] : 0.f; l0w[g][2] = live ? L0.w[2 * L0.cout + c] : 0.f;
+    l0w[g][3] = live ? L0.scale[tower * L0.cout + c] : 0.f; l0w[g][4] = live ? L0.shift[tower * L0.cout + c] : 0.f;
+  }
+  float hsc[CTH], hsh[CTH];
+#pragma unroll
+  for (int ct = 0; ct < CTH; ++ct) {
+    const int col = ct * 32 + (lane & 31);
+    const bool live = col < L1.cout;
+    hsc[ct] = live ? L1.scale[tower * L1.cout + col] : 0.f;
+    hsh[ct] = live ? L1.shift[tower * L1.cout + col] : 0.f;
+  }
+  const f32x4* w1p = reinterpret_cast<const f32x4*>(L1.w);   // channel tile ct's image at w1p + ct * KGH * 64 (wave-uniform) + lane
+  f32x4 bh[KGH], bw[KGL];
+#pragma unroll
+  for (int kg = 0; kg < KGH; ++kg) bh[kg] = w1p[kg * 64 + lane];
+  if (wave * 32 < L2.cout) {
+    const f32x4* wp = reinterpret_cast<const f32x4*>(L2.w) + (size_t)wave * KGL * 64 + lane;
+#pragma unroll
+    for (int kg = 0; kg < KGL; ++kg) bw[kg] = wp[kg * 64];
+  }
+  // (No start stagger between the two workgroups of a CU: an s_sleep of 2 / 4 / 8 k cycles for the waves in the odd wave slots, once before the
+  // first tile, measured inside the run-to-run spread -- DESIGN.md 4.1, round 8.)
+  for (int tile = tile_lo; tile < tile_hi; ++tile) {
+    // ---- prologue: p' = (p - c) @ R   (models/tp8.py:106,113,122,127) into the wave's own staging rows ----
+    if (lane < 32) {
+      const float x = nx - xf[0], y = ny - xf[1], z = nz - xf[2];
+      xs[lane * 4 + 0] = x * xf[3] + y * xf[6] + z * xf[9];
+      xs[lane * 4 + 1] = x * xf[4] + y * xf[7] + z * xf[10];
+      xs[lane * 4 + 2] = x * xf[5] + y * xf[8] + z * xf[11];
+    }
+    if (tile + 1 < tile_hi) request_xyz(tile + 1);
+    if (tile != tile_lo) __syncthreads();   // readers done: the previous tile's last layer has left the activation buffer
+    __builtin_amdgcn_wave_barrier();
+
+    // ---- layer 0: K = 3 lift on the VALU; a 32-lane group writes one row, 32 consecutive channels.  Four rows' points are read in front of
+    // their eight outputs (the compiler cannot move an LDS read above the LDS writes itself) ----
+#pragma unroll
+    for (int rb = 0; rb < 16; rb += 4) {
+      f32x4 p[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) p[i] = *reinterpret_cast<const f32x4*>(xs + ((rb + i) * 2 + half) * 4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          const float acc = fmaf(p[i][2], l0w[g][2], fmaf(p[i][1], l0w[g][1], p[i][0] * l0w[g][0]));
+          hrows[((rb + i) * 2 + half) * LD + (lane & 31) + 32 * g] = fmaxf(fmaf(acc, l0w[g][3], l0w[g][4]), 0.f);
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+
+    // ---- hidden layer in place: the rows' A fragments into registers, then four chains whose outputs overwrite the rows ----
+    f32x4 ah[KGH];
+    {
+      const float* arow = hrows + (lane & 31) * LD + half * 4;
+#pragma unroll
+      for (int kg = 0; kg < KGH; ++kg) ah[kg] = *reinterpret_cast<const f32x4*>(arow + kg * 8);
+    }
+    asm volatile("" ::: "memory");
+    {
+      float* outp = hrows + 4 * half * LD + (lane & 31);   // accumulator register r -> row (r & 3) + 8 (r >> 2) + 4 half
+      f32x16 acc0, acc1;
+      duo_hidden_chain<KGH, LD, false>(ah, bh, w1p + 1 * KGH * 64, lane, acc0, acc0, 0.f, 0.f, outp);   // (no previous chain: prev is not read)
+      duo_hidden_chain<KGH, LD, true>(ah, bh, w1p + 2 * KGH * 64, lane, acc1, acc0, hsc[0], hsh[0], outp);
+      duo_hidden_chain<KGH, LD, true>(ah, bh, w1p + 3 * KGH * 64, lane, acc0, acc1, hsc[1], hsh[1], outp + 32);
+      duo_hidden_chain<KGH, LD, true>(ah, bh, w1p, lane, acc1, acc0, hsc[2], hsh[2], outp + 64);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) outp[96 + ((r & 3) + 8 * (r >> 2)) * LD] = fmaxf(fmaf(acc1[r], hsc[3], hsh[3]), 0.f);
+    }
+    __syncthreads();   // h2 complete
+
+    // ---- last layer + max over the tile's points (utils/tf_util.py:350-373) ----
+    rowserial_last_layer<KGL, LD, kDuoWaves, kPoolRegs>(L2, smem + TP * 4 + (lane & 31) * LD + half * 4, dst, tower, wave, lane, tile + 1 < tile_hi, bw, pool);
+  }
+  publish_pool<kDuoWaves, kPoolRegs>(L2, dst, wave, lane, pool);
 }
 
 // ---------------------------------------------------------------------------------

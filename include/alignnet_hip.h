@@ -773,6 +773,9 @@ int alignnet_tracklet_extract_frustum(alignnet_handle* h, const int32_t* frames,
  *   "dg_cloud_parts" (dgcnn training: workgroups per cloud of the edge kernels, 0 = as many as fill the chip at this batch, 1 .. 8 = fixed; results agree up to the grouping of partial sums);
  *   "infer_tile_points" (eval PointNet backbone: points per workgroup tile; 0 = automatic -- 64-point tiles while the 128-point tiling would cover at most half of the
  *   256 CUs (2B x ceil(N / 128) <= 128: B <= 8 at N = 1024; 0.19 -> 0.134 ms per step at B = 1, 0.198 -> 0.142 at B = 8), 128 otherwise; 64 / 128 = fixed; bit-identical outputs);
+ *   "infer_wg_waves" (eval PointNet backbone, shipped shape on 128-point tiles: waves per workgroup; 8 = pointnet_fused<128, 68, 132, 16>, one workgroup per CU;
+ *   4 = pointnet_fused_duo<128, 132, 16>, two independent workgroups per CU, one's prologue under the other's last layer; 0 = automatic -- 4 once the grid has
+ *   two workgroups for every CU, 8 below; other shapes, "ab_last_layer_stream" and 64-point tiles run eight waves whatever it says; bit-identical outputs);
  *   "pn_cloud_parts" (the same split for the per-cloud kernels both backbones share: phase 2 / the first-layer Gram, phase 3 -- the lift to C3 with its running
  *   arg-extreme and Gram, the parts' extremes folded exactly in tile order -- and passes B2, B1; the chip is full from 2B = 256 (128-point-tile kernels) or 512
  *   clouds, the reference's shipped batch of 128 brings 256; 0 = automatic, 1 .. 8 = fixed).
@@ -780,7 +783,9 @@ int alignnet_tracklet_extract_frustum(alignnet_handle* h, const int32_t* frames,
  *   ablation switches exist only in the separate ablation build (csrc/ablate.h, `make ablate`).
  * Read-only keys (alignnet_get_option; parity tests use them to assert which kernel instantiation ran, since the shipped
  * widths 64 / 128 dispatch to kernels with the widths compiled in):
- * "last_backbone_kernel": ALIGNNET_KERNEL_* of the most recent eval-mode backbone launch;
+ * "last_backbone_kernel": ALIGNNET_KERNEL_* of the most recent eval-mode backbone launch (the four- and the eight-wave form of the shipped shape
+ *   report the same number);  "last_backbone_wg_waves": the waves per workgroup of that launch;  "backbone_wgs_per_cu": what
+ *   hipOccupancyMaxActiveBlocksPerMultiprocessor answers for its kernel, block size and dynamic LDS (PointNet fp32 kernels; 0 otherwise);
  * "comm_world": number of ranks of the communicator (0 = none); "comm_buckets": bucket all-reduces the last step issued;
  * "sync_collectives": sync_bn / global_loss collectives (per-layer all-reduces, gathers) the last training step issued;
  * "comm_order": issue order of the last training step's backward, one decimal digit per event: 1..3 = backward of stage 1..3 queued,
