@@ -150,6 +150,7 @@ class Engine:
             raise EngineError(self._lib.alignnet_last_error(None).decode())
         self.num_points = self._c.num_points
         self.num_bins = self._c.num_bins
+        self._dataset_sizes = None   # source sizes of the uploaded dataset's rows
         self._inflight = []   # output arrays of submitted, not yet waited-for batches (forward_submit / forward_wait)
 
     def close(self):
@@ -319,6 +320,7 @@ class Engine:
         assert off[-1, 0] == p1.shape[0] and off[-1, 1] == p2.shape[0], "offsets do not cover the point blobs"
         self._check(self._lib.alignnet_dataset_upload(self._h, _fp(p1), _fp(p2), off.ctypes.data_as(C.POINTER(C.c_int64)),
                                                       _fp(lab), off.shape[0] - 1))
+        self._dataset_sizes = np.diff(off[:, 0])   # source sizes per row (evaluate_registration_rows splits its correspondences by them)
 
     @staticmethod
     def _rows(rows):
@@ -389,6 +391,52 @@ class Engine:
             self._check(self._lib.alignnet_icp_register_dataset(self._h, rp, r.size, dp(init), float(radius), int(its), ICP_FULL_ROTATION,
                                                                 dp(out), dp(fit), dp(rmse), itp))
         return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+
+    # ---- evaluation of given transforms without ground truth (alignnet_evaluate_registration*; definition: tests/reg_eval_ref.py) ----
+    def _evaluate_registration(self, call, B, sizes, transforms, threshold, centers, want_information, want_correspondences):
+        """call(tf, threshold, centers, fitness, rmse, information, correspondences) -> rc with the pointers bound; sizes: the B source sizes."""
+        tf = np.ascontiguousarray(transforms, np.float64).reshape(B, 16)
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        cen = None if centers is None else np.ascontiguousarray(centers, np.float64).reshape(B, 3)
+        fit, rmse = np.empty(B, np.float64), np.empty(B, np.float64)
+        info = np.empty((B, 6, 6), np.float64) if want_information else None
+        corr = np.full(max(int(np.sum(sizes)), 1), -1, np.int32) if want_correspondences else None
+        self._check(call(dp(tf), float(threshold), dp(cen), dp(fit), dp(rmse), dp(info), None if corr is None else corr.ctypes.data_as(C.POINTER(C.c_int32))))
+        res = dict(fitness=fit, rmse=rmse)
+        if want_information:
+            res["information"] = info
+        if want_correspondences:
+            ends = np.cumsum(sizes, dtype=np.int64)
+            res["correspondences"] = [corr[e - n:e].copy() for e, n in zip(ends, sizes)]
+        return res
+
+    def evaluate_registration(self, sources, targets, transforms, threshold=0.02, centers=None, want_information=False, want_correspondences=False):
+        """Fitness and inlier RMSE of given transforms [B, 4, 4] on the pairs (sources[b], targets[b]) -- Open3D's evaluate_registration: ONE
+        correspondence step, nearest target within `threshold` of every transformed source point -- with no ground truth involved.  Returns
+        dict(fitness [B], rmse [B]); want_information adds information [B, 6, 6] (Open3D's get_information_matrix_from_point_clouds about
+        `centers` [B, 3], default the origin), want_correspondences a list of int32 arrays (target index per source point, -1: no inlier).
+        The search is the engine's icp_search option."""
+        fn = self._register_fn("alignnet_evaluate_registration")
+        B = len(sources)
+        off = np.zeros((B + 1, 2), np.int64)
+        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
+        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
+        p1, p2 = cat(sources), cat(targets)
+        offp = off.ctypes.data_as(C.POINTER(C.c_int64))
+        return self._evaluate_registration(lambda *a: fn(self._h, _fp(p1), _fp(p2), offp, B, *a), B, np.diff(off[:, 0]), transforms, threshold, centers,
+                                           want_information, want_correspondences)
+
+    def evaluate_registration_rows(self, rows, transforms, threshold=0.02, centers=None, want_information=False, want_correspondences=False):
+        """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows; the correspondences follow `rows`."""
+        fn = self._register_fn("alignnet_evaluate_registration_dataset")
+        r, rp = self._rows(rows)
+        sizes = np.zeros(r.size, np.int64)
+        if want_correspondences:
+            if self._dataset_sizes is None:
+                raise EngineError("evaluate_registration_rows: want_correspondences needs the source sizes of a dataset uploaded with upload_dataset")
+            sizes = self._dataset_sizes[np.clip(r, 0, len(self._dataset_sizes) - 1)]   # (a row out of range is the library's to report)
+        return self._evaluate_registration(lambda *a: fn(self._h, rp, r.size, *a), r.size, sizes, transforms, threshold, centers, want_information,
+                                           want_correspondences)
 
     def debug_icp_scan(self, source, target, T, radius=0.1, constrained=True, lds_points=0):
         """Test hook: ONE evaluation (correspondence step at the 4x4 `T`) of one pair by the ICP kernel's own scan, with what it decided per
@@ -834,6 +882,7 @@ class Engine:
         lab = np.ascontiguousarray(labels, np.float32).reshape(-1, 12)
         assert hasattr(self, "_scene_offsets") and lab.shape[0] == self._scene_offsets.shape[0] - 1, "one label row per generated scene"
         self._check(self._lib.alignnet_scene_install_dataset(self._h, _fp(lab)))
+        self._dataset_sizes = np.diff(self._scene_offsets[:, 0])
 
     # ---- KITTI tracklet extraction (csrc/alignnet_crop.hip; alignnet3d/tracklets.py builds the arguments) ----
     def tracklet_upload_scans(self, scans):
@@ -911,6 +960,7 @@ class Engine:
         lab = np.ascontiguousarray(labels, np.float32).reshape(-1, 12)
         assert hasattr(self, "_tracklet_offsets") and lab.shape[0] == self._tracklet_offsets.shape[0] - 1, "one label row per extracted pair"
         self._check(self._lib.alignnet_tracklet_install_dataset(self._h, _fp(lab)))
+        self._dataset_sizes = np.diff(self._tracklet_offsets[:, 0])
 
     def debug_scene_cast(self, mesh, scale, pose, lds_triangles=0, binned=False, rows=False):
         """Test hook: ONE cloud by the shipped cast kernel, no noise.  Returns dict(t [64, 4500] float64 (inf = miss), triangle [64, 4500] (-1), window =

@@ -15,7 +15,11 @@ read_image_size reads (W, H) from a PNG's header (all the reference takes from t
 What is this project's own: the reference's script that chooses WHICH (frame, frame) pairs of a track become examples is unpublished, the
 selection of the `Hard` variants included; `pairs` therefore pairs one track id in frames f and f + gap, and `gap` and `min_points` are
 options of this project, not the reference's.  No colour columns are produced (the reference reads [:, :3] everywhere, and colours need the
-camera images' pixels); FromHeldScene is not provided."""
+camera images' pixels).
+
+Held data -- a tracker's own output, no ground truth -- is FromHeldScene's (:1036-1052): the two crops as they are, zero labels, and the meta keys
+`trackid`, `frames`, `timestamps` that evaluation.evaluate_held turns into a speed per track.  held_pairs / held_meta / extract(..., held=True) make
+it from label files in the same 17-column format (what trackers emit) and a timestamp per frame."""
 import os
 import struct
 from collections import namedtuple
@@ -82,6 +86,50 @@ def pairs(labels, classes=("Car",), gap=1, min_points=0, counts=None, seq=0):
         out.append(Pair(int(seq), (f, f + gap), t, labels.cls[i], float(labels.truncated[i]), float(labels.occluded[i]), labels.box[i].copy(),
                         labels.box[j].copy(), labels.bbox2d[i].copy(), labels.bbox2d[j].copy(), (i, j)))
     return out
+
+
+HeldPair = namedtuple("HeldPair", Pair._fields + ("timestamps",))
+
+
+def read_timestamps(path):
+    """A timestamp file: one value in seconds per frame, line f = frame f.  Returns a float64 array."""
+    with open(path) as fh:
+        return np.array([float(line) for line in fh if line.strip()], np.float64)
+
+
+def rate_timestamps(frame_rate=10.0):
+    """frame -> frame / frame_rate seconds, for data without a timestamp file (KITTI's scanner turns at 10 Hz)."""
+    if not frame_rate > 0:
+        raise ValueError("frame_rate = %r: expected > 0" % (frame_rate,))
+    return lambda frame: float(frame) / float(frame_rate)
+
+
+def held_pairs(labels, classes, timestamps, seq, gap=1, min_points=0, counts=None):
+    """The pairs of pairs(...) as HeldPair: the same fields plus timestamps = (seconds of frame f, seconds of frame f + gap).  timestamps: a sequence
+    indexed by frame number (read_timestamps) or a callable frame -> seconds (rate_timestamps).  As in pairs, no pair is made across a hole in a track."""
+    at = timestamps if callable(timestamps) else lambda f: float(timestamps[f])
+    out = []
+    for p in pairs(labels, classes, gap=gap, min_points=min_points, counts=counts, seq=seq):
+        try:
+            ts = (float(at(p.frames[0])), float(at(p.frames[1])))
+        except IndexError:
+            raise ValueError("sequence %d: no timestamp for frame %d or %d (%d given)" % (seq, p.frames[0], p.frames[1], len(timestamps))) from None
+        out.append(HeldPair(*p, ts))
+    return out
+
+
+HELD_TRACKID_STRIDE = 10000
+
+
+def held_meta(pair):
+    """Scene.save_meta + FromHeldScene.additional_meta (:986-997, 1043-1052): the base keys with zero positions, angles and translation (there is no
+    ground truth), then class, frames, timestamps, trackid, in that order.  trackid = seq * 10000 + the label file's track id: THIS PROJECT'S rule --
+    the reference's ids come from an unpublished tracker dump; all evaluate_held asks of them is that one object keeps one id and two objects differ,
+    which holds for up to 10000 tracks per sequence.  `class` is the label's (the reference writes 'Car' for every held track)."""
+    zero = np_to_str(np.zeros(3))
+    return {"start_position": zero, "start_angle": 0.0, "end_position": zero, "end_angle": 0.0, "translation": zero, "rel_angle": 0.0,
+            "class": pair.cls, "frames": [int(pair.frames[0]), int(pair.frames[1])], "timestamps": [float(pair.timestamps[0]), float(pair.timestamps[1])],
+            "trackid": int(pair.seq) * HELD_TRACKID_STRIDE + int(pair.track)}
 
 
 def filter_min_points(pair_list, offsets, min_points):
@@ -161,14 +209,17 @@ def meta(pair, vo1=None, vo2=None):
             "bbox3ds": [np_to_str(pair.box1), np_to_str(pair.box2)], "bbox2ds": [np_to_str(pair.bbox2d1), np_to_str(pair.bbox2d2)]}
 
 
-def extract_args(pair_list, frame_index):
+def extract_args(pair_list, frame_index, held=False):
     """(frames [B, 2] int32, boxes [B, 2, 7] float64, dz [B, 2] float32, labels [B, 12] float32) of Engine.tracklet_extract /
-    tracklet_install_dataset: frame_index maps a pair's frame numbers to positions in the uploaded scans; dz = (0, float32(z_difference))."""
+    tracklet_install_dataset: frame_index maps a pair's frame numbers to positions in the uploaded scans; dz = (0, float32(z_difference)).
+    held=True (FromHeldScene): dz and the twelve label columns are zeros -- there is no ground truth to take z_difference from."""
     B = len(pair_list)
     frames, boxes, dz, lab = np.zeros((B, 2), np.int32), np.zeros((B, 2, 7)), np.zeros((B, 2), np.float32), np.zeros((B, 12), np.float32)
     for i, p in enumerate(pair_list):
         frames[i] = frame_index[p.frames[0]], frame_index[p.frames[1]]
         boxes[i, 0], boxes[i, 1] = p.box1, p.box2
+        if held:
+            continue
         l12, zd = labels12(p.box1, p.box2)
         dz[i, 1] = np.float32(zd)
         lab[i] = l12
@@ -238,12 +289,13 @@ def frustum_args(pair_list, frame_index, calib, image_size):
     return rects, proj, image
 
 
-def extract(engine, scans, pair_list, install=False, from_bbox2d=False, calib=None, image_size=None, clip=2.0):
+def extract(engine, scans, pair_list, install=False, from_bbox2d=False, calib=None, image_size=None, clip=2.0, held=False):
     """Crop `pair_list` (pairs of ONE sequence) on the GPU.  scans: {frame number: float32 [n, 3 or 4]} or a list indexed by frame number;
     the frames the pairs use are uploaded in one call.  Returns the offsets table [B + 1, 2]; the crops stay on the device --
     engine.tracklet_read() copies them out, install=True makes them the HBM-resident dataset with the pairs' labels (sample_batch,
     train_step_rows, register_rows, ... then work on them).  from_bbox2d=True: the image-frustum crop to the pairs' bbox2d1 / bbox2d2 in
-    place of the 3D boxes (calib, image_size: see frustum_args; clip: the reference's clip_distance); labels and dz are the same."""
+    place of the 3D boxes (calib, image_size: see frustum_args; clip: the reference's clip_distance); labels and dz are the same.
+    held=True: both crops as they are (no z_difference subtracted from the second) and zero labels, as FromHeldScene has them."""
     if from_bbox2d and (calib is None or image_size is None):
         raise ValueError("from_bbox2d=True needs calib and image_size")
     get = scans.__getitem__
@@ -253,7 +305,7 @@ def extract(engine, scans, pair_list, install=False, from_bbox2d=False, calib=No
         engine.tracklet_upload_scans((np.zeros((0, 4), np.float32), np.zeros(1, np.int64)))
     else:
         engine.tracklet_upload_scans([get(f) for f in used])
-    frames, boxes, dz, lab = extract_args(pair_list, index)
+    frames, boxes, dz, lab = extract_args(pair_list, index, held=held)
     if from_bbox2d:
         rects, proj, image = frustum_args(pair_list, index, calib, image_size)
         off = engine.tracklet_extract_frustum(frames, rects, proj, image, dz, clip)

@@ -171,6 +171,29 @@ struct IcpGridArgs : IcpArgs {
   const long long* ws_off;      // [B] byte offset of pair b's part
 };
 
+// alignnet_evaluate_registration*: ONE evaluation at the given transform (icp_kernel<false, false, kGrid, true>) and, over its inliers, the sums of
+// Open3D's GetInformationMatrixFromPointClouds.  With (x, y, z) = the inlier's TARGET point minus the pair's centre, G^T G of the three rows
+// [0, z, -y, 1, 0, 0], [-z, 0, x, 0, 1, 0], [y, -x, 0, 0, 0, 1] has 21 upper entries of which six are zero, three are the count and the other twelve are
+// nine distinct sums and their negatives: eleven accumulators with the count and the squared distances (kIcpSumsEval), fixed order, mirrored at the end
+struct IcpEvalArgs : IcpGridArgs {
+  const double* centers;        // [B][3], or null: the origin
+  double* info;                 // [B][36] row-major, or null: the sums are not taken
+  int* corr;                    // per source point the inlier's target (original index) or -1, or null
+  const long long* corr_off;    // [B] where pair b's source range starts in corr
+};
+constexpr int kIcpSumsEval = 11;    // count, dist2, y^2 + z^2, x^2 + z^2, x^2 + y^2, xy, xz, yz, x, y, z
+// entry (i, j), i <= j, of the matrix from the reduced sums t; "+ 0.0" keeps a negated zero sum from showing as -0
+__device__ __forceinline__ double icp_info_entry(const double* t, int i, int j)
+{
+  switch (i * 6 + j) {
+    case 0: return t[2];  case 1: return -t[5] + 0.0;  case 2: return -t[6] + 0.0;  case 4: return -t[10] + 0.0;  case 5: return t[9];
+    case 7: return t[3];  case 8: return -t[7] + 0.0;  case 9: return t[10];  case 11: return -t[8] + 0.0;
+    case 14: return t[4];  case 15: return -t[9] + 0.0;  case 16: return t[8];
+    case 21: case 28: case 35: return t[0];
+    default: return 0.0;
+  }
+}
+
 // path record of a quad (tr_paths): bits 2 s, 2 s + 1 = what lane s did with its slice of the LDS-resident targets, bit 8 = the winner came from the tail
 constexpr int kIcpPathNone = 0, kIcpPathSingle = 1, kIcpPathWalk = 2, kIcpPathTailWon = 256;
 
@@ -196,11 +219,14 @@ __device__ __forceinline__ void block_reduce(double (&v)[N], double* red /*[wave
 // kTrace: the SAME scan, and behind the quad's merge one record per source point (IcpArgs::tr_*) -- the test hook's instantiations; the
 // shipped ones (kTrace = false) compile to what they were without it (per-kernel resource remarks unchanged)
 // kGrid: the grid search in place of the scan (one lane per source point, the bucket table in LDS); loop, sums, estimate and stop are the same source
-template <bool kFull, bool kTrace = false, bool kGrid = false>
-__global__ __launch_bounds__(kIcpThreads) void icp_kernel(const std::conditional_t<kGrid, IcpGridArgs, IcpArgs> a)
+// kEval: the evaluation call (IcpEvalArgs): the same search, the sums above in place of the estimate's, out after the first evaluation, no transform
+// written.  The other instantiations compile to what they were without it (DESIGN.md 4.7f has the remarks of both)
+template <bool kFull, bool kTrace = false, bool kGrid = false, bool kEval = false>
+__global__ __launch_bounds__(kIcpThreads) void icp_kernel(const std::conditional_t<kEval, IcpEvalArgs, std::conditional_t<kGrid, IcpGridArgs, IcpArgs>> a)
 {
+  static_assert(!kEval || (!kFull && !kTrace), "the evaluation has no estimate and no trace");
   constexpr int kSplit = kGrid ? 1 : kIcpSplit;   // lanes per source point
-  constexpr int kSums = kFull ? kIcpSumsFull : kIcpSums;
+  constexpr int kSums = kEval ? kIcpSumsEval : kFull ? kIcpSumsFull : kIcpSums;
   extern __shared__ __attribute__((aligned(16))) double tgt[];   // [3][lds_points] doubles | [3][4 slices][S4] floats
   __shared__ double T[12];            // rows 0..2 of the 4x4
   __shared__ double red[(kIcpThreads / 64) * kSums], tot[kSums];
@@ -240,6 +266,9 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const std::conditional
   // sum p q - n mean(p) mean(q) cancels |offset|^2 / extent^2 of its digits (a cloud 4 km from the origin: the rotation came out 6e-8 off
   // Open3D's two-pass estimate, tests/test_icp_gpu.py::test_icp_exact_ties_and_far_frames); about the pivot the terms are of the clouds' size
   const double cx = n2 > 0 ? (double)dst[0] : 0.0, cy = n2 > 0 ? (double)dst[1] : 0.0, cz = n2 > 0 ? (double)dst[2] : 0.0;
+  [[maybe_unused]] double ex = 0.0, ey = 0.0, ez = 0.0;   // kEval: the centre of the information matrix (the caller's, or the origin)
+  if constexpr (kEval)
+    if (a.centers) { ex = a.centers[(size_t)b * 3]; ey = a.centers[(size_t)b * 3 + 1]; ez = a.centers[(size_t)b * 3 + 2]; }
   double fit_prev = 0.0, rmse_prev = 0.0, fit = 0.0, rmse = 0.0;
   int k = 0;
   if (n1 > 0 && n2 > 0)
@@ -334,6 +363,22 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const std::conditional
             a.tr_paths[i] = path | (bj >= nl ? kIcpPathTailWon : 0);
           }
         }
+        if constexpr (kEval) {
+          if (active && sub == 0) {
+            const bool in = best <= r2;
+            if (a.corr) a.corr[a.corr_off[b] + i] = in ? bj : -1;
+            if (in) {
+              v[0] += 1.0; v[1] += best;
+              if (a.info) {
+                const double x = (kGrid ? (double)brec.x : bj < nl ? tx[bj] : (double)dst[(long long)bj * 3]) - ex;
+                const double y = (kGrid ? (double)brec.y : bj < nl ? ty[bj] : (double)dst[(long long)bj * 3 + 1]) - ey;
+                const double z = (kGrid ? (double)brec.z : bj < nl ? tz[bj] : (double)dst[(long long)bj * 3 + 2]) - ez;
+                v[2] += y * y + z * z; v[3] += x * x + z * z; v[4] += x * x + y * y;
+                v[5] += x * y; v[6] += x * z; v[7] += y * z; v[8] += x; v[9] += y; v[10] += z;
+              }
+            }
+          }
+        } else
         if (active && sub == 0 && best <= r2) {
           const double qx = kGrid ? (double)brec.x : bj < nl ? tx[bj] : (double)dst[(long long)bj * 3];
           const double qy = kGrid ? (double)brec.y : bj < nl ? ty[bj] : (double)dst[(long long)bj * 3 + 1];
@@ -354,7 +399,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const std::conditional
       block_reduce(v, red, tot);
       const double cnt = tot[0];
       fit = cnt / (double)n1;
-      rmse = cnt > 0.0 ? sqrt(tot[kFull ? 16 : 9] / cnt) : 0.0;
+      rmse = cnt > 0.0 ? sqrt(tot[kEval ? 1 : kFull ? 16 : 9] / cnt) : 0.0;
+      if constexpr (kEval) break;   // one evaluation: the exit of its = 0
       if (k > 0 && fabs(fit - fit_prev) < 1e-6 && fabs(rmse - rmse_prev) < 1e-6) break;
       if (k == a.its) break;
       fit_prev = fit; rmse_prev = rmse;
@@ -409,8 +455,16 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const std::conditional
       __syncthreads();
     }
   __syncthreads();
+  if constexpr (kEval) {
+    // the 6x6 matrix from the reduced sums, the lower half mirrored; an empty cloud (no evaluation ran, tot is unset) gives the zero matrix
+    if (a.info && tid < 36) {
+      const int r = tid / 6, c = tid % 6;
+      a.info[(size_t)b * 36 + tid] = n1 > 0 && n2 > 0 ? icp_info_entry(tot, min(r, c), max(r, c)) : 0.0;
+    }
+  } else {
   if (tid < 12) a.out[(size_t)b * 16 + tid] = T[tid];
   if (tid >= 12 && tid < 16) a.out[(size_t)b * 16 + tid] = tid == 15 ? 1.0 : 0.0;
+  }
   if (tid == 0) {
     if (a.fitness) a.fitness[b] = fit;
     if (a.rmse) a.rmse[b] = rmse;
@@ -563,6 +617,29 @@ int reserve_grid_ws(alignnet_handle* h, size_t need)
   return 0;
 }
 
+// which search each pair takes under `mode` (the "icp_search" values), and the grid pairs' workspace: consecutive grid pairs form chunks of at most
+// kIcpGridWsBudget (one pair may exceed it alone; a chunk's first pair sits at offset 0), every chunk reuses the handle's workspace in stream order.
+// need: the bytes reserved, 0 when no pair takes the grid
+int plan_search(alignnet_handle* h, int mode, const std::vector<long long>& n2, std::vector<char>* grid, std::vector<long long>* ws_off, size_t* need)
+{
+  const int B = (int)n2.size();
+  grid->assign(B, 0);
+  ws_off->assign(B, 0);
+  size_t cur = 0; int open = -1;
+  *need = 0;
+  for (int b = 0; b < B; ++b) {
+    (*grid)[b] = mode == 1 || (mode == 2 && n2[b] > kIcpGridAuto);
+    if (!(*grid)[b]) { open = -1; continue; }
+    if (n2[b] > 0x7fffffff) return fail(h, "icp: more than 2^31 - 1 target points in a pair");
+    const size_t bytes = icp_grid_pair_bytes(n2[b]);
+    if (open < 0 || cur + bytes > kIcpGridWsBudget) { open = b; cur = 0; }
+    (*ws_off)[b] = (long long)cur; cur += bytes;
+    *need = std::max(*need, cur);
+  }
+  if (*need && reserve_grid_ws(h, *need)) return 1;
+  return 0;
+}
+
 // stage_n2: what the scan's LDS stage is sized for
 int run_icp(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, const double* init, double radius, int its, bool full, double* out,
             double* fitness, double* rmse, int* iters, const IcpTraceOut* trace = nullptr, const alignnet::IcpDeviceIo* dev = nullptr)
@@ -575,21 +652,11 @@ int run_icp(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, c
   // which search each pair takes ("icp_search"; the read-backs choose their own), and the grid pairs' workspace: consecutive grid pairs form
   // chunks of at most kIcpGridWsBudget (one pair may exceed it alone), every chunk reuses the handle's workspace in stream order
   const int mode = trace ? (trace->grid ? 1 : 0) : h->icp_search;
-  std::vector<char> grid(B, 0);
+  std::vector<char> grid;
   std::vector<long long> ws_off_own;
   std::vector<long long>& ws_off = dev ? *dev->h_ws_off : ws_off_own;
-  ws_off.assign(B, 0);
-  size_t need = 0, cur = 0; int open = -1;
-  for (int b = 0; b < B; ++b) {
-    grid[b] = mode == 1 || (mode == 2 && n2[b] > kIcpGridAuto);
-    if (!grid[b]) { open = -1; continue; }
-    if (n2[b] > 0x7fffffff) return fail(h, "icp: more than 2^31 - 1 target points in a pair");
-    const size_t bytes = icp_grid_pair_bytes(n2[b]);
-    if (open < 0 || cur + bytes > kIcpGridWsBudget) { open = b; cur = 0; }
-    ws_off[b] = (long long)cur; cur += bytes;
-    need = std::max(need, cur);
-  }
-  if (need && reserve_grid_ws(h, need)) return 1;
+  size_t need = 0;
+  if (plan_search(h, mode, n2, &grid, &ws_off, &need)) return 1;
   IcpGridArgs a;
   IcpResults res;
   DevBuf<long long> wsoff;
@@ -693,6 +760,91 @@ int icp_rows(alignnet_handle* h, const char* fn, const int32_t* rows, int32_t B,
   if (stage_rows(h, fn, rows, B, &c)) return 1;
   // the scan's LDS stage stays sized for the budget whatever the rows hold, as it was when the host did not know the sizes: the kernel clamps per pair
   return run_icp(h, c, kIcpLdsBudget, B, init, radius, its, full, out, fitness, rmse, iterations);
+}
+
+// ---- evaluation of given transforms (alignnet_evaluate_registration*): icp_kernel<false, false, kGrid, true>, one launch per run of pairs -----------
+// what the entry points check before anything is staged or queued
+int eval_arguments(alignnet_handle* h, const std::string& fn, int32_t B, const double* transforms, double threshold, const double* fitness, const double* rmse)
+{
+  if (B < 1) return fail(h, fn + ": B < 1");
+  if (!transforms || !fitness || !rmse) return fail(h, fn + ": null transforms / fitness / rmse");
+  if (!(threshold > 0.0)) return fail(h, fn + ": threshold must be > 0");
+  return 0;
+}
+
+// corr_off [B]: where pair b's source range starts in `correspondences`, corr_total its length.  The search per pair, the grid workspace and its chunks
+// are run_icp's (plan_search); one synchronisation, at the end, with the downloads
+int run_eval(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, const double* transforms, double threshold, const double* centers,
+             double* fitness, double* rmse, double* information, int32_t* correspondences, const std::vector<long long>& corr_off, long long corr_total)
+{
+  std::vector<char> grid;
+  std::vector<long long> ws_off;
+  size_t need = 0;
+  if (plan_search(h, h->icp_search, c.n2, &grid, &ws_off, &need)) return 1;
+  DevBuf<double> tf, fr, cen, info;
+  DevBuf<long long> tab;   // corr_off [B] | ws_off [B]
+  DevBuf<int> corr;
+  HIP_TRY(h, tf.alloc((size_t)B * 16));
+  HIP_TRY(h, fr.alloc((size_t)B * 2));
+  HIP_TRY(h, tab.alloc((size_t)B * 2));
+  HIP_TRY(h, hipMemcpyAsync(tf.p, transforms, (size_t)B * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(tab.p, corr_off.data(), (size_t)B * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(tab.p + B, ws_off.data(), (size_t)B * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+  if (centers) {
+    HIP_TRY(h, cen.alloc((size_t)B * 3));
+    HIP_TRY(h, hipMemcpyAsync(cen.p, centers, (size_t)B * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  if (information) HIP_TRY(h, info.alloc((size_t)B * 36));
+  if (correspondences) {
+    HIP_TRY(h, corr.alloc((size_t)std::max<long long>(corr_total, 1)));
+    HIP_TRY(h, hipMemsetAsync(corr.p, 0xff, (size_t)std::max<long long>(corr_total, 1) * sizeof(int), h->stream));   // -1 where no evaluation runs (an empty target)
+  }
+  IcpEvalArgs a;
+  a.pts[0] = c.pts[0]; a.pts[1] = c.pts[1]; a.off = c.off; a.rows = c.rows; a.init = tf.p; a.radius = threshold; a.its = 0;
+  a.lds_points = (int)std::max<long long>(1, std::min(kIcpLdsBudget, stage_n2));
+  a.out = nullptr; a.fitness = fr.p; a.rmse = fr.p + B; a.iters = nullptr;
+  a.tr_index = a.tr_inlier = a.tr_paths = nullptr; a.tr_dist = nullptr;
+  a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = tab.p + B;
+  a.centers = cen.p; a.info = info.p; a.corr = corr.p; a.corr_off = tab.p;
+  static alignnet::PerDeviceOnce attr[3];
+  const void* const kernels[3] = {reinterpret_cast<const void*>(icp_kernel<false, false, false, true>),
+                                  reinterpret_cast<const void*>(icp_kernel<false, false, true, true>), reinterpret_cast<const void*>(icp_grid_build_kernel)};
+  for (int kn = 0; kn < 3; ++kn)
+    if ((kn == 0 || need) && attr[kn].need(h->cfg.device)) {
+      HIP_TRY(h, hipFuncSetAttribute(kernels[kn], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+      attr[kn].mark(h->cfg.device);
+    }
+  for (int lo = 0; lo < B;) {
+    int hi = lo + 1;
+    IcpEvalArgs r = a;   // pairs lo.. as a launch of their own
+    r.init += (size_t)lo * 16; r.fitness += lo; r.rmse += lo; r.corr_off += lo; r.ws_off += lo;
+    if (r.centers) r.centers += (size_t)lo * 3;
+    if (r.info) r.info += (size_t)lo * 36;
+    if (r.rows) r.rows += lo; else r.off += (size_t)lo * 2;
+    if (!grid[lo]) {
+      while (hi < B && !grid[hi]) ++hi;
+      hipLaunchKernelGGL((icp_kernel<false, false, false, true>), dim3(hi - lo), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, r);
+    } else {
+      long long big = c.n2[lo];
+      while (hi < B && grid[hi] && ws_off[hi] != 0) { big = std::max(big, c.n2[hi]); ++hi; }
+      const size_t lds = ((size_t)icp_grid_buckets(big) + 1) * 4;
+      {
+        alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID_BUILD);
+        const IcpGridArgs g = r;   // (the build reads the clouds, the radius and the workspace)
+        hipLaunchKernelGGL(icp_grid_build_kernel, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, g);
+      }
+      alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID);
+      hipLaunchKernelGGL((icp_kernel<false, false, true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+    }
+    HIP_TRY(h, hipGetLastError());
+    lo = hi;
+  }
+  HIP_TRY(h, hipMemcpyAsync(fitness, fr.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(rmse, fr.p + B, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (information) HIP_TRY(h, hipMemcpyAsync(information, info.p, (size_t)B * 36 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (correspondences && corr_total) HIP_TRY(h, hipMemcpyAsync(correspondences, corr.p, (size_t)corr_total * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return 0;
 }
 
 // ---- point-to-plane ICP (alignnet_icp_plane_register*): target normals once per call, a 6x6 / 4x4 normal-equation estimate in the loop -------------
@@ -1181,6 +1333,38 @@ extern "C" int alignnet_icp_register_dataset(alignnet_handle* h, const int32_t* 
   bool full = false;
   if (icp_flags(h, "alignnet_icp_register_dataset", flags, &full)) return 1;
   return icp_rows(h, "alignnet_icp_register_dataset", rows, B, init, radius, its, full, out, fitness, rmse, iterations);
+}
+
+extern "C" int alignnet_evaluate_registration(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
+                                              const double* transforms, double threshold, const double* centers, double* fitness, double* rmse,
+                                              double* information, int32_t* correspondences)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_evaluate_registration");
+  if (eval_arguments(h, name, B, transforms, threshold, fitness, rmse)) return 1;
+  IcpClouds c;
+  if (stage_host(h, name.c_str(), points1, points2, offsets, B, &c)) return 1;
+  std::vector<long long> corr_off(B);
+  for (int b = 0; b < B; ++b) corr_off[b] = offsets[(size_t)b * 2] - offsets[0];   // the offsets table's source ranges
+  return run_eval(h, c, *std::max_element(c.n2.begin(), c.n2.end()), B, transforms, threshold, centers, fitness, rmse, information, correspondences,
+                  corr_off, offsets[(size_t)B * 2] - offsets[0]);
+}
+
+extern "C" int alignnet_evaluate_registration_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* transforms, double threshold,
+                                                      const double* centers, double* fitness, double* rmse, double* information,
+                                                      int32_t* correspondences)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_evaluate_registration_dataset");
+  if (eval_arguments(h, name, B, transforms, threshold, fitness, rmse)) return 1;
+  IcpClouds c;
+  if (stage_rows(h, name, rows, B, &c)) return 1;
+  alignnet::DatasetTables t;
+  alignnet_dataset_tables(h, &t);
+  std::vector<long long> corr_off(B);
+  long long total = 0;   // the rows' source ranges back to back
+  for (int b = 0; b < B; ++b) { corr_off[b] = total; total += t.h_off[((size_t)rows[b] + 1) * 2] - t.h_off[(size_t)rows[b] * 2]; }
+  return run_eval(h, c, kIcpLdsBudget, B, transforms, threshold, centers, fitness, rmse, information, correspondences, corr_off, total);
 }
 
 extern "C" int alignnet_debug_icp_scan(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2, const double* T,

@@ -128,6 +128,50 @@ def process_velocities(tracks, eval_dir, avg_window):
     return velocities
 
 
+def evaluate_held(cfg, val_idxs, all_pred_translations, all_pred_angles, all_gt_translations, all_gt_angles, eval_dir=None, avg_window=5, mean_time=0):
+    """Held data -- a tracker's output, no ground truth (evaluation.py:49-78, called at train.py:506-508): a smoothed speed per track from the meta
+    keys trackid, frames, timestamps.  Restated with the reference's quirks: the time between the frames is max(0.05, t2 - t1); tracks and frames
+    keep the first-seen order of val_idxs, a later example of the same (trackid, frame2) replaces the earlier one's value in its place; the speed at
+    position i is the xy norm of the mean velocity over positions [max(0, i - avg_window + 1), i + avg_window + 1) -- not process_velocities' window;
+    the files are <eval_dir>/track<trackid>.txt (eval_dir itself, the id unpadded), one value per line; and the speeds are computed only while
+    writing, so eval_dir=None returns an empty dict.  The angles and the ground truth are not read.  Returns (velocities, dict(mean_time))."""
+    tracks = {}
+    for idx, file_idx in enumerate(val_idxs):
+        with open("%s/meta/%s.json" % (cfg.data.basepath, str(file_idx).zfill(8))) as fh:
+            meta = json.load(fh)
+        timestamp1, timestamp2 = meta["timestamps"]
+        time_passed = np.maximum(0.05, timestamp2 - timestamp1)
+        tracks.setdefault(meta["trackid"], {})[meta["frames"][1]] = all_pred_translations[idx] / time_passed
+    velocities = {}
+    if eval_dir is None:
+        return velocities, dict(mean_time=mean_time)
+    for trackid, track in tracks.items():
+        vel = list(track.values())
+        speeds = velocities.setdefault(trackid, [])
+        with open("%s/track%s.txt" % (eval_dir, trackid), "w") as fh:
+            for i in range(len(vel)):
+                window = vel[max(0, i - avg_window + 1):i + avg_window + 1]
+                total = window[0]
+                for v in window[1:]:        # left to right, as the reference's mean over an object array adds them
+                    total = total + v
+                speed = np.linalg.norm((total / len(window))[:2])
+                speeds.append(speed)
+                fh.write("%s\n" % speed)
+    return velocities, dict(mean_time=mean_time)
+
+
+def reg_eval_summary(reg_eval, eval_dir=None):
+    """Namespace(fitness, inlier_rmse): the plain means of the per-pair arrays (fitness_per_pair, rmse_per_pair); with eval_dir the arrays are
+    written there as reg_fitness.npy / reg_inlier_rmse.npy.  No pair gives 0 / 0."""
+    fit, rmse = (np.asarray(a, np.float64).ravel() for a in reg_eval)
+    assert fit.shape == rmse.shape, "one fitness and one inlier rmse per pair"
+    if eval_dir is not None:
+        os.makedirs(eval_dir, exist_ok=True)
+        np.save("%s/reg_fitness.npy" % eval_dir, fit)
+        np.save("%s/reg_inlier_rmse.npy" % eval_dir, rmse)
+    return Namespace(fitness=float(fit.mean()) if fit.size else 0.0, inlier_rmse=float(rmse.mean()) if rmse.size else 0.0)
+
+
 def _bucket():
     z = lambda: np.zeros(3, dtype=float)
     return dict(corr_levels_translation=z(), corr_levels_angles=z(), corr_levels=z(), mean_dist_translation=0.0,
@@ -151,7 +195,10 @@ def _summarise(node):
 
 
 def evaluate(cfg, val_idxs, all_pred_translations, all_pred_angles, all_gt_translations, all_gt_angles, all_pred_centers,
-             all_gt_pc1centers, eval_dir=None, accept_inverted_angle=False, detailed_eval=False, avg_window=5, mean_time=0):
+             all_gt_pc1centers, eval_dir=None, accept_inverted_angle=False, detailed_eval=False, avg_window=5, mean_time=0, reg_eval=None):
+    """reg_eval (this project's, not a reference argument): None leaves result.reg_eval at the zeros the reference writes (evaluation.py:213, 271);
+    (fitness_per_pair, rmse_per_pair) -- Engine.evaluate_registration_rows at every pair's final transform -- fills it with their plain means, a
+    pair without inliers counting as 0 in both as Open3D reports it, and writes the arrays to reg_fitness.npy / reg_inlier_rmse.npy in eval_dir."""
     new_t = translate_transform_to_new_center_of_rotation(all_pred_translations, all_pred_angles, all_pred_centers, all_gt_pc1centers)
     measures = {k: _bucket() for k, _ in _DIST_KEYS}
     measures["val"] = {k: _bucket() for k, _ in _DIST_KEYS}
@@ -215,7 +262,7 @@ def evaluate(cfg, val_idxs, all_pred_translations, all_pred_angles, all_gt_trans
     result = _summarise(measures)
     result.val = _summarise(measures["val"])
     result.test = _summarise(measures["test"])
-    result.reg_eval = Namespace(fitness=0.0, inlier_rmse=0.0)
+    result.reg_eval = Namespace(fitness=0.0, inlier_rmse=0.0) if reg_eval is None else reg_eval_summary(reg_eval, eval_dir)
     result.mean_time = mean_time
     if eval_dir is not None:
         os.makedirs(eval_dir, exist_ok=True)

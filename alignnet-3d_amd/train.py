@@ -129,6 +129,15 @@ class Run:
                     self.icp_data = provider.use_packed_cache()
                     self.icp_data.upload(self.engine)
                 logger.info("evaluation: one register call per batch (evaluation.register = device)")
+        # evaluation.reg_eval: fitness / inlier RMSE of every pair's final transform on the full clouds, which it needs in HBM like --refineICP
+        self.reg_eval = reg_eval_option()
+        if self.reg_eval is not None:
+            if self.icp_data is None:
+                self.icp_data = provider.use_packed_cache()
+                self.icp_data.upload(self.engine)
+            if not flags.refineICP:
+                set_icp_search(self.engine)
+            logger.info("evaluation: registration fitness / inlier RMSE within %g m (evaluation.reg_eval)" % self.reg_eval)
         self.train_idx = provider.getDataFiles("%s/split/train.txt" % cfg.data.basepath)
         self.val_idx = provider.getDataFiles("%s/split/val.txt" % cfg.data.basepath)
         self.batches_per_epoch = len(self.train_idx) // cfg.training.batch_size
@@ -227,9 +236,11 @@ class Run:
             store[k] = np.empty((nval, 1), np.float32)
         gt_t, gt_a, gt_c1 = np.empty((nval, 3), np.float32), np.empty((nval, 1), np.float32), np.empty((nval, 3), np.float32)
         loss_sum, cumulated, full_batches = 0.0, 0.0, nval // B
+        reg = np.zeros((2, nval)) if self.reg_eval is not None and self.rank == 0 and not do_timings else None   # fitness, inlier rmse per pair
         for b in range(int(np.ceil(nval / B))):
             s, e = b * B, min((b + 1) * B, nval)
             n = e - s
+            T = None   # the refined transforms of this batch, when ICP ran
             batch = provider.load_batch(val[s:e], override_batch_size=override_batch_size,
                                         dont_load_pointclouds=self.device_data is not None or self.register_device)
             lo, hi = parallel.shard_range(n, self.rank, self.world)
@@ -257,6 +268,8 @@ class Run:
                 for k in names3:
                     store[k][s:e] = ep[k]
                 gt_t[s:e], gt_a[s:e], gt_c1[s:e] = batch[2][:n], batch[3][:n], batch[4][:n]
+                if reg is not None:
+                    self.reg_eval_batch(val[s:e], store, s, e, T, reg)
                 continue
             if hi > lo and self.device_data is not None:
                 ep = self.engine.forward_rows(self.device_data.rows_of(val[s:e])[lo:hi], seed=int(np.random.randint(0, 2 ** 62)))
@@ -300,24 +313,49 @@ class Run:
             for k in names3:
                 store[k][s:e] = ep[k]
             gt_t[s:e], gt_a[s:e], gt_c1[s:e] = batch[2][:n], batch[3][:n], batch[4][:n]
+            if reg is not None:
+                self.reg_eval_batch(val[s:e], store, s, e, T, reg)
         mean_loss = loss_sum / full_batches if full_batches > 0 else 0.0
         mean_time = cumulated / float(nval)
         if do_timings:
             print("Timing bs=%s: %s" % (override_batch_size, mean_time))
+        elif self.rank == 0 and held_tracks(val):
+            # train.py:506-508: a speed per track from the predicted translations and the meta's timestamps; no eval.json, as in the reference
+            tracks, _ = evaluation.evaluate_held(cfg, val, store["pred_translations"], store["pred_angles"], gt_t, gt_a, eval_dir=eval_dir,
+                                                 mean_time=mean_time)
+            logger.info("Held evaluation: %d tracks written to %s, Mean ex. time: %.5f" % (len(tracks), eval_dir, mean_time))
+            if reg is not None:   # this project's: the one quality number a run without ground truth can have
+                q = evaluation.reg_eval_summary(reg, eval_dir)
+                with open("%s/eval_held.json" % eval_dir, "w") as fh:
+                    json.dump({"mean_time": mean_time, "reg_eval": evaluation.ns_to_dict(q)}, fh)
+                logger.info("Fitness: %.2f%%, Inlier RMSE: %.2f%%" % (q.fitness * 100.0, q.inlier_rmse * 100.0))
         elif self.rank == 0:
             for inv in (False, True):
                 ev = evaluation.evaluate(cfg, val, store["pred_translations"], store["pred_angles"], gt_t, gt_a,
                                          store["pred_s2_pc1centers"], gt_c1, eval_dir=eval_dir, accept_inverted_angle=inv,
-                                         mean_time=mean_time)
+                                         mean_time=mean_time, reg_eval=reg)
                 pct = lambda v: " ".join("%.2f%%" % (a * 100.0) for a in v)
+                quality = "" if reg is None else "Fitness: %.2f%%, Inlier RMSE: %.2f%%, " % (ev.reg_eval.fitness * 100.0, ev.reg_eval.inlier_rmse * 100.0)
                 logger.info("Mean translation distance: %s, Mean angle distance: %s, Levels: %s, Translation levels: %s, "
-                            "Angle levels: %s, Mean ex. time: %.5f" % (ev.mean_dist_translation, ev.mean_dist_angle, pct(ev.corr_levels),
-                                                                       pct(ev.corr_levels_translation), pct(ev.corr_levels_angles), mean_time))
+                            "Angle levels: %s, %sMean ex. time: %.5f" % (ev.mean_dist_translation, ev.mean_dist_angle, pct(ev.corr_levels),
+                                                                         pct(ev.corr_levels_translation), pct(ev.corr_levels_angles), quality,
+                                                                         mean_time))
         if self.rank == 0:
             for k, v in store.items():
                 np.save("%s/%s.npy" % (eval_dir, k), v)
             logger.info("val mean loss: %f" % mean_loss if self.world == 1 else "val mean loss: n/a (batch split over %d ranks)" % self.world)
         return mean_time
+
+    def reg_eval_batch(self, ids, store, s, e, T, reg):
+        """evaluation.reg_eval: fitness and inlier RMSE of the examples `ids` = val[s:e] at their final transforms, on the full clouds in HBM, into
+        reg[:, s:e].  T: the refined transforms when ICP ran; otherwise get_mat_angle(pred_translation, pred_angle, pred_s2_pc1center) of the values
+        AS STORED (float32, what the .npy files of the evaluation hold), so that the numbers can be recomputed from the evaluation directory.
+        Called outside the timed region: mean_time keeps its meaning."""
+        if T is None:
+            T = [evaluation.get_mat_angle(store["pred_translations"][i], store["pred_angles"][i], rotation_center=store["pred_s2_pc1centers"][i])
+                 for i in range(s, e)]
+        r = self.engine.evaluate_registration_rows(self.icp_data.rows_of(ids), T, threshold=self.reg_eval)
+        reg[0, s:e], reg[1, s:e] = r["fitness"], r["rmse"]
 
     # ---- train.py:187-332 -------------------------------------------------------------------------------------
     def train(self, eval_only=False, eval_epoch=None, eval_only_model_to_load=None, do_timings=False, override_batch_size=None):
@@ -402,6 +440,36 @@ def register_option(config=None, environ=None):
     if name not in REGISTER:
         raise ValueError("evaluation.register / ALIGNNET_REGISTER = %r: expected one of %s" % (name, ", ".join(REGISTER)))
     return name
+
+
+def reg_eval_option(config=None):
+    """Optional, not a reference key: "evaluation": {"reg_eval": {"threshold": 0.02}} fills the reference's `Fitness` / `Inlier RMSE` fields
+    (evaluation.py:213, 271 leave them zero; tp_utils/pointcloud.py:1405-1406 shows what was meant: o3.evaluate_registration(pc1, pc2, 0.02, T)) with
+    the fitness and inlier RMSE of every pair's final transform on the FULL clouds (Engine.evaluate_registration_rows): the one quality number that
+    needs no ground truth.  Absent: off, every output as it was.  Returns the threshold, or None."""
+    config = cfg if config is None else config
+    ev = getattr(config, "evaluation", None)
+    opt = getattr(ev, "reg_eval", None)
+    if opt is None or opt is False:
+        return None
+    threshold = float(getattr(opt, "threshold", 0.02))
+    if not threshold > 0.0:
+        raise ValueError("evaluation.reg_eval.threshold = %r: expected a distance > 0" % (threshold,))
+    return threshold
+
+
+def held_tracks(val):
+    """The reference's held branch (train.py:506-508) applies when evaluation.special.mode is "held"; evaluation.evaluate_held then needs the meta
+    keys of FromHeldScene.  True when the mode is held AND the first val example's meta has `trackid` and `timestamps` (make_kitti_dataset.py --held
+    writes them); held runs on any other data evaluate as they always did here."""
+    if not (cfg.evaluation.has("special") and cfg.evaluation.special.mode == "held") or not len(val):
+        return False
+    try:
+        with open("%s/meta/%s.json" % (cfg.data.basepath, str(val[0]).zfill(8))) as fh:
+            meta = json.load(fh)
+    except OSError:
+        return False
+    return "trackid" in meta and "timestamps" in meta
 
 
 ICP_ESTIMATE = ("point", "plane")

@@ -344,6 +344,30 @@ int alignnet_icp_register(alignnet_handle* h, const float* points1, const float*
                           double* rmse, int32_t* iterations);
 int alignnet_icp_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
                                   int32_t its, int32_t flags, double* out, double* fitness, double* rmse, int32_t* iterations);
+/* ---- evaluation of given transforms: what needs no ground truth (Open3D's evaluate_registration and
+ * get_information_matrix_from_point_clouds; tests/reg_eval_ref.py is the definition) ---------------------------
+ * Clouds as in alignnet_icp_register / _dataset (concatenated with offsets [B + 1][2], or rows of the uploaded dataset);
+ * transforms [B][16] row-major 4x4 float64 (source onto target).  Per pair ONE correspondence step at its transform and
+ * nothing else: the nearest target of every transformed source point by the ICP kernel's own rule (fp64 decision, equal
+ * distances to the lower index), an inlier when dist2 <= threshold^2 (the closed interval of the ICP loop).
+ *   fitness [B] = inliers / n1;  rmse [B] = sqrt(sum dist2 / inliers), 0 without inliers.
+ *   correspondences (int32, may be NULL): per source point the chosen target's index within its cloud, -1 when not an
+ *     inlier.  Host form: indexed by the offsets table's source ranges ([offsets[B][0]] entries); _dataset: the rows'
+ *     source ranges back to back in `rows` order.
+ *   information [B][36] (may be NULL): row-major 6x6, parameters (rotation x, y, z; translation x, y, z) = the sum over
+ *     the inliers of G^T G, G = [0, z, -y, 1, 0, 0; -z, 0, x, 0, 1, 0; y, -x, 0, 0, 0, 1] for the inlier's TARGET point
+ *     minus the pair's row of centers [B][3] = (x, y, z); centers NULL = the origin, Open3D's definition.  fp64 sums
+ *     in a fixed order; symmetric bit for bit.
+ * An empty source or target cloud: fitness 0, rmse 0, correspondences -1, a zero matrix.  The search is the handle's
+ * "icp_search" option as for alignnet_icp_register.  Errors (null transforms / fitness / rmse / offsets / rows, B < 1,
+ * threshold <= 0, decreasing offsets, a row out of range, no dataset) are found before anything is queued.
+ * Added without moving ALIGNNET_ABI_VERSION (as alignnet_register was). */
+int alignnet_evaluate_registration(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets,
+                                   int32_t B, const double* transforms, double threshold, const double* centers,
+                                   double* fitness, double* rmse, double* information, int32_t* correspondences);
+int alignnet_evaluate_registration_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* transforms,
+                                           double threshold, const double* centers, double* fitness, double* rmse,
+                                           double* information, int32_t* correspondences);
 /* Test hook: ONE evaluation (the correspondence step at the transform T [16], no estimate) of one pair by the kernel of
  * alignnet_icp_register* itself (the same scan source, compiled with a record behind it), and what it decided for
  * every source point: index [n1] the chosen target (-1: empty target cloud); dist2 [n1] its squared distance, fp64;
