@@ -505,8 +505,35 @@ class Engine:
                                                                   0 if constrained else ICP_FULL_ROTATION, dp(out), dp(fit), dp(rmse), itp))
         return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
 
+    # ---- generalized (plane-to-plane) ICP (csrc/alignnet_icp.hip: icp_generalized_*; semantics: tests/icp_generalized_ref.py) ----
+    def icp_generalized_refine(self, sources, targets, inits, radius=0.1, normal_radius=0.3, its=30, constrained=True):
+        """Generalized ICP (Segal, Haehnel, Thrun 2009): icp_plane_refine's loop, arguments and return dict with every correspondence weighted by
+        the inverse of the sum of the two surface covariances (1e-3 along the normal, 1 across it).  Normals of BOTH clouds are computed once per
+        call, each cloud on its own within `normal_radius`, the source's in its own frame.  A single plane gives a regular system."""
+        B = len(sources)
+        off = np.zeros((B + 1, 2), np.int64)
+        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
+        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
+        p1, p2 = cat(sources), cat(targets)
+        init, out, fit, rmse, it, dp = self._icp_bufs(inits, B)
+        offp, itp = off.ctypes.data_as(C.POINTER(C.c_int64)), it.ctypes.data_as(C.POINTER(C.c_int32))
+        fn = self._register_fn("alignnet_icp_generalized_register")
+        self._check(fn(self._h, _fp(p1), _fp(p2), offp, B, dp(init), float(radius), float(normal_radius), int(its),
+                       0 if constrained else ICP_FULL_ROTATION, dp(out), dp(fit), dp(rmse), itp))
+        return dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+
+    def icp_generalized_refine_rows(self, rows, inits, radius=0.1, normal_radius=0.3, its=30, constrained=True):
+        """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows."""
+        r, rp = self._rows(rows)
+        init, out, fit, rmse, it, dp = self._icp_bufs(inits, r.size)
+        itp = it.ctypes.data_as(C.POINTER(C.c_int32))
+        fn = self._register_fn("alignnet_icp_generalized_register_dataset")
+        self._check(fn(self._h, rp, r.size, dp(init), float(radius), float(normal_radius), int(its), 0 if constrained else ICP_FULL_ROTATION, dp(out),
+                       dp(fit), dp(rmse), itp))
+        return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+
     # ---- one-call registration: clouds to transforms on the device (csrc/alignnet_register.hip; DESIGN.md 4.8b) ----
-    REFINE = {None: 0, "point": 1, "plane": 2}
+    REFINE = {None: 0, "point": 1, "plane": 2, "generalized": 4}   # (the option values of alignnet_register_options.refine; 3 is not assigned)
 
     def _register_fn(self, name):
         try:
@@ -517,7 +544,7 @@ class Engine:
 
     def _register_bufs(self, B, refine, radius, normal_radius, its, constrained, want_net, want_loss):
         if refine not in self.REFINE:
-            raise ValueError("refine = %r: expected None, 'point' or 'plane'" % (refine,))
+            raise ValueError("refine = %r: expected None, 'point', 'plane' or 'generalized'" % (refine,))
         opt = _capi.RegisterOptions(self.REFINE[refine], int(its) if refine else 0, 0 if constrained else ICP_FULL_ROTATION, float(radius),
                                     float(normal_radius))
         n = max(B, 0)
@@ -547,7 +574,7 @@ class Engine:
 
     def register(self, sources, targets, seed=0, streams=None, refine=None, radius=0.1, normal_radius=0.3, its=30, constrained=True, want_net=False):
         """Two raw clouds per pair in, a 4x4 per pair out, in ONE engine call: the sampler's draw, the eval forward, the fp64 yaw decode, the
-        initial transform T_net and -- refine="point" | "plane" -- ICP on the full clouds from it, with no return to the host in between.
+        initial transform T_net and -- refine="point" | "plane" | "generalized" -- ICP on the full clouds from it, with no return to the host in between.
         sources / targets: lists of [n, 3] arrays; streams: [B] ids of the pairs' random streams (None: the pair index) -- pair b is drawn as
         register_rows would draw it were the pair example streams[b] of the dataset.  Returns dict(transforms [B, 4, 4] (refined, or T_net),
         network_transforms [B, 4, 4], angles [B, 4] = a1, a2, a_rem, pred_angle, loss=None; fitness, rmse, iterations when refining; the
@@ -598,6 +625,27 @@ class Engine:
         n1, n2 = len(p1), len(p2)
         return dict(normals=nrm[:n2].copy(), neighbours=nbr[:n2].copy(), index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1,
                     residual=res[:n1].copy(), sums=sums, update=upd.reshape(4, 4), fitness=float(fit[0]), rmse=float(rmse[0]))
+
+    def debug_icp_generalized(self, source, target, T, radius=0.1, normal_radius=0.3, constrained=True):
+        """Test hook: one pair through the generalized-ICP kernels' own source -- both clouds' normals and neighbour counts, ONE evaluation at the
+        4x4 `T` and the estimate that follows.  Returns dict(normals [n2, 3], neighbours [n2] (the target's), source_normals [n1, 3],
+        source_neighbours [n1], index [n1] (-1 without a candidate), dist2 [n1] (inf without), inlier [n1] bool, sums [29] (count, sum dist2, upper
+        triangle of J^T M J, J^T M d; 16 used by the z-constrained estimate), update [4, 4], fitness, rmse)."""
+        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+        Tm = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+        n, m = max(len(p1), 1), max(len(p2), 1)
+        nrm, nbr, snrm, snbr = np.zeros((m, 3), np.float64), np.zeros(m, np.int32), np.zeros((n, 3), np.float64), np.zeros(n, np.int32)
+        idx, d2, inl = np.full(n, -1, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32)
+        sums, upd, fit, rmse = np.zeros(29, np.float64), np.zeros(16, np.float64), np.zeros(1, np.float64), np.zeros(1, np.float64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.alignnet_debug_icp_generalized(self._h, _fp(p1), len(p1), _fp(p2), len(p2), dp(Tm), float(radius), float(normal_radius),
+                                                             0 if constrained else ICP_FULL_ROTATION, dp(nrm), ip(nbr), dp(snrm), ip(snbr), ip(idx), dp(d2),
+                                                             ip(inl), dp(sums), dp(upd), dp(fit), dp(rmse)))
+        n1, n2 = len(p1), len(p2)
+        return dict(normals=nrm[:n2].copy(), neighbours=nbr[:n2].copy(), source_normals=snrm[:n1].copy(), source_neighbours=snbr[:n1].copy(),
+                    index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1, sums=sums, update=upd.reshape(4, 4), fitness=float(fit[0]),
+                    rmse=float(rmse[0]))
 
     # ---- global registration: RANSAC on FPFH feature matches (csrc/alignnet_globalreg.hip) ----
     @staticmethod
@@ -1216,7 +1264,7 @@ class Engine:
     PROFILED_KERNELS = ("backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1",
                         "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact",
                         "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band",
-                        "tracklet_test", "tracklet_compact")
+                        "tracklet_test", "tracklet_compact", "icp_generalized_normals", "icp_generalized")
 
     def profile_kernels(self):
         """{kernel: (ms, launches)} accumulated since the last profile_read(reset=True); call BEFORE that reset."""

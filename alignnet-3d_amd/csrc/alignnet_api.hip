@@ -1024,6 +1024,7 @@ extern "C" int alignnet_set_option(alignnet_handle* h, const char* key, int64_t 
   if (k == "pn_cloud_parts") { if (value < 0 || value > 8) return fail(h, "pn_cloud_parts must be 0 (automatic) .. 8"); h->pn_parts_opt = (int)value; return 0; }
   if (k == "icp_search") { if (value < 0 || value > 2) return fail(h, "icp_search must be 0 (scan), 1 (grid) or 2 (automatic)"); h->icp_search = (int)value; return 0; }
   if (k == "icp_plane_ws_budget") { if (value < 0) return fail(h, "icp_plane_ws_budget must be >= 0 (0 = 1 GiB)"); h->icp_plane_ws_budget = (size_t)value; return 0; }
+  if (k == "icp_generalized_ws_budget") { if (value < 0) return fail(h, "icp_generalized_ws_budget must be >= 0 (0 = 1 GiB)"); h->icp_generalized_ws_budget = (size_t)value; return 0; }
   if (k == "scene_cast") { if (value < 0 || value > 2) return fail(h, "scene_cast must be 0 (scan), 1 (binned) or 2 (automatic)"); h->scene_cast = (int)value; return 0; }
   if (k == "scene_rows") { if (value != 0 && value != 1) return fail(h, "scene_rows must be 0 (whole tiles) or 1 (by elevation band)"); h->scene_rows = (int)value; return 0; }
   for (const auto& ak : kAbKeys)
@@ -1073,6 +1074,8 @@ extern "C" int alignnet_get_option(alignnet_handle* h, const char* key, int64_t*
   if (k == "icp_search") { *value = h->icp_search; return 0; }
   if (k == "icp_plane_ws_budget") { *value = (int64_t)h->icp_plane_ws_budget; return 0; }
   if (k == "icp_plane_chunks") { *value = h->icp_plane_chunks; return 0; }
+  if (k == "icp_generalized_ws_budget") { *value = (int64_t)h->icp_generalized_ws_budget; return 0; }
+  if (k == "icp_generalized_chunks") { *value = h->icp_generalized_chunks; return 0; }
   if (k == "icp_grid_ws_bytes") { *value = (int64_t)h->icp_grid_ws_used; return 0; }
   if (k == "scene_cast") { *value = h->scene_cast; return 0; }
   if (k == "scene_rows") { *value = h->scene_rows; return 0; }

@@ -552,7 +552,7 @@ int run_goicp(alignnet_handle* h, const std::string& name, const float* d_p0, co
       const long long stage_n2 = 0;   // the scan's LDS stage at its budget whatever the batch holds, as the _dataset entry points size it
       const alignnet::IcpDeviceIo io = {a.s_init, a.s_out, a.s_fit, a.s_rmse, a.s_iters, a.s_wsoff, &h_icp_wsoff};
       const float* const wpts[2] = {a.ws[0], a.ws[1]};
-      if (alignnet_icp_run_device(h, wpts, a.wsoff, a.s_rows, h_sn2.data(), stage_n2, n, io, q.start_radius, 0.0, q.start_its, false, false)) return 1;
+      if (alignnet_icp_run_device(h, wpts, a.wsoff, a.s_rows, nullptr, h_sn2.data(), stage_n2, n, io, q.start_radius, 0.0, q.start_its, false, 1)) return 1;
       hipLaunchKernelGGL(goicp_start_pose_kernel, dim3((n + 63) / 64), dim3(64), 0, h->stream, a, n);
       HIP_TRY(h, hipGetLastError());
       const GoLevel lv0 = go_level(q, 0, depth);

@@ -475,16 +475,15 @@ __global__ __launch_bounds__(kIcpThreads) void icp_kernel(const std::conditional
 // Grid build, one workgroup per pair: cell edge from the pair's largest |coordinate|, then a counting sort of the targets by hashed cell -- counts by
 // LDS atomics, an exclusive scan over the H buckets (each thread a contiguous run, the runs' totals scanned across the block), the starts written
 // out, the scatter by LDS atomics on the running starts.  Both passes hash the same values, so the positions handed out stay inside [0, n2).
-__global__ __launch_bounds__(kIcpThreads) void icp_grid_build_kernel(const IcpGridArgs a)
+// The cloud is the caller's: `dst` [n2][3], its grid at `ws`, cells for `radius` (the kernels below name the target; the generalized estimate also
+// grids the source)
+__device__ __forceinline__ void icp_grid_build_cloud(const float* dst, long long n2, char* ws, double radius)
 {
   extern __shared__ int cnt[];        // [H + 1]
   __shared__ double wmax[kIcpThreads / 64];
   __shared__ int wsum[kIcpThreads / 64], wocc[kIcpThreads / 64], wbig[kIcpThreads / 64];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long row = a.rows ? a.rows[b] : b;
-  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
-  const float* dst = a.pts[1] + t_lo * 3;
-  const IcpGridView g = icp_grid_view(a.ws + a.ws_off[b], n2, false);   // (its edge is found here)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const IcpGridView g = icp_grid_view(ws, n2, false);   // (its edge is found here)
   const int H = g.buckets;
   double m = 0.0;
   for (long long j = tid; j < n2; j += kIcpThreads)
@@ -495,7 +494,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_grid_build_kernel(const IcpGr
   for (int j = tid; j <= H; j += kIcpThreads) cnt[j] = 0;
   __syncthreads();
   for (int q = 0; q < kIcpThreads / 64; ++q) m = fmax(m, wmax[q]);
-  const double e = fmax(a.radius * (1.0 + kGridSpan), (m + a.radius) * kGridSpan);
+  const double e = fmax(radius * (1.0 + kGridSpan), (m + radius) * kGridSpan);
   for (long long j = tid; j < n2; j += kIcpThreads)
     atomicAdd(&cnt[icp_grid_bucket((double)dst[j * 3], (double)dst[j * 3 + 1], (double)dst[j * 3 + 2], e, g.mask)], 1);
   __syncthreads();
@@ -532,6 +531,14 @@ __global__ __launch_bounds__(kIcpThreads) void icp_grid_build_kernel(const IcpGr
   }
 }
 
+__global__ __launch_bounds__(kIcpThreads) void icp_grid_build_kernel(const IcpGridArgs a)
+{
+  const int b = blockIdx.x;
+  const long long row = a.rows ? a.rows[b] : b;
+  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
+  icp_grid_build_cloud(a.pts[1] + t_lo * 3, n2, a.ws + a.ws_off[b], a.radius);
+}
+
 // shared driver: tables already on the device
 // alignnet_debug_icp_scan: host arrays [n1] for the records of pair 0's first evaluation; lds_points > 0 overrides the LDS stage's size (<= the budget)
 // alignnet_debug_icp_grid (grid = true): the same through the grid search, paths = candidates evaluated, info = pair 0's IcpGridInfo
@@ -553,6 +560,7 @@ Args icp_args_from(const Args& a, int lo)   // the arguments of pairs lo.. as a 
 struct IcpClouds {
   const float* pts[2] = {nullptr, nullptr}; const long long* off = nullptr; const int* rows = nullptr;
   std::vector<long long> n2;   // the target sizes of the B pairs as the host knows them
+  std::vector<long long> n1;   // the source sizes (the generalized estimate carves a source grid per pair)
   PairUpload up; DevBuf<int> up_rows;
 };
 
@@ -561,7 +569,7 @@ int stage_host(alignnet_handle* h, const std::string& name, const float* points1
 {
   if (!h) return 1;
   if (upload_pairs(h, name, points1, points2, offsets, B, &c->up)) return 1;
-  c->n2.swap(c->up.n2);
+  c->n2.swap(c->up.n2); c->n1.swap(c->up.n1);
   c->pts[0] = c->up.pts[0].p; c->pts[1] = c->up.pts[1].p; c->off = c->up.off.p;
   return 0;
 }
@@ -579,8 +587,11 @@ int stage_rows(alignnet_handle* h, const std::string& name, const int32_t* rows,
   HIP_TRY(h, c->up_rows.alloc((size_t)B));
   HIP_TRY(h, hipMemcpyAsync(c->up_rows.p, rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   // target sizes from the host's copy of the offsets (the grid search carves its workspace per pair)
-  c->n2.resize(B);
-  for (int i = 0; i < B; ++i) c->n2[i] = t.h_off[((size_t)rows[i] + 1) * 2 + 1] - t.h_off[(size_t)rows[i] * 2 + 1];
+  c->n2.resize(B); c->n1.resize(B);
+  for (int i = 0; i < B; ++i) {
+    c->n2[i] = t.h_off[((size_t)rows[i] + 1) * 2 + 1] - t.h_off[(size_t)rows[i] * 2 + 1];
+    c->n1[i] = t.h_off[((size_t)rows[i] + 1) * 2] - t.h_off[(size_t)rows[i] * 2];
+  }
   c->pts[0] = t.pts[0]; c->pts[1] = t.pts[1]; c->off = t.off; c->rows = c->up_rows.p;
   return 0;
 }
@@ -900,14 +911,10 @@ __device__ __forceinline__ double icp_affine_unfused(double t0, double t1, doubl
 // grid B's records in original-index order inside every bucket: one lane per record finds its bucket again (the build's hash of the build's edge),
 // counts the bucket's records of lower index and writes itself there in the second array.  blockIdx.x = pair * parts + part (the pair in x: no
 // 65,535 limit on the pairs of a chunk); the parts of a pair stride over its records
-__global__ __launch_bounds__(kIcpPlaneLanes) void icp_plane_sort_kernel(const IcpPlaneArgs a)
+// the cloud's grid `g` (n2 records) and where the ordered records go are the caller's
+__device__ __forceinline__ void icp_plane_sort_cloud(const IcpGridView& g, float4* srt, long long n2, int part, int parts)
 {
-  const int b = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
-  const long long row = a.rows ? a.rows[b] : b;
-  const long long n2 = a.off[(row + 1) * 2 + 1] - a.off[row * 2 + 1];
-  const IcpGridView g = icp_grid_view(a.ws + a.ws_off_b[b], n2);   // grid B
-  float4* const srt = icp_plane_sorted(icp_grid_view(a.ws + a.ws_off[b], n2), n2);   // (behind the pair's grid A)
-  for (long long j = (long long)part * kIcpPlaneLanes + threadIdx.x; j < n2; j += (long long)a.parts * kIcpPlaneLanes) {
+  for (long long j = (long long)part * kIcpPlaneLanes + threadIdx.x; j < n2; j += (long long)parts * kIcpPlaneLanes) {
     const float4 q = g.rec[j];
     const int mine = __float_as_int(q.w);
     const unsigned hb = icp_grid_bucket((double)q.x, (double)q.y, (double)q.z, g.edge, g.mask);
@@ -918,18 +925,22 @@ __global__ __launch_bounds__(kIcpPlaneLanes) void icp_plane_sort_kernel(const Ic
   }
 }
 
-__global__ __launch_bounds__(kIcpPlaneLanes) void icp_plane_normals_kernel(const IcpPlaneArgs a)
+__global__ __launch_bounds__(kIcpPlaneLanes) void icp_plane_sort_kernel(const IcpPlaneArgs a)
 {
   const int b = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
   const long long row = a.rows ? a.rows[b] : b;
-  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
-  const float* dst = a.pts[1] + t_lo * 3;
-  const IcpGridView g = icp_grid_view(a.ws + a.ws_off_b[b], n2), ga = icp_grid_view(a.ws + a.ws_off[b], n2);   // grid B; grid A for the arrays
-  const float4* const srt = icp_plane_sorted(ga, n2);
-  double* const nrm = icp_plane_normals(ga, n2);
-  int* const cnt = icp_plane_counts(ga, n2);
-  const double r2 = a.normal_radius * a.normal_radius;
-  for (long long i = (long long)part * kIcpPlaneLanes + threadIdx.x; i < n2; i += (long long)a.parts * kIcpPlaneLanes) {
+  const long long n2 = a.off[(row + 1) * 2 + 1] - a.off[row * 2 + 1];
+  const IcpGridView g = icp_grid_view(a.ws + a.ws_off_b[b], n2);   // grid B
+  float4* const srt = icp_plane_sorted(icp_grid_view(a.ws + a.ws_off[b], n2), n2);   // (behind the pair's grid A)
+  icp_plane_sort_cloud(g, srt, n2, part, a.parts);
+}
+
+// normals and neighbour counts of the cloud `dst` [n2][3] from its grid `g` and the index-ordered records `srt`
+__device__ __forceinline__ void icp_plane_normals_cloud(const float* dst, long long n2, const IcpGridView& g, const float4* srt, double* nrm, int* cnt,
+                                                        double normal_radius, int part, int parts)
+{
+  const double r2 = normal_radius * normal_radius;
+  for (long long i = (long long)part * kIcpPlaneLanes + threadIdx.x; i < n2; i += (long long)parts * kIcpPlaneLanes) {
     const double qx = (double)dst[i * 3], qy = (double)dst[i * 3 + 1], qz = (double)dst[i * 3 + 2];
     const int gx = icp_grid_cell(qx, g.edge), gy = icp_grid_cell(qy, g.edge), gz = icp_grid_cell(qz, g.edge);
     int K = 0;
@@ -966,6 +977,16 @@ __global__ __launch_bounds__(kIcpPlaneLanes) void icp_plane_normals_kernel(const
     nrm[i * 3] = n[0]; nrm[i * 3 + 1] = n[1]; nrm[i * 3 + 2] = n[2];
     cnt[i] = K;
   }
+}
+
+__global__ __launch_bounds__(kIcpPlaneLanes) void icp_plane_normals_kernel(const IcpPlaneArgs a)
+{
+  const int b = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
+  const long long row = a.rows ? a.rows[b] : b;
+  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
+  const float* dst = a.pts[1] + t_lo * 3;
+  const IcpGridView g = icp_grid_view(a.ws + a.ws_off_b[b], n2), ga = icp_grid_view(a.ws + a.ws_off[b], n2);   // grid B; grid A for the arrays
+  icp_plane_normals_cloud(dst, n2, g, icp_plane_sorted(ga, n2), icp_plane_normals(ga, n2), icp_plane_counts(ga, n2), a.normal_radius, part, a.parts);
 }
 
 // the update U (rows 0..2 of the 4x4) from the reduced sums; false (U = I): nothing determined
@@ -1158,36 +1179,266 @@ __global__ __launch_bounds__(kIcpThreads) void icp_plane_kernel(const IcpPlaneAr
   }
 }
 
-// alignnet_debug_icp_plane: host arrays of the one pair
-struct IcpPlaneTrace { long long n1, n2; double* normals; int* neighbours; int* index; double* dist; int* inlier; double* resid; double* sums; double* update; };
+// ---- generalized (plane-to-plane) ICP (alignnet_icp_generalized_register*): normals of BOTH clouds once per call, every correspondence weighted by
+// the inverse of the sum of the two surface covariances ---------------------------------------------------------------------------------------------
+// Semantics: tests/icp_generalized_ref.py (Segal, Haehnel, Thrun 2009; the covariances of Open3D's registration_generalized_icp, epsilon 1e-3).  A
+// point with unit normal n has the covariance C = I - (1 - eps) n n^T, never stored.  Per pair, once per call: what point-to-plane prepares for the
+// target (grid A, grid B, ordered records, normals, counts: the same kernels, the same layout at the head of the pair's part) and behind it a third
+// grid over the SOURCE with cells of normal_radius, its ordered records, normals and counts (icp_generalized_*_source_kernel: the bodies of the
+// target's kernels on the other cloud; the normals are taken in the source's own frame) and one int per source point for the loop.
+// Loop (icp_generalized_kernel, one workgroup of 1024 lanes per pair, bucket starts of grid A in LDS, icp_grid_nearest): evaluate, stop test, estimate,
+// T <- U T as icp_plane_kernel.  Estimate over the inliers (p, q, n_q, n_p), R = the rotation of the current T: m = R n_p,
+// A = 2 I - (1 - eps)(n_q n_q^T + m m^T) = C_q + R C_p R^T, M = A^-1 by cofactors, d = p - q, a = p - c, J = [e_x x a, e_y x a, e_z x a, I] (full) or
+// [e_z x a, I] (z-constrained); the sums are count, sum |d|^2, the upper triangle of sum J^T M J row by row and sum J^T M d: point-to-plane's 16 / 29
+// slots, reduced by block_reduce and solved by icp_plane_update as they are.  Everything per correspondence is evaluated without contraction in the
+// order the restatement states (icp_generalized_terms), so every term is the restatement's to the last bit; the zeros and ones of J are left out
+// (x * 0, x + 0 and x * 1 are exact).
+// Registers: the full-rotation point-to-plane kernel spills with its 29 fp64 accumulators in the 128 registers a 1024-lane workgroup leaves a lane,
+// and this estimate holds M, W = M J and w = M d beside them.  The full-rotation instantiation therefore takes the matrix sums in TWO PASSES over the
+// inliers of a lane (the first of DESIGN.md 4.7d's leads): pass 0 searches, leaves each source point's correspondence (or -1) in the pair's workspace
+// and accumulates slots 0..14; pass 1 reads it back, recomputes p, M and W from the same inputs and accumulates slots 15..28.  Each pass ends in its
+// own block_reduce (15 and 14 wide), so no accumulator of one pass is live in the other.  The z-constrained instantiation (16 slots) takes one pass.
+constexpr double kIcpGenKappa = 1.0 - 1e-3;   // 1 - eps
+constexpr int kIcpGenSplit = 15;              // full rotation: slots [0, 15) in pass 0, [15, 29) in pass 1
 
-// shared driver of the point-to-plane entry points: clouds already on the device
-int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* init, double radius, double normal_radius, int its, bool full, double* out,
-                  double* fitness, double* rmse, int* iters, const IcpPlaneTrace* trace = nullptr, const alignnet::IcpDeviceIo* dev = nullptr)
+// a pair's workspace: the point-to-plane layout of the target | source grid | its records, index-ordered [n1] float4 | source normals [n1][3] doubles |
+// source neighbour counts [n1] ints | correspondences [n1] ints
+__host__ __device__ inline size_t icp_gen_source_off(long long n2) { return icp_plane_pair_bytes(n2); }
+__host__ __device__ inline size_t icp_gen_sorted_off(long long n1) { return icp_grid_pair_bytes(n1); }   // (from the source part's head)
+__host__ __device__ inline size_t icp_gen_normals_off(long long n1) { return icp_gen_sorted_off(n1) + icp_r256((size_t)n1 * 16); }
+__host__ __device__ inline size_t icp_gen_counts_off(long long n1) { return icp_gen_normals_off(n1) + icp_r256((size_t)n1 * 24); }
+__host__ __device__ inline size_t icp_gen_corr_off(long long n1) { return icp_gen_counts_off(n1) + icp_r256((size_t)n1 * 4); }
+__host__ __device__ inline size_t icp_gen_pair_bytes(long long n1, long long n2) { return icp_gen_source_off(n2) + icp_gen_corr_off(n1) + icp_r256((size_t)n1 * 4); }
+
+// the three source kernels: blockIdx.x = pair for the build, pair * parts + part for the other two (IcpPlaneArgs as the target's kernels take it)
+__global__ __launch_bounds__(kIcpThreads) void icp_generalized_build_source_kernel(const IcpPlaneArgs a)
+{
+  const int b = blockIdx.x;
+  const long long row = a.rows ? a.rows[b] : b;
+  const long long s_lo = a.off[row * 2], n1 = a.off[(row + 1) * 2] - s_lo;
+  const long long n2 = a.off[(row + 1) * 2 + 1] - a.off[row * 2 + 1];
+  icp_grid_build_cloud(a.pts[0] + s_lo * 3, n1, a.ws + a.ws_off[b] + icp_gen_source_off(n2), a.normal_radius);
+}
+
+__global__ __launch_bounds__(kIcpPlaneLanes) void icp_generalized_sort_source_kernel(const IcpPlaneArgs a)
+{
+  const int b = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
+  const long long row = a.rows ? a.rows[b] : b;
+  const long long n1 = a.off[(row + 1) * 2] - a.off[row * 2], n2 = a.off[(row + 1) * 2 + 1] - a.off[row * 2 + 1];
+  char* const ws = a.ws + a.ws_off[b] + icp_gen_source_off(n2);
+  icp_plane_sort_cloud(icp_grid_view(ws, n1), reinterpret_cast<float4*>(ws + icp_gen_sorted_off(n1)), n1, part, a.parts);
+}
+
+__global__ __launch_bounds__(kIcpPlaneLanes) void icp_generalized_normals_source_kernel(const IcpPlaneArgs a)
+{
+  const int b = blockIdx.x / a.parts, part = blockIdx.x % a.parts;
+  const long long row = a.rows ? a.rows[b] : b;
+  const long long s_lo = a.off[row * 2], n1 = a.off[(row + 1) * 2] - s_lo;
+  const long long n2 = a.off[(row + 1) * 2 + 1] - a.off[row * 2 + 1];
+  char* const ws = a.ws + a.ws_off[b] + icp_gen_source_off(n2);
+  icp_plane_normals_cloud(a.pts[0] + s_lo * 3, n1, icp_grid_view(ws, n1), reinterpret_cast<const float4*>(ws + icp_gen_sorted_off(n1)),
+                          reinterpret_cast<double*>(ws + icp_gen_normals_off(n1)), reinterpret_cast<int*>(ws + icp_gen_counts_off(n1)), a.normal_radius,
+                          part, a.parts);
+}
+
+// column k of J's rotation block (e_k x a) times the vector x, its zero left out: (0, -a_z, a_y), (a_z, 0, -a_x), (-a_y, a_x, 0)
+__device__ __forceinline__ double icp_gen_rotdot(int k, double ax, double ay, double az, double x0, double x1, double x2)
+{
+#pragma clang fp contract(off)
+  return k == 0 ? (-az) * x1 + ay * x2 : k == 1 ? az * x0 + (-ax) * x2 : (-ay) * x0 + ax * x1;
+}
+
+// the terms of one correspondence in the slots [kLo, kHi) added onto v[0 .. kHi - kLo): p, q the points, nq / np the target's and the source's normal,
+// T the current transform (its rotation turns np), c the pivot, best the squared distance.  No contraction, the restatement's order
+template <bool kFull, int kLo, int kHi>
+__device__ __forceinline__ void icp_generalized_terms(double px, double py, double pz, double qx, double qy, double qz, const double* nq, const double* np,
+                                                      const double* T, double cx, double cy, double cz, double best, double (&v)[kHi - kLo])
+{
+#pragma clang fp contract(off)
+  constexpr int N = kFull ? 6 : 4, R = kFull ? 3 : 1, kRot0 = kFull ? 0 : 2;   // columns; rotation columns; the axis of the first of them
+  const double m0 = (T[0] * np[0] + T[1] * np[1]) + T[2] * np[2];
+  const double m1 = (T[4] * np[0] + T[5] * np[1]) + T[6] * np[2];
+  const double m2 = (T[8] * np[0] + T[9] * np[1]) + T[10] * np[2];
+  const double a00 = 2.0 - kIcpGenKappa * (nq[0] * nq[0] + m0 * m0), a01 = -(kIcpGenKappa * (nq[0] * nq[1] + m0 * m1));
+  const double a02 = -(kIcpGenKappa * (nq[0] * nq[2] + m0 * m2)), a11 = 2.0 - kIcpGenKappa * (nq[1] * nq[1] + m1 * m1);
+  const double a12 = -(kIcpGenKappa * (nq[1] * nq[2] + m1 * m2)), a22 = 2.0 - kIcpGenKappa * (nq[2] * nq[2] + m2 * m2);
+  const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
+  const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
+  const double det = (a00 * c00 + a01 * c01) + a02 * c02;
+  double M[3][3];
+  M[0][0] = c00 / det; M[0][1] = M[1][0] = c01 / det; M[0][2] = M[2][0] = c02 / det;
+  M[1][1] = c11 / det; M[1][2] = M[2][1] = c12 / det; M[2][2] = c22 / det;
+  const double dx = px - qx, dy = py - qy, dz = pz - qz, ax = px - cx, ay = py - cy, az = pz - cz;
+  double W[3][N], w[3];   // M J, M d
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) W[r][k] = icp_gen_rotdot(kRot0 + k, ax, ay, az, M[r][0], M[r][1], M[r][2]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) W[r][R + j] = M[r][j];
+    w[r] = (M[r][0] * dx + M[r][1] * dy) + M[r][2] * dz;
+  }
+  double t[kFull ? kIcpPlaneSumsFull : kIcpPlaneSums];
+  t[0] = 1.0; t[1] = best;
+  int q = 2;
+#pragma unroll
+  for (int k = 0; k < N; ++k)
+#pragma unroll
+    for (int l = k; l < N; ++l) t[q++] = k < R ? icp_gen_rotdot(kRot0 + k, ax, ay, az, W[0][l], W[1][l], W[2][l]) : W[k - R][l];
+#pragma unroll
+  for (int k = 0; k < N; ++k) t[q++] = k < R ? icp_gen_rotdot(kRot0 + k, ax, ay, az, w[0], w[1], w[2]) : w[k - R];
+#pragma unroll
+  for (int s = kLo; s < kHi; ++s) v[s - kLo] += t[s];
+}
+
+// kTrace (alignnet_debug_icp_generalized, one pair): as icp_plane_kernel's
+template <bool kFull, bool kTrace = false>
+__global__ __launch_bounds__(kIcpThreads) void icp_generalized_kernel(const IcpPlaneArgs a)
+{
+  constexpr int kSums = kFull ? kIcpPlaneSumsFull : kIcpPlaneSums, kFirst = kFull ? kIcpGenSplit : kSums;   // kFirst: the slots of pass 0
+  extern __shared__ __attribute__((aligned(16))) int gstart[];   // [H + 1] bucket starts of grid A
+  __shared__ double T[12];
+  __shared__ double red[(kIcpThreads / 64) * kFirst], tot[kSums];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const long long row = a.rows ? a.rows[b] : b;
+  const long long s_lo = a.off[row * 2], n1 = a.off[(row + 1) * 2] - s_lo;
+  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
+  const float* src = a.pts[0] + s_lo * 3;
+  const float* dst = a.pts[1] + t_lo * 3;
+  if (tid < 12) T[tid] = a.init[(size_t)b * 16 + tid];
+  IcpGridView g = icp_grid_view(a.ws + a.ws_off[b], n2);
+  const double* const nrm = icp_plane_normals(g, n2);
+  const char* const sws = g.ws + icp_gen_source_off(n2);
+  const double* const snrm = reinterpret_cast<const double*>(sws + icp_gen_normals_off(n1));
+  [[maybe_unused]] int* const corr = reinterpret_cast<int*>(g.ws + icp_gen_source_off(n2) + icp_gen_corr_off(n1));
+  for (int j = tid; j <= g.buckets; j += kIcpThreads) gstart[j] = g.start[j];
+  g.start = gstart;   // the search reads the LDS copy
+  __syncthreads();
+  const double r2 = a.radius * a.radius;
+  const double cx = n2 > 0 ? (double)dst[0] : 0.0, cy = n2 > 0 ? (double)dst[1] : 0.0, cz = n2 > 0 ? (double)dst[2] : 0.0;   // the pivot of icp_kernel
+  double fit_prev = 0.0, rmse_prev = 0.0, fit = 0.0, rmse = 0.0;
+  int k = 0;
+  if (n1 > 0 && n2 > 0)
+    for (k = 0;; ++k) {
+      {
+        double v[kFirst];
+#pragma unroll
+        for (int q = 0; q < kFirst; ++q) v[q] = 0.0;
+        for (long long i = tid; i < n1; i += kIcpThreads) {
+          const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
+          const double px = icp_affine_unfused(T[0], T[1], T[2], T[3], sx, sy, sz);
+          const double py = icp_affine_unfused(T[4], T[5], T[6], T[7], sx, sy, sz);
+          const double pz = icp_affine_unfused(T[8], T[9], T[10], T[11], sx, sy, sz);
+          double best = 1e300; int bj = 0x7fffffff;
+          float4 brec = {0.f, 0.f, 0.f, 0.f};
+          int cand = 0;   // (counted by icp_kernel's traced instantiation alone)
+          icp_grid_nearest<false>(px, py, pz, g, best, bj, brec, cand);
+          const bool inlier = best <= r2;
+          if constexpr (kFull) corr[i] = inlier ? bj : -1;
+          if (inlier)
+            icp_generalized_terms<kFull, 0, kFirst>(px, py, pz, (double)brec.x, (double)brec.y, (double)brec.z, nrm + (size_t)bj * 3, snrm + (size_t)i * 3, T,
+                                                    cx, cy, cz, best, v);
+          if constexpr (kTrace) {
+            if (k == 0) {
+              const bool found = bj != 0x7fffffff;
+              a.tr_index[i] = found ? bj : -1; a.tr_dist[i] = found ? best : __builtin_huge_val(); a.tr_inlier[i] = inlier;
+            }
+          }
+        }
+        block_reduce(v, red, tot);
+      }
+      if constexpr (kFull) {   // pass 1: the lane's own correspondences again, the other slots
+        double v[kSums - kFirst];
+#pragma unroll
+        for (int q = 0; q < kSums - kFirst; ++q) v[q] = 0.0;
+        for (long long i = tid; i < n1; i += kIcpThreads) {
+          const int bj = corr[i];
+          if (bj < 0) continue;
+          const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
+          const double px = icp_affine_unfused(T[0], T[1], T[2], T[3], sx, sy, sz);
+          const double py = icp_affine_unfused(T[4], T[5], T[6], T[7], sx, sy, sz);
+          const double pz = icp_affine_unfused(T[8], T[9], T[10], T[11], sx, sy, sz);
+          icp_generalized_terms<kFull, kFirst, kSums>(px, py, pz, (double)dst[(size_t)bj * 3], (double)dst[(size_t)bj * 3 + 1], (double)dst[(size_t)bj * 3 + 2],
+                                                      nrm + (size_t)bj * 3, snrm + (size_t)i * 3, T, cx, cy, cz, 0.0, v);
+        }
+        block_reduce(v, red, tot + kFirst);
+      }
+      const double cnt = tot[0];
+      fit = cnt / (double)n1;
+      rmse = cnt > 0.0 ? sqrt(tot[1] / cnt) : 0.0;
+      if constexpr (kTrace) {
+        if (tid == 0) {
+          double U[12];
+          icp_plane_update<kFull>(tot, cx, cy, cz, U);
+          for (int q = 0; q < kIcpPlaneSumsFull; ++q) a.tr_sums[q] = q < kSums ? tot[q] : 0.0;
+          for (int q = 0; q < 12; ++q) a.tr_update[q] = U[q];
+        }
+        break;
+      }
+      if (k > 0 && fabs(fit - fit_prev) < 1e-6 && fabs(rmse - rmse_prev) < 1e-6) break;
+      if (k == a.its) break;
+      fit_prev = fit; rmse_prev = rmse;
+      if (tid == 0) {
+        double U[12], n[12];
+        if (icp_plane_update<kFull>(tot, cx, cy, cz, U)) {   // T <- U T
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int col = 0; col < 4; ++col) n[r * 4 + col] = U[r * 4] * T[col] + U[r * 4 + 1] * T[4 + col] + U[r * 4 + 2] * T[8 + col];
+            n[r * 4 + 3] += U[r * 4 + 3];
+          }
+          for (int q = 0; q < 12; ++q) T[q] = n[q];
+        }
+      }
+      __syncthreads();
+    }
+  __syncthreads();
+  if (tid < 12) a.out[(size_t)b * 16 + tid] = T[tid];
+  if (tid >= 12 && tid < 16) a.out[(size_t)b * 16 + tid] = tid == 15 ? 1.0 : 0.0;
+  if (tid == 0) {
+    if (a.fitness) a.fitness[b] = fit;
+    if (a.rmse) a.rmse[b] = rmse;
+    if (a.iters) a.iters[b] = k;
+  }
+}
+
+// alignnet_debug_icp_plane / _generalized: host arrays of the one pair (resid: point-to-plane; src_normals / src_neighbours: generalized; else null)
+struct IcpPlaneTrace {
+  long long n1, n2; double* normals; int* neighbours; int* index; double* dist; int* inlier; double* resid; double* sums; double* update;
+  double* src_normals = nullptr; int* src_neighbours = nullptr;
+};
+
+// shared driver of the point-to-plane and (gen) the generalized entry points: clouds already on the device
+int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* init, double radius, double normal_radius, int its, bool full, bool gen,
+                  double* out, double* fitness, double* rmse, int* iters, const IcpPlaneTrace* trace = nullptr, const alignnet::IcpDeviceIo* dev = nullptr)
 {
   // dev: as in run_icp
   const std::vector<long long>& n2 = c.n2;
-  if (!init || !out) return fail(h, "icp_plane: null init / out");
-  if (!(radius > 0.0) || !(normal_radius > 0.0) || its < 0) return fail(h, "icp_plane: radius and normal_radius must be > 0 and its >= 0");
-  // consecutive pairs form chunks of at most kIcpGridWsBudget of workspace (two grids, the ordered records, normals and counts per pair; one pair may
-  // exceed it alone); every chunk reuses the handle's workspace -- the grid search's -- in stream order
+  const std::vector<long long>& n1 = c.n1;   // (read by the generalized estimate alone)
+  const std::string what(gen ? "icp_generalized" : "icp_plane");
+  if (!init || !out) return fail(h, what + ": null init / out");
+  if (!(radius > 0.0) || !(normal_radius > 0.0) || its < 0) return fail(h, what + ": radius and normal_radius must be > 0 and its >= 0");
+  if (gen && (int)n1.size() != B) return fail(h, what + ": the source sizes are not known");
+  // consecutive pairs form chunks of at most kIcpGridWsBudget of workspace (two grids, the ordered records, normals and counts per pair, and with gen the
+  // source's part behind them; one pair may exceed it alone); every chunk reuses the handle's workspace -- the grid search's -- in stream order
   std::vector<long long> ws_off_own;
   std::vector<long long>& ws_off = dev ? *dev->h_ws_off : ws_off_own;
   ws_off.assign(2 * (size_t)B, 0);
   std::vector<int> first;   // the chunks' first pairs
-  const size_t budget = h->icp_plane_ws_budget ? h->icp_plane_ws_budget : kIcpGridWsBudget;
+  const size_t own_budget = gen ? h->icp_generalized_ws_budget : h->icp_plane_ws_budget, budget = own_budget ? own_budget : kIcpGridWsBudget;
   constexpr int kChunkPairs = 1 << 20;   // pairs x parts (<= 1024) of a chunk stay a valid gridDim.x
   size_t need = 0, cur = 0;
   for (int b = 0; b < B; ++b) {
-    if (n2[b] > 0x7fffffff) return fail(h, "icp_plane: more than 2^31 - 1 target points in a pair");
-    const size_t bytes = icp_plane_pair_bytes(n2[b]);
+    if (n2[b] > 0x7fffffff) return fail(h, what + ": more than 2^31 - 1 target points in a pair");
+    if (gen && n1[b] > 0x7fffffff) return fail(h, what + ": more than 2^31 - 1 source points in a pair");
+    const size_t bytes = gen ? icp_gen_pair_bytes(n1[b], n2[b]) : icp_plane_pair_bytes(n2[b]);
     if (b == 0 || cur + bytes > budget || b - first.back() >= kChunkPairs) { first.push_back(b); cur = 0; }
     ws_off[b] = (long long)cur; ws_off[(size_t)B + b] = (long long)(cur + icp_grid_pair_bytes(n2[b]));
     cur += bytes;
     need = std::max(need, cur);
   }
   first.push_back(B);
-  h->icp_plane_chunks = (int)first.size() - 1;
+  (gen ? h->icp_generalized_chunks : h->icp_plane_chunks) = (int)first.size() - 1;
   if (reserve_grid_ws(h, need)) return 1;
   IcpPlaneArgs a;
   IcpResults res;
@@ -1211,14 +1462,20 @@ int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* i
     a.tr_dist = trd.p; a.tr_resid = trd.p + tn; a.tr_sums = trd.p + 2 * tn; a.tr_update = a.tr_sums + kIcpPlaneSumsFull;
     a.tr_index = tri.p; a.tr_inlier = tri.p + tn;
   }
-  static alignnet::PerDeviceOnce attr[4];
-  const int which = (full ? 1 : 0) + (trace ? 2 : 0);
-  const void* const kernels[4] = {reinterpret_cast<const void*>(icp_plane_kernel<false>), reinterpret_cast<const void*>(icp_plane_kernel<true>),
-                                  reinterpret_cast<const void*>(icp_plane_kernel<false, true>), reinterpret_cast<const void*>(icp_plane_kernel<true, true>)};
-  if (attr[which].need(h->cfg.device)) {
-    HIP_TRY(h, hipFuncSetAttribute(kernels[which], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+  static alignnet::PerDeviceOnce attr[8];
+  const int which = (full ? 1 : 0) + (trace ? 2 : 0), slot = which + (gen ? 4 : 0);
+  const void* const kernels[8] = {reinterpret_cast<const void*>(icp_plane_kernel<false>), reinterpret_cast<const void*>(icp_plane_kernel<true>),
+                                  reinterpret_cast<const void*>(icp_plane_kernel<false, true>), reinterpret_cast<const void*>(icp_plane_kernel<true, true>),
+                                  reinterpret_cast<const void*>(icp_generalized_kernel<false>), reinterpret_cast<const void*>(icp_generalized_kernel<true>),
+                                  reinterpret_cast<const void*>(icp_generalized_kernel<false, true>),
+                                  reinterpret_cast<const void*>(icp_generalized_kernel<true, true>)};
+  if (attr[slot].need(h->cfg.device)) {
+    HIP_TRY(h, hipFuncSetAttribute(kernels[slot], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(icp_grid_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
-    attr[which].mark(h->cfg.device);
+    if (gen)
+      HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(icp_generalized_build_source_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     160 * 1024 - 4096));
+    attr[slot].mark(h->cfg.device);
   }
   for (size_t c = 0; c + 1 < first.size(); ++c) {
     const int lo = first[c], hi = first[c + 1];
@@ -1228,20 +1485,40 @@ int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* i
     const size_t lds = ((size_t)icp_grid_buckets(big) + 1) * 4;
     IcpGridArgs ga = r, gb = r;
     gb.radius = normal_radius; gb.ws_off = r.ws_off_b;
+    const long long big1 = gen ? *std::max_element(n1.begin() + lo, n1.begin() + hi) : 0;   // the chunk's largest source
     {
       alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID_BUILD);
       hipLaunchKernelGGL(icp_grid_build_kernel, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, ga);
       hipLaunchKernelGGL(icp_grid_build_kernel, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, gb);
+      if (gen)
+        hipLaunchKernelGGL(icp_generalized_build_source_kernel, dim3(hi - lo), dim3(kIcpThreads), ((size_t)icp_grid_buckets(big1) + 1) * 4, h->stream, r);
     }
     if (big > 0) {
       // the parts per pair are sized by the chunk's largest target: a small pair beside a large one launches workgroups that find nothing to do
-      alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_PLANE_NORMALS);
+      alignnet::ProfScope prof_scope(h, gen ? alignnet::PK_ICP_GENERALIZED_NORMALS : alignnet::PK_ICP_PLANE_NORMALS);
       r.parts = (int)std::min<long long>((big + kIcpPlaneLanes - 1) / kIcpPlaneLanes, kIcpPlaneMaxBlocks);
       const dim3 blocks((unsigned)r.parts * (unsigned)(hi - lo));
       hipLaunchKernelGGL(icp_plane_sort_kernel, blocks, dim3(kIcpPlaneLanes), 0, h->stream, r);
       hipLaunchKernelGGL(icp_plane_normals_kernel, blocks, dim3(kIcpPlaneLanes), 0, h->stream, r);
     }
-    alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_PLANE);
+    if (big1 > 0) {   // the source's, its parts sized by the chunk's largest source
+      alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GENERALIZED_NORMALS);
+      r.parts = (int)std::min<long long>((big1 + kIcpPlaneLanes - 1) / kIcpPlaneLanes, kIcpPlaneMaxBlocks);
+      const dim3 blocks((unsigned)r.parts * (unsigned)(hi - lo));
+      hipLaunchKernelGGL(icp_generalized_sort_source_kernel, blocks, dim3(kIcpPlaneLanes), 0, h->stream, r);
+      hipLaunchKernelGGL(icp_generalized_normals_source_kernel, blocks, dim3(kIcpPlaneLanes), 0, h->stream, r);
+    }
+    alignnet::ProfScope prof_scope(h, gen ? alignnet::PK_ICP_GENERALIZED : alignnet::PK_ICP_PLANE);
+    if (gen) {
+      if (which == 3)
+        hipLaunchKernelGGL((icp_generalized_kernel<true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      else if (which == 2)
+        hipLaunchKernelGGL((icp_generalized_kernel<false, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      else if (full)
+        hipLaunchKernelGGL(icp_generalized_kernel<true>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      else
+        hipLaunchKernelGGL(icp_generalized_kernel<false>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+    } else
     if (which == 3)
       hipLaunchKernelGGL((icp_plane_kernel<true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
     else if (which == 2)
@@ -1259,9 +1536,14 @@ int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* i
       HIP_TRY(h, hipMemcpyAsync(trace->normals, base + icp_plane_normals_off(trace->n2), t2 * 24, hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(h, hipMemcpyAsync(trace->neighbours, base + icp_plane_counts_off(trace->n2), t2 * 4, hipMemcpyDeviceToHost, h->stream));
     }
+    if (gen && m) {   // (one pair: its source part sits behind the target's)
+      const char* const sws = base + icp_gen_source_off(trace->n2);
+      HIP_TRY(h, hipMemcpyAsync(trace->src_normals, sws + icp_gen_normals_off(trace->n1), m * 24, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(trace->src_neighbours, sws + icp_gen_counts_off(trace->n1), m * 4, hipMemcpyDeviceToHost, h->stream));
+    }
     if (m) {
       HIP_TRY(h, hipMemcpyAsync(trace->dist, trd.p, m * 8, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(trace->resid, trd.p + tn, m * 8, hipMemcpyDeviceToHost, h->stream));
+      if (trace->resid) HIP_TRY(h, hipMemcpyAsync(trace->resid, trd.p + tn, m * 8, hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(h, hipMemcpyAsync(trace->index, tri.p, m * 4, hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(h, hipMemcpyAsync(trace->inlier, tri.p + tn, m * 4, hipMemcpyDeviceToHost, h->stream));
     }
@@ -1273,12 +1555,12 @@ int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* i
 }
 
 int icp_plane_host(alignnet_handle* h, const char* fn, const float* points1, const float* points2, const int64_t* offsets, int32_t B, const double* init,
-                   double radius, double normal_radius, int32_t its, bool full, double* out, double* fitness, double* rmse, int32_t* iterations,
+                   double radius, double normal_radius, int32_t its, bool full, bool gen, double* out, double* fitness, double* rmse, int32_t* iterations,
                    const IcpPlaneTrace* trace = nullptr)
 {
   IcpClouds c;
   if (stage_host(h, fn, points1, points2, offsets, B, &c)) return 1;
-  return run_icp_plane(h, c, B, init, radius, normal_radius, its, full, out, fitness, rmse, iterations, trace);
+  return run_icp_plane(h, c, B, init, radius, normal_radius, its, full, gen, out, fitness, rmse, iterations, trace);
 }
 
 // flags of alignnet_icp_register*: bit 0 = full rotation; no other bit is defined
@@ -1291,15 +1573,17 @@ int icp_flags(alignnet_handle* h, const char* fn, int32_t flags, bool* full)
 
 }  // namespace
 
-int alignnet_icp_run_device(alignnet_handle* h, const float* const pts[2], const long long* off, const int* rows, const long long* n2, long long stage_n2,
-                            int B, const alignnet::IcpDeviceIo& io, double radius, double normal_radius, int its, bool full, bool plane)
+int alignnet_icp_run_device(alignnet_handle* h, const float* const pts[2], const long long* off, const int* rows, const long long* n1, const long long* n2,
+                            long long stage_n2, int B, const alignnet::IcpDeviceIo& io, double radius, double normal_radius, int its, bool full, int estimate)
 {
   if (!h) return 1;
-  if (!pts[0] || !pts[1] || !off || !n2 || B < 1 || !io.ws_off || !io.h_ws_off) return fail(h, "icp: null device argument or B < 1");
+  if (!pts[0] || !pts[1] || !off || (estimate == 4 && !n1) || !n2 || B < 1 || !io.ws_off || !io.h_ws_off) return fail(h, "icp: null device argument or B < 1");
   IcpClouds c;   // (nothing of it is uploaded here: its buffers stay empty)
   c.pts[0] = pts[0]; c.pts[1] = pts[1]; c.off = off; c.rows = rows;
   c.n2.assign(n2, n2 + B);
-  if (plane) return run_icp_plane(h, c, B, io.init, radius, normal_radius, its, full, io.out, io.fitness, io.rmse, io.iters, nullptr, &io);
+  if (n1) c.n1.assign(n1, n1 + B);
+  if (estimate >= 2)
+    return run_icp_plane(h, c, B, io.init, radius, normal_radius, its, full, estimate == 4, io.out, io.fitness, io.rmse, io.iters, nullptr, &io);
   return run_icp(h, c, stage_n2 > 0 ? stage_n2 : kIcpLdsBudget, B, io.init, radius, its, full, io.out, io.fitness, io.rmse, io.iters, nullptr, &io);
 }
 
@@ -1410,7 +1694,7 @@ extern "C" int alignnet_icp_plane_register(alignnet_handle* h, const float* poin
   if (!h) return 1;
   bool full = false;
   if (icp_flags(h, "alignnet_icp_plane_register", flags, &full)) return 1;
-  return icp_plane_host(h, "alignnet_icp_plane_register", points1, points2, offsets, B, init, radius, normal_radius, its, full, out, fitness, rmse, iterations);
+  return icp_plane_host(h, "alignnet_icp_plane_register", points1, points2, offsets, B, init, radius, normal_radius, its, full, false, out, fitness, rmse, iterations);
 }
 
 extern "C" int alignnet_icp_plane_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
@@ -1423,7 +1707,7 @@ extern "C" int alignnet_icp_plane_register_dataset(alignnet_handle* h, const int
   if (icp_flags(h, name.c_str(), flags, &full)) return 1;
   IcpClouds c;
   if (stage_rows(h, name, rows, B, &c)) return 1;
-  return run_icp_plane(h, c, B, init, radius, normal_radius, its, full, out, fitness, rmse, iterations);
+  return run_icp_plane(h, c, B, init, radius, normal_radius, its, full, false, out, fitness, rmse, iterations);
 }
 
 extern "C" int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2, const double* T,
@@ -1440,7 +1724,54 @@ extern "C" int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1
   double up[12];
   const IcpPlaneTrace tr = {n1, n2, normals, neighbours, index, dist2, inlier, residual, sums, up};
   double out[16];
-  if (icp_plane_host(h, name.c_str(), points1, points2, off, 1, T, radius, normal_radius, 0, full, out, fitness, rmse, nullptr, &tr)) return 1;
+  if (icp_plane_host(h, name.c_str(), points1, points2, off, 1, T, radius, normal_radius, 0, full, false, out, fitness, rmse, nullptr, &tr)) return 1;
+  const bool ran = n1 > 0 && n2 > 0;   // (an empty cloud: no evaluation, no update)
+  for (int q = 0; q < 16; ++q) update[q] = q < 12 && ran ? up[q] : (q % 5 == 0 ? 1.0 : 0.0);
+  return 0;
+}
+
+extern "C" int alignnet_icp_generalized_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B,
+                                                 const double* init, double radius, double normal_radius, int32_t its, int32_t flags, double* out,
+                                                 double* fitness, double* rmse, int32_t* iterations)
+{
+  if (!h) return 1;
+  bool full = false;
+  if (icp_flags(h, "alignnet_icp_generalized_register", flags, &full)) return 1;
+  return icp_plane_host(h, "alignnet_icp_generalized_register", points1, points2, offsets, B, init, radius, normal_radius, its, full, true, out, fitness,
+                        rmse, iterations);
+}
+
+extern "C" int alignnet_icp_generalized_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
+                                                         double normal_radius, int32_t its, int32_t flags, double* out, double* fitness, double* rmse,
+                                                         int32_t* iterations)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_icp_generalized_register_dataset");
+  bool full = false;
+  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
+  IcpClouds c;
+  if (stage_rows(h, name, rows, B, &c)) return 1;
+  return run_icp_plane(h, c, B, init, radius, normal_radius, its, full, true, out, fitness, rmse, iterations);
+}
+
+extern "C" int alignnet_debug_icp_generalized(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2, const double* T,
+                                              double radius, double normal_radius, int32_t flags, double* target_normals, int32_t* target_neighbours,
+                                              double* source_normals, int32_t* source_neighbours, int32_t* index, double* dist2, int32_t* inlier,
+                                              double* sums, double* update, double* fitness, double* rmse)
+{
+  if (!h) return 1;
+  const std::string name("alignnet_debug_icp_generalized");
+  bool full = false;
+  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
+  if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(h, name + ": n1 / n2 out of range");
+  if (!target_normals || !target_neighbours || !source_normals || !source_neighbours || !index || !dist2 || !inlier || !sums || !update)
+    return fail(h, name + ": null output");
+  const int64_t off[4] = {0, 0, n1, n2};
+  double up[12];
+  IcpPlaneTrace tr = {n1, n2, target_normals, target_neighbours, index, dist2, inlier, nullptr, sums, up};
+  tr.src_normals = source_normals; tr.src_neighbours = source_neighbours;
+  double out[16];
+  if (icp_plane_host(h, name.c_str(), points1, points2, off, 1, T, radius, normal_radius, 0, full, true, out, fitness, rmse, nullptr, &tr)) return 1;
   const bool ran = n1 > 0 && n2 > 0;   // (an empty cloud: no evaluation, no update)
   for (int q = 0; q < 16; ++q) update[q] = q < 12 && ran ? up[q] : (q % 5 == 0 ? 1.0 : 0.0);
   return 0;

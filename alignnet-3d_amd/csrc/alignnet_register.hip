@@ -4,7 +4,7 @@
 // (train.py:447-481): eight tensors come down, three list comprehensions decode the yaws (models/tp8.py:55-65), get_mat_angle runs once per
 // sample (evaluation.py:46-57) and the 4x4 inits go up again for the ICP call.  Here the same chain is queued on the handle's stream in one piece:
 //   dataset_sample_kernel (alignnet_dataset.hip) -> the eval forward (alignnet_forward_device) -> register_decode_kernel -> register_init_kernel
-//   -> [the loss of alignnet_eval_loss on the dataset's labels] -> [icp_kernel / icp_plane_kernel from the device-resident T_net] -> downloads
+//   -> [the loss of alignnet_eval_loss on the dataset's labels] -> [icp_kernel / icp_plane_kernel / icp_generalized_kernel from the device-resident T_net] -> downloads
 // and the host waits once, at the end.  Every buffer lives in RegisterWS on the handle: it grows when B grows (and, for clouds from the host, when
 // they do), so a steady-state call allocates nothing.  The two kernels here are a few hundred flops per pair; what matters is that they are two
 // launches between two latency-critical stages and that their fp64 arithmetic is NumPy's to the last bit (no contraction).
@@ -28,7 +28,7 @@ struct RegisterWS {
   int *rows = nullptr, *iters = nullptr;
   float* cloud[2] = {nullptr, nullptr};   // clouds from the host, each grown on its own
   size_t cloud_cap[2] = {0, 0};           // points
-  std::vector<long long> h_ws_off, h_n2;  // host staging that must outlive the queued copies
+  std::vector<long long> h_ws_off, h_n1, h_n2;  // host staging that must outlive the queued copies
 };
 
 RegisterWS* rws(alignnet_handle* h) { return static_cast<RegisterWS*>(h->register_ws); }
@@ -150,7 +150,8 @@ int check_options(alignnet_handle* h, const std::string& name, const alignnet_re
 {
   if (!o || !out) return fail(h, name + ": null options / outputs");
   if (!out->transforms) return fail(h, name + ": outputs->transforms must not be null");
-  if (o->refine < 0 || o->refine > 2) return fail(h, name + ": refine must be 0 (none), 1 (point-to-point) or 2 (point-to-plane), got " + std::to_string(o->refine));
+  if (o->refine < 0 || o->refine == 3 || o->refine > 4)
+    return fail(h, name + ": refine must be 0 (none), 1 (point-to-point), 2 (point-to-plane) or 4 (generalized), got " + std::to_string(o->refine));
   if (o->its < 0) return fail(h, name + ": its must be >= 0");
   if (o->flags & ~ALIGNNET_ICP_FULL_ROTATION) return fail(h, name + ": unknown flags " + std::to_string(o->flags) + " (ALIGNNET_ICP_FULL_ROTATION is the only one)");
   if (o->refine == 0) {
@@ -158,14 +159,14 @@ int check_options(alignnet_handle* h, const std::string& name, const alignnet_re
     if (out->fitness || out->rmse || out->iterations) return fail(h, name + ": fitness / rmse / iterations are results of the refinement (refine is 0)");
   } else {
     if (!(o->radius > 0.0)) return fail(h, name + ": radius must be > 0");
-    if (o->refine == 2 && !(o->normal_radius > 0.0)) return fail(h, name + ": normal_radius must be > 0");
+    if (o->refine >= 2 && !(o->normal_radius > 0.0)) return fail(h, name + ": normal_radius must be > 0");
   }
   if (out->loss && !dataset) return fail(h, name + ": loss needs the dataset's labels (alignnet_register_dataset)");
   return 0;
 }
 
-// everything behind the staging: src names the clouds on the device, n2 the B target sizes, stage_n2 the ICP scan's LDS stage (<= 0: its budget)
-int run(alignnet_handle* h, const alignnet::SampleSource& src, const long long* n2, long long stage_n2, int B, uint64_t seed,
+// everything behind the staging: src names the clouds on the device, n1 / n2 the B source / target sizes, stage_n2 the ICP scan's LDS stage (<= 0: its budget)
+int run(alignnet_handle* h, const alignnet::SampleSource& src, const long long* n1, const long long* n2, long long stage_n2, int B, uint64_t seed,
         const alignnet_register_options* o, const alignnet_register_outputs* out)
 {
   RegisterWS* w = rws(h);
@@ -182,8 +183,8 @@ int run(alignnet_handle* h, const alignnet::SampleSource& src, const long long* 
   if (out->loss && alignnet_eval_loss_launch(h, &lab, B, w->loss)) return 1;
   if (o->refine) {
     const alignnet::IcpDeviceIo io = {w->tnet, w->refined, w->fit, w->rmse, w->iters, w->ws_off, &w->h_ws_off};
-    if (alignnet_icp_run_device(h, src.pts, src.off, src.rows, n2, stage_n2, B, io, o->radius, o->normal_radius, o->its,
-                                (o->flags & ALIGNNET_ICP_FULL_ROTATION) != 0, o->refine == 2))
+    if (alignnet_icp_run_device(h, src.pts, src.off, src.rows, n1, n2, stage_n2, B, io, o->radius, o->normal_radius, o->its,
+                                (o->flags & ALIGNNET_ICP_FULL_ROTATION) != 0, o->refine))
       return 1;
   }
   // downloads, then the call's one synchronisation
@@ -234,10 +235,13 @@ extern "C" int alignnet_register_dataset(alignnet_handle* h, const int32_t* rows
   if (ensure(h, B)) return 1;
   RegisterWS* w = rws(h);
   HIP_TRY(h, hipMemcpyAsync(w->rows, rows, (size_t)B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  w->h_n2.resize(B);
-  for (int i = 0; i < B; ++i) w->h_n2[i] = t.h_off[((size_t)rows[i] + 1) * 2 + 1] - t.h_off[(size_t)rows[i] * 2 + 1];
+  w->h_n1.resize(B); w->h_n2.resize(B);
+  for (int i = 0; i < B; ++i) {
+    w->h_n1[i] = t.h_off[((size_t)rows[i] + 1) * 2] - t.h_off[(size_t)rows[i] * 2];
+    w->h_n2[i] = t.h_off[((size_t)rows[i] + 1) * 2 + 1] - t.h_off[(size_t)rows[i] * 2 + 1];
+  }
   const alignnet::SampleSource src = {{t.pts[0], t.pts[1]}, t.off, t.labels, w->rows, nullptr};
-  return run(h, src, w->h_n2.data(), 0, B, seed, options, outputs);
+  return run(h, src, w->h_n1.data(), w->h_n2.data(), 0, B, seed, options, outputs);
 }
 
 extern "C" int alignnet_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets, int32_t B, uint64_t seed,
@@ -260,8 +264,8 @@ extern "C" int alignnet_register(alignnet_handle* h, const float* points1, const
     if (np[t]) HIP_TRY(h, hipMemcpyAsync(w->cloud[t], host[t], np[t] * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(w->off, offsets, (size_t)(B + 1) * 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
   if (streams) HIP_TRY(h, hipMemcpyAsync(w->streams, streams, (size_t)B * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-  w->h_n2.resize(B);
-  for (int i = 0; i < B; ++i) w->h_n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1];
+  w->h_n1.resize(B); w->h_n2.resize(B);
+  for (int i = 0; i < B; ++i) { w->h_n1[i] = offsets[(i + 1) * 2] - offsets[i * 2]; w->h_n2[i] = offsets[(i + 1) * 2 + 1] - offsets[i * 2 + 1]; }
   const alignnet::SampleSource src = {{w->cloud[0], w->cloud[1]}, w->off, nullptr, nullptr, streams ? w->streams : nullptr};
-  return run(h, src, w->h_n2.data(), *std::max_element(w->h_n2.begin(), w->h_n2.end()), B, seed, options, outputs);
+  return run(h, src, w->h_n1.data(), w->h_n2.data(), *std::max_element(w->h_n2.begin(), w->h_n2.end()), B, seed, options, outputs);
 }

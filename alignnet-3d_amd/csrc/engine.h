@@ -37,9 +37,9 @@ struct Stack { int first, n; };   // range of layers
 // Kernels whose launches are bracketed with HIP events on the handle's stream while profiling is enabled
 // (alignnet_profile_enable; read back by name through alignnet_profile_read_kernel -- bench.py's roofline legs).
 enum ProfKernel { PK_BACKBONE = 0, PK_KNN, PK_TRAIN_PHASE2, PK_TRAIN_PHASE3, PK_TRAIN_GRAM, PK_TRAIN_B2, PK_TRAIN_B1, PK_DG_FWD, PK_DG_BWD_EDGE,
-                  PK_ALLREDUCE, PK_OPTIMIZER, PK_SCENE_WINDOW, PK_SCENE_CAST, PK_SCENE_COMPACT, PK_ICP_GRID_BUILD, PK_ICP_GRID, PK_SCENE_BIN, PK_ICP_PLANE_NORMALS, PK_ICP_PLANE, PK_SCENE_BAND, PK_TRACKLET_TEST, PK_TRACKLET_COMPACT, PK_COUNT };
+                  PK_ALLREDUCE, PK_OPTIMIZER, PK_SCENE_WINDOW, PK_SCENE_CAST, PK_SCENE_COMPACT, PK_ICP_GRID_BUILD, PK_ICP_GRID, PK_SCENE_BIN, PK_ICP_PLANE_NORMALS, PK_ICP_PLANE, PK_SCENE_BAND, PK_TRACKLET_TEST, PK_TRACKLET_COMPACT, PK_ICP_GENERALIZED_NORMALS, PK_ICP_GENERALIZED, PK_COUNT };
 static const char* const kProfKernelNames[PK_COUNT] = {"backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2",
-                                                       "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact", "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band", "tracklet_test", "tracklet_compact"};
+                                                       "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact", "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band", "tracklet_test", "tracklet_compact", "icp_generalized_normals", "icp_generalized"};
 
 // KITTI tracklet extraction (alignnet_crop.hip); read back as the options "tracklet_chunk" / "tracklet_jobs_per_pass"
 constexpr int kTrackletChunk = 1024;        // points of a frame per workgroup
@@ -107,10 +107,11 @@ int alignnet_dataset_install(alignnet_handle* h, const float* points1, const flo
 // alignnet_dataset.hip: queue one draw (no jitter) of B pairs from `s` into out0 / out1 [B][N][3] and, with labels, into lab [12][cap]; lab_ptrs: the six tensors inside lab
 int alignnet_dataset_sample_launch(alignnet_handle* h, const alignnet::SampleSource& s, int B, int cap, uint64_t seed, float* out0, float* out1,
                                    float* lab, alignnet_labels* lab_ptrs);
-// alignnet_icp.hip: what alignnet_icp_register* / alignnet_icp_plane_register* (plane) queue for clouds that are staged already, from and into device
-// buffers.  n2: the B target sizes (host); stage_n2: what the scan's LDS stage is sized for (<= 0: its budget, as the _dataset entry points size it)
-int alignnet_icp_run_device(alignnet_handle* h, const float* const pts[2], const long long* off, const int* rows, const long long* n2, long long stage_n2,
-                            int B, const alignnet::IcpDeviceIo& io, double radius, double normal_radius, int its, bool full, bool plane);
+// alignnet_icp.hip: what alignnet_icp_register* (estimate 1) / alignnet_icp_plane_register* (2) / alignnet_icp_generalized_register* (4: the values of alignnet_register_options.refine) queue for clouds
+// that are staged already, from and into device buffers.  n1, n2: the B source and target sizes (host; n1 may be null unless estimate is 4); stage_n2: what the scan's LDS stage is sized
+// for (<= 0: its budget, as the _dataset entry points size it)
+int alignnet_icp_run_device(alignnet_handle* h, const float* const pts[2], const long long* off, const int* rows, const long long* n1, const long long* n2,
+                            long long stage_n2, int B, const alignnet::IcpDeviceIo& io, double radius, double normal_radius, int its, bool full, int estimate);
 // alignnet_train.hip: the loss of alignnet_eval_loss on the last eval forward from DEVICE labels, queued only: d_work[0] = loss, [1..16] = summaries
 size_t alignnet_eval_loss_work_floats(int B);
 int alignnet_eval_loss_launch(alignnet_handle* h, const alignnet_labels* d_labels, int B, float* d_work);
@@ -174,6 +175,8 @@ struct alignnet_handle {
   size_t icp_grid_ws_bytes = 0, icp_grid_ws_used = 0;   // allocated; carved by the last call ("icp_grid_ws_bytes")
   size_t icp_plane_ws_budget = 0;  // "icp_plane_ws_budget": workspace of one chunk of point-to-plane pairs; 0 = the grid search's 1 GiB
   int icp_plane_chunks = 0;        // "icp_plane_chunks" (read-only): chunks the last point-to-plane call ran
+  size_t icp_generalized_ws_budget = 0;  // "icp_generalized_ws_budget": the same for a chunk of generalized-ICP pairs
+  int icp_generalized_chunks = 0;        // "icp_generalized_chunks" (read-only): chunks the last generalized-ICP call ran
   int scene_cast = 0;              // alignnet_set_option("scene_cast"): 0 = scan, 1 = binned, 2 = binned for meshes beyond one LDS chunk of the scan (alignnet_scene.hip)
   int scene_rows = 0;              // alignnet_set_option("scene_rows"): 1 = both casts run their inner loop by elevation band (alignnet_scene.hip, stage 2c)
   int scene_binned_clouds = 0;     // clouds of the last alignnet_scene_generate that took the binned cast ("scene_binned_clouds"), and the

@@ -2,7 +2,7 @@
 """Register one pair of clouds with a trained model, in one engine call (Engine.register: sampler, network, decode, initial
 transform and optionally ICP on the full clouds, all on the device).
 
-    python register_pair.py --config F --model CKPT --source a.npy --target b.npy [--refine p2p|plane] [--its K] [--seed S]
+    python register_pair.py --config F --model CKPT --source a.npy --target b.npy [--refine p2p|plane|generalized] [--its K] [--seed S]
 
 CKPT is a `.aln3` checkpoint as train.py writes it.  Prints the 4x4 that maps the source onto the target, then fitness and rmse
 of the refinement (n/a without --refine)."""
@@ -18,7 +18,7 @@ if HERE not in sys.path:
 
 from config import load_config, configGlobal as cfg  # noqa: E402
 
-REFINE = {None: None, "p2p": "point", "plane": "plane"}
+REFINE = {None: None, "p2p": "point", "plane": "plane", "generalized": "generalized"}
 
 
 def parse_args(argv=None):
@@ -27,7 +27,7 @@ def parse_args(argv=None):
     p.add_argument("--model", required=True, help="Checkpoint (.aln3)")
     p.add_argument("--source", required=True, help="[n, >=3] .npy cloud to move")
     p.add_argument("--target", required=True, help="[m, >=3] .npy cloud to move it onto")
-    p.add_argument("--refine", choices=["p2p", "plane"], default=None, help="ICP refinement of the network's transform on the full clouds")
+    p.add_argument("--refine", choices=["p2p", "plane", "generalized"], default=None, help="ICP refinement of the network's transform on the full clouds")
     p.add_argument("--its", type=int, default=30, help="ICP iterations")
     p.add_argument("--seed", type=int, default=0, help="Seed of the sampler's draw")
     return p.parse_args(argv)

@@ -472,14 +472,16 @@ def held_tracks(val):
     return "trackid" in meta and "timestamps" in meta
 
 
-ICP_ESTIMATE = ("point", "plane")
+ICP_ESTIMATE = ("point", "plane", "generalized")
 
 
 def icp_estimate_option(config=None, environ=None):
-    """Optional, not a reference key: "evaluation": {"icp_estimate": "point" | "plane", "icp_normal_radius": 0.3} (or ALIGNNET_ICP_ESTIMATE, which
-    wins when set) selects the estimate of every ICP call -- point-to-point (default: every call as it was) or point-to-plane on target normals
-    taken within icp_normal_radius (Engine.icp_plane_refine_rows).  The reference's own spellings of point-to-plane (variant /
-    refine / --refineICPmethod p2plane) stay rejected: its function is `assert False`.  Returns (name, normal radius)."""
+    """Optional, not a reference key: "evaluation": {"icp_estimate": "point" | "plane" | "generalized", "icp_normal_radius": 0.3} (or
+    ALIGNNET_ICP_ESTIMATE, which wins when set) selects the estimate of every ICP call -- point-to-point (default: every call as it was),
+    point-to-plane on target normals taken within icp_normal_radius (Engine.icp_plane_refine_rows) or generalized ICP on both
+    clouds' normals within the same radius (Engine.icp_generalized_refine_rows; not "gicp": the reference's o3_gicp is the RANSAC
+    baseline).  The reference's own spellings of point-to-plane (variant / refine / --refineICPmethod p2plane) stay rejected: its function is
+    `assert False`.  Returns (name, normal radius)."""
     config = cfg if config is None else config
     environ = os.environ if environ is None else environ
     ev = getattr(config, "evaluation", None)
@@ -493,10 +495,13 @@ def icp_estimate_option(config=None, environ=None):
 
 
 def icp_rows(engine, rows, inits, radius, its, constrained=True):
-    """The ICP call of the --refineICP refinement and of the ICP mode: point-to-point, or point-to-plane when icp_estimate_option() says so."""
+    """The ICP call of the --refineICP refinement and of the ICP mode: point-to-point, or point-to-plane / generalized when icp_estimate_option()
+    says so."""
     name, normal_radius = icp_estimate_option()
     if name == "plane":
         return engine.icp_plane_refine_rows(rows, inits, radius=radius, normal_radius=normal_radius, its=its, constrained=constrained)
+    if name == "generalized":
+        return engine.icp_generalized_refine_rows(rows, inits, radius=radius, normal_radius=normal_radius, its=its, constrained=constrained)
     return engine.icp_refine_rows(rows, inits, radius=radius, its=its, constrained=constrained)
 
 
@@ -504,6 +509,8 @@ def log_icp_estimate():
     name, normal_radius = icp_estimate_option()
     if name == "plane":
         logger.info("ICP estimate: point-to-plane (target normals within %g m)" % normal_radius)
+    if name == "generalized":
+        logger.info("ICP estimate: generalized (normals of both clouds within %g m)" % normal_radius)
 
 
 def icp_plan(icp):

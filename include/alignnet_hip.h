@@ -419,6 +419,31 @@ int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1, int64_t n
                              int32_t* neighbours, int32_t* index, double* dist2, int32_t* inlier, double* residual,
                              double* sums, double* update, double* fitness, double* rmse);
 
+/* ---- generalized (plane-to-plane) ICP (Segal, Haehnel, Thrun 2009; semantics: tests/icp_generalized_ref.py) -------------
+ * Arguments, results, flags and errors of alignnet_icp_plane_register*.  Per pair, once: normals of the target AND of the
+ * source, each cloud on its own by the rule above (the source's in its own frame).  A point with unit normal n has the
+ * covariance C = I - (1 - 1e-3) n n^T; the loop of alignnet_icp_register with the estimate that minimises
+ * sum d^T (C_q + R C_p R^T)^-1 d, d = U p - q, R = the rotation of the current transform, linearised about the pair's first
+ * target point and solved as point-to-plane's system is (same scaling, same pivot floor, same update).  Motion along a
+ * surface is penalised weakly instead of left free: a single plane gives a regular system.  Always the grid search.
+ * Workspace per pair: point-to-plane's, a third grid over the source, its ordered records, normals and counts, one int
+ * per source point. */
+int alignnet_icp_generalized_register(alignnet_handle* h, const float* points1, const float* points2,
+                                      const int64_t* offsets, int32_t B, const double* init, double radius,
+                                      double normal_radius, int32_t its, int32_t flags, double* out, double* fitness,
+                                      double* rmse, int32_t* iterations);
+int alignnet_icp_generalized_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init,
+                                              double radius, double normal_radius, int32_t its, int32_t flags,
+                                              double* out, double* fitness, double* rmse, int32_t* iterations);
+/* Test hook, as alignnet_debug_icp_plane: normals [n][3] and neighbour counts [n] of the target and of the source, ONE
+ * evaluation at T [16] -- index / dist2 / inlier [n1] -- the reduced sums [29] (count, sum of dist2, the upper triangle
+ * of J^T M J row by row, J^T M d; the 16 of the z-constrained estimate first, zeros behind) and the update [16]. */
+int alignnet_debug_icp_generalized(alignnet_handle* h, const float* points1, int64_t n1, const float* points2, int64_t n2,
+                                   const double* T, double radius, double normal_radius, int32_t flags,
+                                   double* target_normals, int32_t* target_neighbours, double* source_normals,
+                                   int32_t* source_neighbours, int32_t* index, double* dist2, int32_t* inlier,
+                                   double* sums, double* update, double* fitness, double* rmse);
+
 /* ---- one-call registration: two raw clouds per pair in, a 4x4 transform per pair out ------------
  * The chain the evaluation loop joins in host Python (train.py:447-481), queued as one piece on the device: the
  * sampler (alignnet_dataset_sample's draw, no jitter), the eval forward, the decode of the three yaws in fp64
@@ -426,7 +451,8 @@ int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1, int64_t n
  * residual logit of that class, minus 2 pi when > pi; the residual is not de-normalised), pred_angle = (a2 - a1) + a_rem,
  * T_net = get_mat_angle(pred_translation, pred_angle, rotation_center = pred_s2_pc1center) (evaluation.py:46-57:
  * rotation about z around the centre, then the translation; float32 inputs widened, everything else float64), and with
- * `refine` the ICP of alignnet_icp_register (1) or alignnet_icp_plane_register (2) on the FULL clouds from T_net:
+ * `refine` the ICP of alignnet_icp_register (1), alignnet_icp_plane_register (2) or alignnet_icp_generalized_register (4;
+ * 3 is not assigned and stays an error) on the FULL clouds from T_net:
  * the handle's "icp_search" option, that entry point's stop rule and results, bit for bit what it returns for
  * init = T_net.  Nothing returns to the host between the stages: one synchronisation, at the end, with the downloads;
  * the buffers live in a workspace on the handle that grows with B (and, for host clouds, with their size) and is
@@ -437,8 +463,8 @@ int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1, int64_t n
  *     drawn as the dataset form would draw it were the pair installed as example streams[b] (NULL: b, the pair index).
  *   An empty cloud samples to N points at the origin (provider.py:97-98); ICP leaves such a pair at T_net.
  *   options: refine 0 = none (its must be 0; fitness / rmse / iterations must be NULL), 1 = point-to-point, 2 =
- *     point-to-plane; its >= 0; flags = ALIGNNET_ICP_FULL_ROTATION or 0; radius > 0 when refining; normal_radius > 0
- *     for refine 2.
+ *     point-to-plane, 4 = generalized; its >= 0; flags = ALIGNNET_ICP_FULL_ROTATION or 0; radius > 0 when refining;
+ *     normal_radius > 0 for refine 2 and 4.
  *   outputs: every pointer may be NULL except transforms.  transforms / network_transforms [B][16] row-major float64
  *     (transforms = the refined estimate, or T_net without refinement); angles [B][4] = a1, a2, a_rem, pred_angle;
  *     net = host arrays for the eight raw forward outputs (each may be NULL); loss [17] = loss + the 16 summaries of
@@ -447,11 +473,11 @@ int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1, int64_t n
  * Errors (null arguments, B < 1, offsets that decrease or start below 0, a row out of range, no dataset, bad option
  * values) are found before anything is queued: the engine's state is what it was. */
 typedef struct {
-  int32_t refine;        /* 0 none, 1 point-to-point, 2 point-to-plane */
+  int32_t refine;        /* 0 none, 1 point-to-point, 2 point-to-plane, 4 generalized */
   int32_t its;           /* ICP iterations, >= 0; with refine 0 must be 0 */
   int32_t flags;         /* ALIGNNET_ICP_FULL_ROTATION or 0; anything else is an error */
   double  radius;        /* > 0 when refine != 0 */
-  double  normal_radius; /* refine 2 only */
+  double  normal_radius; /* refine 2 and 4 only */
 } alignnet_register_options;
 
 typedef struct {         /* every pointer may be NULL except transforms */
@@ -788,6 +814,8 @@ int alignnet_tracklet_extract_frustum(alignnet_handle* h, const int32_t* frames,
  *   ordered records, normals and counts per pair; a pair that needs more forms a chunk alone).  Results do not depend on it: a smaller value
  *   only cuts a call into more chunks (a test hook for the chunking, and a way to bound the allocation).
  *   "icp_plane_chunks" (read-only): the chunks the last point-to-plane call ran.
+ * "icp_generalized_ws_budget" / "icp_generalized_chunks" (read-only): the same two for alignnet_icp_generalized_register* (its pairs also hold the
+ *   source's grid, ordered records, normals, counts and correspondences).
  * "tracklet_chunk" (read-only): the points of a frame one workgroup of alignnet_tracklet_extract takes (1024);
  *   "tracklet_jobs_per_pass" (read-only): the crop jobs of a frame it stages in LDS per pass (32).  Tests size their edge cases from them.
  * "ab_*" (0/1, default 0): A/B dispatch overrides -- each selects an earlier kernel variant of the SAME arithmetic for same-box comparisons
@@ -841,7 +869,8 @@ int alignnet_profile_read(alignnet_handle* h, double* backbone_ms, int64_t* back
  * "allreduce" (what the compute stream waits for), "optimizer", and the stages of alignnet_scene_generate: "scene_window" (azimuth windows),
  * "scene_cast" ("scene_band" instead when "scene_rows" is 1), "scene_compact" (counts, scan, scatter + noise), and of the ICP grid search: "icp_grid_build", "icp_grid" (the iterations), and of
  * point-to-plane ICP: "icp_plane_normals" (the ordering of the second grid's buckets + the normals), "icp_plane" (the iterations; its two grid builds
- * count under "icp_grid_build"), and of alignnet_tracklet_extract and alignnet_tracklet_extract_frustum: "tracklet_test" (membership + counts), "tracklet_compact" (scan + scatter). */
+ * count under "icp_grid_build"), of generalized ICP: "icp_generalized_normals" (both clouds' orderings + normals), "icp_generalized" (the iterations; its
+ * three grid builds count under "icp_grid_build"), and of alignnet_tracklet_extract and alignnet_tracklet_extract_frustum: "tracklet_test" (membership + counts), "tracklet_compact" (scan + scatter). */
 int alignnet_profile_read_kernel(alignnet_handle* h, const char* name, double* ms, int64_t* launches);
 
 #ifdef __cplusplus
