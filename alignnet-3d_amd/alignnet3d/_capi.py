@@ -187,7 +187,15 @@ SYMBOLS = {
                                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "alignnet_debug_goicp_nodes": (C.c_int, [H, FP, C.c_int64, FP, C.c_int64, C.POINTER(GoicpParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-    "alignnet_scene_set_sensor": (C.c_int, [H, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "alignnet_pose_graph_optimize": (C.c_int, [H, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                               C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "alignnet_debug_pose_graph_system": (C.c_int, [H, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_double, C.c_int32,
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "alignnet_scene_set_sensor":(C.c_int, [H, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "alignnet_scene_upload_meshes": (C.c_int, [H, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32]),
     "alignnet_scene_free_meshes": (C.c_int, [H]),
     "alignnet_scene_generate": (C.c_int, [H, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32, C.c_uint64,
@@ -217,7 +225,7 @@ SYMBOLS = {
 # symbols added after ABI version 1 was fixed: an earlier build named by ALIGNNET_HIP_LIB loads without them
 LATE_SYMBOLS = ("alignnet_register", "alignnet_register_dataset", "alignnet_tracklet_extract_frustum", "alignnet_goicp_register",
                 "alignnet_goicp_register_dataset", "alignnet_evaluate_registration", "alignnet_evaluate_registration_dataset",
-                "alignnet_icp_generalized_register", "alignnet_icp_generalized_register_dataset")
+                "alignnet_icp_generalized_register", "alignnet_icp_generalized_register_dataset", "alignnet_pose_graph_optimize")
 
 _lib = None
 

@@ -877,6 +877,99 @@ class Engine:
         self._check(self._lib.alignnet_debug_goicp_nodes(self._h, _fp(p1), len(p1), _fp(p2), len(p2), C.byref(p), ip(d), ip(c), len(c), dp(ub), dp(lb)))
         return ub, lb
 
+    # ---- multiway registration: pose-graph optimisation (csrc/alignnet_posegraph.hip; semantics: tests/pose_graph_ref.py) ----
+    POSE_GRAPH_STATUS = ("CONVERGED", "ITERATIONS", "STALLED", "EMPTY")
+    POSE_GRAPH_PRUNE = 0.25   # Open3D's edge_prune_threshold
+
+    @staticmethod
+    def _pose_graph_arrays(graphs):
+        """The concatenated arrays of a list of graphs; each graph is a dict(poses [n, 4, 4], i [m], j [m], T [m, 4, 4], info [m, 6, 6], c [m, 3],
+        uncertain [m]).  Checks shapes, indices and finiteness: nothing wrong reaches the library."""
+        node_off, edge_off = np.zeros(len(graphs) + 1, np.int64), np.zeros(len(graphs) + 1, np.int64)
+        poses, edges, T, info, c, unc = [], [], [], [], [], []
+        for k, g in enumerate(graphs):
+            X = np.asarray(g["poses"], np.float64)
+            if X.ndim != 3 or X.shape[1:] != (4, 4) or len(X) < 1:
+                raise ValueError("pose graph %d: poses must be [n >= 1, 4, 4]" % k)
+            n, m = len(X), len(g["i"])
+            e = np.stack([np.asarray(g["i"], np.int64).reshape(m), np.asarray(g["j"], np.int64).reshape(m)], 1)
+            if m and (e.min() < 0 or e.max() >= n):
+                raise ValueError("pose graph %d: edge index out of range" % k)
+            if m and (e[:, 0] == e[:, 1]).any():
+                raise ValueError("pose graph %d: an edge joins a node to itself (i == j)" % k)
+            parts = (X, np.asarray(g["T"], np.float64).reshape(m, 4, 4), np.asarray(g["info"], np.float64).reshape(m, 6, 6),
+                     np.asarray(g["c"], np.float64).reshape(m, 3))
+            if not all(np.isfinite(p).all() for p in parts):
+                raise ValueError("pose graph %d: a non-finite entry" % k)
+            node_off[k + 1], edge_off[k + 1] = node_off[k] + n, edge_off[k] + m
+            poses.append(X); edges.append(e.astype(np.int32)); T.append(parts[1]); info.append(parts[2]); c.append(parts[3])
+            unc.append(np.asarray(g["uncertain"]).reshape(m).astype(bool).astype(np.int32))
+        cat = lambda L, shape, dt: np.ascontiguousarray(np.concatenate(L, 0), dt) if L else np.zeros(shape, dt)
+        return (node_off, edge_off, cat(poses, (0, 4, 4), np.float64), cat(edges, (0, 2), np.int32), cat(T, (0, 4, 4), np.float64),
+                cat(info, (0, 6, 6), np.float64), cat(c, (0, 3), np.float64), cat(unc, (0,), np.int32))
+
+    @staticmethod
+    def _pose_graph_mu(graphs, info, edge_off, mu, preference, threshold):
+        """mu per graph: the given value(s), or Open3D's rule preference * threshold^2 * the mean inlier count (info[5, 5]) of the graph's edges."""
+        G = len(graphs)
+        if mu is None:
+            out = np.ones(G)
+            for k in range(G):
+                count = info[edge_off[k]: edge_off[k + 1], 5, 5].mean() if edge_off[k + 1] > edge_off[k] else 0.0
+                if count > 0:     # (no edge, or no inlier on any edge: every information matrix is zero, nothing is optimised and mu is not read)
+                    out[k] = float(preference) * float(threshold) ** 2 * count
+        else:
+            out = np.broadcast_to(np.asarray(mu, np.float64), (G,)).copy()
+        if not (np.isfinite(out).all() and (out > 0).all()):
+            raise ValueError("pose graph: mu must be > 0 and finite (mu <= 0: no line process is defined), got %r" % (out.tolist(),))
+        return np.ascontiguousarray(out, np.float64)
+
+    def pose_graph_optimize(self, graphs, constrained=True, mu=None, preference=1.0, threshold=0.02, max_solves=100):
+        """Multiway registration (Open3D's global_optimization with its line process): per graph, one pose per node from the pairwise registration
+        results on its edges, Levenberg-Marquardt to the end on the device, one workgroup per graph, one call for all graphs.
+        graphs: a list of dict(poses [n, 4, 4] initial, i, j [m] node numbers, T [m, 4, 4] cloud i into frame j, info [m, 6, 6] the information matrix of
+        evaluate_registration about c [m, 3] (in frame j), uncertain [m] bool: loop closures under the line process).  Node 0 is never moved; nodes that
+        no chain of edges joins to node 0 keep their pose.  constrained: yaw + translation per node (every transform rotates about z only).
+        mu: the line process's scale (a number or one per graph); None = preference * threshold^2 * the mean inlier count info[5, 5] of the graph's edges.
+        Returns a list of dict(poses, before, after (the objective), solves, status (a POSE_GRAPH_STATUS name), chi2 [m], weights [m],
+        pruned [m] = uncertain & (weights < 0.25))."""
+        fn = self._register_fn("alignnet_pose_graph_optimize")
+        graphs = list(graphs)
+        if not graphs:
+            return []
+        if int(max_solves) < 1:
+            raise ValueError("pose_graph_optimize: max_solves must be >= 1")
+        node_off, edge_off, poses, edges, T, info, c, unc = self._pose_graph_arrays(graphs)
+        mus = self._pose_graph_mu(graphs, info, edge_off, mu, preference, threshold)
+        G, nodes, E = len(graphs), int(node_off[-1]), int(edge_off[-1])
+        out, before, after = np.empty((nodes, 4, 4), np.float64), np.empty(G, np.float64), np.empty(G, np.float64)
+        solves, status, chi2, w = np.empty(G, np.int32), np.empty(G, np.int32), np.empty(E, np.float64), np.empty(E, np.float64)
+        dp, ip, lp = (lambda a: a.ctypes.data_as(C.POINTER(C.c_double))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int64)))
+        self._check(fn(self._h, G, lp(node_off), lp(edge_off), dp(poses), ip(edges), dp(T), dp(info), dp(c), ip(unc), dp(mus), 0 if constrained else 1,
+                       int(max_solves), dp(out), dp(before), dp(after), ip(solves), ip(status), dp(chi2), dp(w)))
+        res = []
+        for k in range(G):
+            ns, es = slice(node_off[k], node_off[k + 1]), slice(edge_off[k], edge_off[k + 1])
+            res.append(dict(poses=out[ns].copy(), before=float(before[k]), after=float(after[k]), solves=int(solves[k]),
+                            status=self.POSE_GRAPH_STATUS[status[k]], chi2=chi2[es].copy(), weights=w[es].copy(), mu=float(mus[k]),
+                            pruned=(unc[es] != 0) & (w[es] < self.POSE_GRAPH_PRUNE)))
+        return res
+
+    def debug_pose_graph_system(self, graph, constrained=True, mu=None, preference=1.0, threshold=0.02):
+        """Test hook: the kernel's own linearisation of ONE graph at its poses, no step taken: dict(r [m, d], chi2 [m], weights [m], F, H [N, N] dense,
+        b [N]), d = 4 (constrained) or 6, N = d (n - 1)."""
+        fn = self._register_fn("alignnet_debug_pose_graph_system")
+        node_off, edge_off, poses, edges, T, info, c, unc = self._pose_graph_arrays([graph])
+        mus = self._pose_graph_mu([graph], info, edge_off, mu, preference, threshold)
+        n, m, d = int(node_off[1]), int(edge_off[1]), 4 if constrained else 6
+        N = d * (n - 1)
+        r, chi2, w, F = np.zeros((m, d)), np.zeros(m), np.zeros(m), C.c_double(0.0)
+        H, b = np.zeros((N, N)), np.zeros(N)
+        dp, ip = (lambda a: a.ctypes.data_as(C.POINTER(C.c_double))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._check(fn(self._h, n, m, dp(poses), ip(edges), dp(T), dp(info), dp(c), ip(unc), float(mus[0]), 0 if constrained else 1, dp(r), dp(chi2), dp(w),
+                       C.byref(F), dp(H), dp(b)))
+        return dict(r=r, chi2=chi2, weights=w, F=float(F.value), H=H, b=b)
+
     # ---- spinning-LiDAR scene generator (csrc/alignnet_scene.hip; alignnet3d/scenes.py builds the arguments) ----
     def scene_upload_meshes(self, meshes, sensor=None):
         """meshes: list of (vertices [nv, 3] float64 normalised as scenes.normalise_mesh does, faces [nf, 3] int, centroid [3]); sensor: (dir_x [4500],
@@ -1264,7 +1357,7 @@ class Engine:
     PROFILED_KERNELS = ("backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1",
                         "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact",
                         "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band",
-                        "tracklet_test", "tracklet_compact", "icp_generalized_normals", "icp_generalized")
+                        "tracklet_test", "tracklet_compact", "icp_generalized_normals", "icp_generalized", "pose_graph")
 
     def profile_kernels(self):
         """{kernel: (ms, launches)} accumulated since the last profile_read(reset=True); call BEFORE that reset."""

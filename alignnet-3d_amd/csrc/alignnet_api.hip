@@ -186,6 +186,7 @@ extern "C" void alignnet_scene_free(alignnet_handle* h);
 extern "C" void alignnet_tracklet_free(alignnet_handle* h);
 extern "C" void alignnet_icp_free(alignnet_handle* h);
 extern "C" void alignnet_goicp_free(alignnet_handle* h);
+extern "C" void alignnet_posegraph_free(alignnet_handle* h);
 
 namespace { void pipe_free(alignnet_handle* h); hipStream_t pipe_stream(alignnet_handle* h, int which); }   // pipelined host path, defined with alignnet_forward_submit below
 
@@ -202,6 +203,7 @@ extern "C" void alignnet_destroy(alignnet_handle* h)
   alignnet_tracklet_free(h);
   alignnet_icp_free(h);
   alignnet_goicp_free(h);
+  alignnet_posegraph_free(h);
   alignnet_register_free(h);
   pipe_free(h);
   free_ws(h);
@@ -1025,6 +1027,8 @@ extern "C" int alignnet_set_option(alignnet_handle* h, const char* key, int64_t 
   if (k == "icp_search") { if (value < 0 || value > 2) return fail(h, "icp_search must be 0 (scan), 1 (grid) or 2 (automatic)"); h->icp_search = (int)value; return 0; }
   if (k == "icp_plane_ws_budget") { if (value < 0) return fail(h, "icp_plane_ws_budget must be >= 0 (0 = 1 GiB)"); h->icp_plane_ws_budget = (size_t)value; return 0; }
   if (k == "icp_generalized_ws_budget") { if (value < 0) return fail(h, "icp_generalized_ws_budget must be >= 0 (0 = 1 GiB)"); h->icp_generalized_ws_budget = (size_t)value; return 0; }
+  if (k == "pose_graph_ws_budget") { if (value < 0) return fail(h, "pose_graph_ws_budget must be >= 0 (0 = 1 GiB)"); h->pose_graph_ws_budget = (size_t)value; return 0; }
+  if (k == "pose_graph_lds_budget") { if (value < -1 || value > 20000) return fail(h, "pose_graph_lds_budget must be -1 (default) or 0 .. 20000 doubles"); h->pose_graph_lds_budget = (int)value; return 0; }
   if (k == "scene_cast") { if (value < 0 || value > 2) return fail(h, "scene_cast must be 0 (scan), 1 (binned) or 2 (automatic)"); h->scene_cast = (int)value; return 0; }
   if (k == "scene_rows") { if (value != 0 && value != 1) return fail(h, "scene_rows must be 0 (whole tiles) or 1 (by elevation band)"); h->scene_rows = (int)value; return 0; }
   for (const auto& ak : kAbKeys)
@@ -1076,6 +1080,10 @@ extern "C" int alignnet_get_option(alignnet_handle* h, const char* key, int64_t*
   if (k == "icp_plane_chunks") { *value = h->icp_plane_chunks; return 0; }
   if (k == "icp_generalized_ws_budget") { *value = (int64_t)h->icp_generalized_ws_budget; return 0; }
   if (k == "icp_generalized_chunks") { *value = h->icp_generalized_chunks; return 0; }
+  if (k == "pose_graph_ws_budget") { *value = (int64_t)h->pose_graph_ws_budget; return 0; }
+  if (k == "pose_graph_chunks") { *value = h->pose_graph_chunks; return 0; }
+  if (k == "pose_graph_lds_budget") { *value = h->pose_graph_lds_budget; return 0; }
+  if (k == "pose_graph_lds_graphs") { *value = h->pose_graph_lds_graphs; return 0; }
   if (k == "icp_grid_ws_bytes") { *value = (int64_t)h->icp_grid_ws_used; return 0; }
   if (k == "scene_cast") { *value = h->scene_cast; return 0; }
   if (k == "scene_rows") { *value = h->scene_rows; return 0; }

@@ -37,9 +37,9 @@ struct Stack { int first, n; };   // range of layers
 // Kernels whose launches are bracketed with HIP events on the handle's stream while profiling is enabled
 // (alignnet_profile_enable; read back by name through alignnet_profile_read_kernel -- bench.py's roofline legs).
 enum ProfKernel { PK_BACKBONE = 0, PK_KNN, PK_TRAIN_PHASE2, PK_TRAIN_PHASE3, PK_TRAIN_GRAM, PK_TRAIN_B2, PK_TRAIN_B1, PK_DG_FWD, PK_DG_BWD_EDGE,
-                  PK_ALLREDUCE, PK_OPTIMIZER, PK_SCENE_WINDOW, PK_SCENE_CAST, PK_SCENE_COMPACT, PK_ICP_GRID_BUILD, PK_ICP_GRID, PK_SCENE_BIN, PK_ICP_PLANE_NORMALS, PK_ICP_PLANE, PK_SCENE_BAND, PK_TRACKLET_TEST, PK_TRACKLET_COMPACT, PK_ICP_GENERALIZED_NORMALS, PK_ICP_GENERALIZED, PK_COUNT };
+                  PK_ALLREDUCE, PK_OPTIMIZER, PK_SCENE_WINDOW, PK_SCENE_CAST, PK_SCENE_COMPACT, PK_ICP_GRID_BUILD, PK_ICP_GRID, PK_SCENE_BIN, PK_ICP_PLANE_NORMALS, PK_ICP_PLANE, PK_SCENE_BAND, PK_TRACKLET_TEST, PK_TRACKLET_COMPACT, PK_ICP_GENERALIZED_NORMALS, PK_ICP_GENERALIZED, PK_POSE_GRAPH, PK_COUNT };
 static const char* const kProfKernelNames[PK_COUNT] = {"backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2",
-                                                       "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact", "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band", "tracklet_test", "tracklet_compact", "icp_generalized_normals", "icp_generalized"};
+                                                       "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact", "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band", "tracklet_test", "tracklet_compact", "icp_generalized_normals", "icp_generalized", "pose_graph"};
 
 // KITTI tracklet extraction (alignnet_crop.hip); read back as the options "tracklet_chunk" / "tracklet_jobs_per_pass"
 constexpr int kTrackletChunk = 1024;        // points of a frame per workgroup
@@ -177,6 +177,12 @@ struct alignnet_handle {
   int icp_plane_chunks = 0;        // "icp_plane_chunks" (read-only): chunks the last point-to-plane call ran
   size_t icp_generalized_ws_budget = 0;  // "icp_generalized_ws_budget": the same for a chunk of generalized-ICP pairs
   int icp_generalized_chunks = 0;        // "icp_generalized_chunks" (read-only): chunks the last generalized-ICP call ran
+  void* pose_graph_ws = nullptr;   // inputs, results and per-graph working arrays of the pose-graph optimisation (alignnet_posegraph.hip), grown on demand
+  size_t pose_graph_ws_bytes = 0;
+  size_t pose_graph_ws_budget = 0; // "pose_graph_ws_budget": per-graph working arrays of one chunk of graphs; 0 = 1 GiB
+  int pose_graph_chunks = 0;       // "pose_graph_chunks" (read-only): chunks (= launches) of the last pose-graph call
+  int pose_graph_lds_budget = -1;  // "pose_graph_lds_budget": doubles of one band a graph may keep in LDS; -1 = the default (alignnet_posegraph.hip: kPgLdsBand), 0 = every band in the workspace
+  int pose_graph_lds_graphs = 0;   // "pose_graph_lds_graphs" (read-only): graphs of the last call whose band lay in LDS
   int scene_cast = 0;              // alignnet_set_option("scene_cast"): 0 = scan, 1 = binned, 2 = binned for meshes beyond one LDS chunk of the scan (alignnet_scene.hip)
   int scene_rows = 0;              // alignnet_set_option("scene_rows"): 1 = both casts run their inner loop by elevation band (alignnet_scene.hip, stage 2c)
   int scene_binned_clouds = 0;     // clouds of the last alignnet_scene_generate that took the binned cast ("scene_binned_clouds"), and the

@@ -625,6 +625,39 @@ int alignnet_debug_goicp_nodes(alignnet_handle* h, const float* points1, int64_t
                                const alignnet_goicp_params* params, const int32_t* depth, const int32_t* coords, int32_t K,
                                double* ub, double* lb);
 
+/* ---- multiway registration: pose-graph optimisation of G graphs in one call (csrc/alignnet_posegraph.hip; semantics:
+ * tests/pose_graph_ref.py) ----------------------------------------------------------------------------
+ * Graphs are concatenated: node_offsets / edge_offsets [G + 1] (from 0, non-decreasing; a graph has >= 1 nodes), poses
+ * [nodes][16] row-major 4x4 float64 (node frame -> the graph's frame; node 0 of a graph is never moved), edges [edges][2] =
+ * (i, j), node numbers inside the edge's graph, i != j; transforms [edges][16] (cloud i into frame j), informations
+ * [edges][36] (evaluate_registration's 6x6 about the centre, only the upper triangle is read), centres [edges][3] (frame
+ * j), uncertain [edges] (0: an odometry edge; otherwise a loop closure under the line process), mu [G] > 0.
+ * flags: ALIGNNET_ICP_FULL_ROTATION = six unknowns per node, otherwise yaw + translation (four).
+ * One workgroup per graph runs Levenberg-Marquardt to the end on the device: at most max_solves >= 1 linear solves.
+ * Nodes that no chain of edges joins to node 0 are held at their given pose, to the bit.
+ * out_poses [nodes][16]; out_before / out_after [G] the objective at the given and the final poses; out_solves [G];
+ * out_status [G] (ALIGNNET_POSE_GRAPH_*; EMPTY: one node, no edge or nothing to move: the given poses); out_chi2 /
+ * out_weights [edges] at the final poses (weight 1 for certain edges).  Every out pointer but out_poses may be NULL.
+ * Every index and every entry is checked before anything reaches the device.  A graph's result depends on the graph and
+ * the arguments only: not on the other graphs of the call, not on the chunking ("pose_graph_ws_budget"), not on whether
+ * its band lies in LDS or in the workspace ("pose_graph_lds_budget").
+ * alignnet_debug_pose_graph_system (test hook, outside the stable surface): one graph, no step taken: r [m][d] (d = 4 or
+ * 6), chi2 [m], weights [m], F, the dense H [N][N] and b [N], N = d (n - 1), from the kernel's own linearisation.
+ * (Added without moving ALIGNNET_ABI_VERSION, as alignnet_register was.) */
+#define ALIGNNET_POSE_GRAPH_CONVERGED 0
+#define ALIGNNET_POSE_GRAPH_ITERATIONS 1
+#define ALIGNNET_POSE_GRAPH_STALLED 2
+#define ALIGNNET_POSE_GRAPH_EMPTY 3
+int alignnet_pose_graph_optimize(alignnet_handle* h, int32_t G, const int64_t* node_offsets, const int64_t* edge_offsets,
+                                 const double* poses, const int32_t* edges, const double* transforms,
+                                 const double* informations, const double* centres, const int32_t* uncertain, const double* mu,
+                                 int32_t flags, int32_t max_solves, double* out_poses, double* out_before, double* out_after,
+                                 int32_t* out_solves, int32_t* out_status, double* out_chi2, double* out_weights);
+int alignnet_debug_pose_graph_system(alignnet_handle* h, int32_t n, int32_t m, const double* poses, const int32_t* edges,
+                                     const double* transforms, const double* informations, const double* centres,
+                                     const int32_t* uncertain, double mu, int32_t flags, double* r, double* chi2,
+                                     double* weights, double* F, double* H, double* b);
+
 /* ---- spinning-LiDAR scene generator (the SynthCars-style datasets, tp_utils/pointcloud.py:945-971,1055-1186) -------
  * A 64 x 4500-ray sensor at the origin (ray index = row * 4500 + column, direction 120 (sin h, cos h, tan v), vfov 26.9
  * degrees, 360 degrees around) is cast against a triangle mesh at two poses per scene; the first hit of every ray is kept
@@ -816,6 +849,11 @@ int alignnet_tracklet_extract_frustum(alignnet_handle* h, const int32_t* frames,
  *   "icp_plane_chunks" (read-only): the chunks the last point-to-plane call ran.
  * "icp_generalized_ws_budget" / "icp_generalized_chunks" (read-only): the same two for alignnet_icp_generalized_register* (its pairs also hold the
  *   source's grid, ordered records, normals, counts and correspondences).
+ * "pose_graph_ws_budget" (bytes, default 0 = 1 GiB) / "pose_graph_chunks" (read-only): the same two for alignnet_pose_graph_optimize (per graph:
+ *   trial poses, 25 doubles per edge, and both bands, b and x when they do not lie in LDS); one launch per chunk.
+ *   "pose_graph_lds_budget" (doubles, default -1 = 20000, at most 20000): a graph whose two bands, b and x (2 N (bw + 1) + 2 N doubles) fit
+ *   keeps them in LDS, any other in its slice of the workspace; 0 puts every graph's in the workspace.  Results do not depend on it.
+ *   "pose_graph_lds_graphs" (read-only): the graphs of the last call that took the LDS placement.
  * "tracklet_chunk" (read-only): the points of a frame one workgroup of alignnet_tracklet_extract takes (1024);
  *   "tracklet_jobs_per_pass" (read-only): the crop jobs of a frame it stages in LDS per pass (32).  Tests size their edge cases from them.
  * "ab_*" (0/1, default 0): A/B dispatch overrides -- each selects an earlier kernel variant of the SAME arithmetic for same-box comparisons
@@ -870,7 +908,8 @@ int alignnet_profile_read(alignnet_handle* h, double* backbone_ms, int64_t* back
  * "scene_cast" ("scene_band" instead when "scene_rows" is 1), "scene_compact" (counts, scan, scatter + noise), and of the ICP grid search: "icp_grid_build", "icp_grid" (the iterations), and of
  * point-to-plane ICP: "icp_plane_normals" (the ordering of the second grid's buckets + the normals), "icp_plane" (the iterations; its two grid builds
  * count under "icp_grid_build"), of generalized ICP: "icp_generalized_normals" (both clouds' orderings + normals), "icp_generalized" (the iterations; its
- * three grid builds count under "icp_grid_build"), and of alignnet_tracklet_extract and alignnet_tracklet_extract_frustum: "tracklet_test" (membership + counts), "tracklet_compact" (scan + scatter). */
+ * three grid builds count under "icp_grid_build"), and of alignnet_tracklet_extract and alignnet_tracklet_extract_frustum: "tracklet_test" (membership + counts), "tracklet_compact" (scan + scatter),
+ * and of alignnet_pose_graph_optimize: "pose_graph" (one launch per chunk of graphs). */
 int alignnet_profile_read_kernel(alignnet_handle* h, const char* name, double* ms, int64_t* launches);
 
 #ifdef __cplusplus
