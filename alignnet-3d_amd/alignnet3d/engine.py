@@ -126,6 +126,37 @@ def _fp(a):
     return a.ctypes.data_as(_capi.FP)
 
 
+def _dp(a):
+    """double* of a float64 array; None (an output the caller does not want) stays None"""
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _ip(a):
+    """int32_t* of an int32 array, None as _dp"""
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _lp(a):
+    """int64_t* of an int64 array, None as _dp"""
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _pack_pairs(sources, targets):
+    """Lists of [n, 3] clouds as the host entry points take them: (p1, p2, off) = the two float32 blobs and the [B + 1, 2] int64 table of the
+    pairs' row offsets into them."""
+    B = len(sources)
+    off = np.zeros((B + 1, 2), np.int64)
+    off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
+    cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
+    return cat(sources), cat(targets), off
+
+
+def _one_pair(source, target, T=None):
+    """The one pair of a debug_* hook: (p1, p2, Tm) = the two clouds as contiguous float32 [n, 3] and the 4x4 `T` as 16 float64 (None without T)."""
+    p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+    return p1, p2, None if T is None else np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+
+
 def centroid_inits(points1, points2, offsets, rows):
     """icp.py:62-66 get_centroid_init for the examples at `rows` of packed tables (points1 / points2 [n, >=3], offsets
     [n + 1, 2] as uploaded with Engine.upload_dataset): identity rotation, translation = mean(pc2) - mean(pc1), the means
@@ -354,54 +385,44 @@ class Engine:
     # ---- ICP refinement on the full clouds (icp.py:69-78 / train.py:463-484) ------
     centroid_inits = staticmethod(centroid_inits)
 
-    @staticmethod
-    def _icp_bufs(inits, B):
+    def _icp_call(self, fn, lead, inits, B, extra):
+        """One call of the ICP family, fn(handle, *lead, B, init, *extra, out, fitness, rmse, iterations): lead = the clouds (blobs and offsets, or
+        rows), extra = what stands between init and the outputs.  Returns dict(transforms, fitness, rmse, iterations)."""
         init = np.ascontiguousarray(inits, np.float64).reshape(B, 16)
         out = np.empty((B, 16), np.float64)
-        fit, rmse, its = np.empty(B, np.float64), np.empty(B, np.float64), np.empty(B, np.int32)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        return init, out, fit, rmse, its, dp
+        fit, rmse, it = np.empty(B, np.float64), np.empty(B, np.float64), np.empty(B, np.int32)
+        self._check(fn(self._h, *lead, B, _dp(init), *extra, _dp(out), _dp(fit), _dp(rmse), _ip(it)))
+        return dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+
+    def _icp_refine(self, refine, register, lead, inits, B, radius, its, constrained):
+        """Point-to-point ICP through `refine` (the z-constrained entry point, no flags argument) or `register` (with the full-rotation flag)."""
+        if constrained:
+            return self._icp_call(refine, lead, inits, B, (float(radius), int(its)))
+        return self._icp_call(register, lead, inits, B, (float(radius), int(its), ICP_FULL_ROTATION))
 
     def icp_refine(self, sources, targets, inits, radius=0.1, its=30, constrained=True):
         """sources / targets: lists of [n, 3] arrays; inits: [B, 4, 4].  Returns dict(transforms, fitness, rmse, iterations).
         constrained=True: rotation about z only (with_constraint=True, alignnet_icp_refine); False: full 3-D rotation
         (with_constraint=False, alignnet_icp_register with ALIGNNET_ICP_FULL_ROTATION)."""
-        B = len(sources)
-        off = np.zeros((B + 1, 2), np.int64)
-        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
-        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
-        p1, p2 = cat(sources), cat(targets)
-        init, out, fit, rmse, it, dp = self._icp_bufs(inits, B)
-        offp, itp = off.ctypes.data_as(C.POINTER(C.c_int64)), it.ctypes.data_as(C.POINTER(C.c_int32))
-        if constrained:
-            self._check(self._lib.alignnet_icp_refine(self._h, _fp(p1), _fp(p2), offp, B, dp(init), float(radius), int(its), dp(out), dp(fit), dp(rmse), itp))
-        else:
-            self._check(self._lib.alignnet_icp_register(self._h, _fp(p1), _fp(p2), offp, B, dp(init), float(radius), int(its), ICP_FULL_ROTATION,
-                                                        dp(out), dp(fit), dp(rmse), itp))
-        return dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+        p1, p2, off = _pack_pairs(sources, targets)
+        return self._icp_refine(self._lib.alignnet_icp_refine, self._lib.alignnet_icp_register, (_fp(p1), _fp(p2), _lp(off)), inits, len(sources), radius,
+                                its, constrained)
 
     def icp_refine_rows(self, rows, inits, radius=0.1, its=30, constrained=True):
         """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows."""
         r, rp = self._rows(rows)
-        init, out, fit, rmse, it, dp = self._icp_bufs(inits, r.size)
-        itp = it.ctypes.data_as(C.POINTER(C.c_int32))
-        if constrained:
-            self._check(self._lib.alignnet_icp_refine_dataset(self._h, rp, r.size, dp(init), float(radius), int(its), dp(out), dp(fit), dp(rmse), itp))
-        else:
-            self._check(self._lib.alignnet_icp_register_dataset(self._h, rp, r.size, dp(init), float(radius), int(its), ICP_FULL_ROTATION,
-                                                                dp(out), dp(fit), dp(rmse), itp))
-        return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+        return self._icp_refine(self._lib.alignnet_icp_refine_dataset, self._lib.alignnet_icp_register_dataset, (rp,), inits, r.size, radius, its,
+                                constrained)
 
     # ---- evaluation of given transforms without ground truth (alignnet_evaluate_registration*; definition: tests/reg_eval_ref.py) ----
     def _evaluate_registration(self, call, B, sizes, transforms, threshold, centers, want_information, want_correspondences):
         """call(tf, threshold, centers, fitness, rmse, information, correspondences) -> rc with the pointers bound; sizes: the B source sizes."""
         tf = np.ascontiguousarray(transforms, np.float64).reshape(B, 16)
-        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
         cen = None if centers is None else np.ascontiguousarray(centers, np.float64).reshape(B, 3)
         fit, rmse = np.empty(B, np.float64), np.empty(B, np.float64)
         info = np.empty((B, 6, 6), np.float64) if want_information else None
         corr = np.full(max(int(np.sum(sizes)), 1), -1, np.int32) if want_correspondences else None
-        self._check(call(dp(tf), float(threshold), dp(cen), dp(fit), dp(rmse), dp(info), None if corr is None else corr.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._check(call(_dp(tf), float(threshold), _dp(cen), _dp(fit), _dp(rmse), _dp(info), _ip(corr)))
         res = dict(fitness=fit, rmse=rmse)
         if want_information:
             res["information"] = info
@@ -418,11 +439,8 @@ class Engine:
         The search is the engine's icp_search option."""
         fn = self._register_fn("alignnet_evaluate_registration")
         B = len(sources)
-        off = np.zeros((B + 1, 2), np.int64)
-        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
-        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
-        p1, p2 = cat(sources), cat(targets)
-        offp = off.ctypes.data_as(C.POINTER(C.c_int64))
+        p1, p2, off = _pack_pairs(sources, targets)
+        offp = _lp(off)
         return self._evaluate_registration(lambda *a: fn(self._h, _fp(p1), _fp(p2), offp, B, *a), B, np.diff(off[:, 0]), transforms, threshold, centers,
                                            want_information, want_correspondences)
 
@@ -444,16 +462,13 @@ class Engine:
         lane of the point's quad did with its slice of the LDS-resident targets (0 none / 1 single / 2 walk; lane s holds targets s, s + 4, ...),
         tail_won [n1] bool: the winner came from the fp64 tail, lds_points as used, fitness, rmse).  lds_points > 0 overrides the LDS stage's
         size (<= 4266) so that small clouds reach the tail."""
-        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
-        Tm = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+        p1, p2, Tm = _one_pair(source, target, T)
         n = max(len(p1), 1)
         idx, d2, inl, paths = np.full(n, -1, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
         used, fit, rmse = np.zeros(1, np.int32), np.zeros(1, np.float64), np.zeros(1, np.float64)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        self._check(self._lib.alignnet_debug_icp_scan(self._h, _fp(p1), len(p1), _fp(p2), len(p2), dp(Tm), float(radius),
-                                                      0 if constrained else ICP_FULL_ROTATION, int(lds_points), ip(idx), dp(d2), ip(inl), ip(paths),
-                                                      ip(used), dp(fit), dp(rmse)))
+        self._check(self._lib.alignnet_debug_icp_scan(self._h, _fp(p1), len(p1), _fp(p2), len(p2), _dp(Tm), float(radius),
+                                                      0 if constrained else ICP_FULL_ROTATION, int(lds_points), _ip(idx), _dp(d2), _ip(inl), _ip(paths),
+                                                      _ip(used), _dp(fit), _dp(rmse)))
         n1 = len(p1)
         paths = paths[:n1]
         return dict(index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1, lanes=np.stack([(paths >> (2 * s)) & 3 for s in range(4)], -1),
@@ -464,73 +479,51 @@ class Engine:
         (set_option("icp_search", 1) selects it for icp_refine*; this read-back takes it whatever the option says).  Returns dict(index [n1]
         chosen target's original index, -1 without a candidate; dist2 [n1] fp64 squared distance, inf without; inlier [n1] bool; candidates
         [n1] records evaluated; cell_edge; buckets_occupied; largest_bucket; fitness; rmse)."""
-        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
-        Tm = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+        p1, p2, Tm = _one_pair(source, target, T)
         n = max(len(p1), 1)
         idx, d2, inl, cand = np.full(n, -1, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
         edge, occ, big, fit, rmse = np.zeros(1, np.float64), np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.float64), np.zeros(1, np.float64)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        self._check(self._lib.alignnet_debug_icp_grid(self._h, _fp(p1), len(p1), _fp(p2), len(p2), dp(Tm), float(radius),
-                                                      0 if constrained else ICP_FULL_ROTATION, ip(idx), dp(d2), ip(inl), ip(cand), dp(edge), ip(occ), ip(big),
-                                                      dp(fit), dp(rmse)))
+        self._check(self._lib.alignnet_debug_icp_grid(self._h, _fp(p1), len(p1), _fp(p2), len(p2), _dp(Tm), float(radius),
+                                                      0 if constrained else ICP_FULL_ROTATION, _ip(idx), _dp(d2), _ip(inl), _ip(cand), _dp(edge), _ip(occ),
+                                                      _ip(big), _dp(fit), _dp(rmse)))
         n1 = len(p1)
         return dict(index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1, candidates=cand[:n1].copy(), cell_edge=float(edge[0]),
                     buckets_occupied=int(occ[0]), largest_bucket=int(big[0]), fitness=float(fit[0]), rmse=float(rmse[0]))
 
     # ---- point-to-plane ICP (csrc/alignnet_icp.hip: icp_plane_*; semantics: tests/icp_plane_ref.py) ----
+    def _icp_surface(self, fn, lead, inits, B, radius, normal_radius, its, constrained):
+        """Point-to-plane or generalized ICP through the entry point `fn`: both take (radius, normal_radius, its, flags) behind init."""
+        return self._icp_call(fn, lead, inits, B, (float(radius), float(normal_radius), int(its), 0 if constrained else ICP_FULL_ROTATION))
+
     def icp_plane_refine(self, sources, targets, inits, radius=0.1, normal_radius=0.3, its=30, constrained=True):
         """Point-to-plane ICP: icp_refine's loop (nearest target within `radius`, same stop rule, same return dict) with the estimate that
         minimises the distances to the targets' tangent planes.  The target normals are computed once per call from ALL target points within
         `normal_radius` (fewer than 3: (0, 0, 1); orientation n_z >= 0).  constrained=True: rotation about z + translation; False: six unknowns.
         A singular system (a single plane) leaves the transform as it is.  Why 0.3 and not the search radius: the 64-ring sensor's ring spacing
         is 0.0075 x range, so at 20 m a radius of 0.1 sees only one ring and every neighbourhood is a line."""
-        B = len(sources)
-        off = np.zeros((B + 1, 2), np.int64)
-        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
-        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
-        p1, p2 = cat(sources), cat(targets)
-        init, out, fit, rmse, it, dp = self._icp_bufs(inits, B)
-        offp, itp = off.ctypes.data_as(C.POINTER(C.c_int64)), it.ctypes.data_as(C.POINTER(C.c_int32))
-        self._check(self._lib.alignnet_icp_plane_register(self._h, _fp(p1), _fp(p2), offp, B, dp(init), float(radius), float(normal_radius), int(its),
-                                                          0 if constrained else ICP_FULL_ROTATION, dp(out), dp(fit), dp(rmse), itp))
-        return dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+        p1, p2, off = _pack_pairs(sources, targets)
+        return self._icp_surface(self._lib.alignnet_icp_plane_register, (_fp(p1), _fp(p2), _lp(off)), inits, len(sources), radius, normal_radius, its,
+                                 constrained)
 
     def icp_plane_refine_rows(self, rows, inits, radius=0.1, normal_radius=0.3, its=30, constrained=True):
         """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows."""
         r, rp = self._rows(rows)
-        init, out, fit, rmse, it, dp = self._icp_bufs(inits, r.size)
-        itp = it.ctypes.data_as(C.POINTER(C.c_int32))
-        self._check(self._lib.alignnet_icp_plane_register_dataset(self._h, rp, r.size, dp(init), float(radius), float(normal_radius), int(its),
-                                                                  0 if constrained else ICP_FULL_ROTATION, dp(out), dp(fit), dp(rmse), itp))
-        return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+        return self._icp_surface(self._lib.alignnet_icp_plane_register_dataset, (rp,), inits, r.size, radius, normal_radius, its, constrained)
 
     # ---- generalized (plane-to-plane) ICP (csrc/alignnet_icp.hip: icp_generalized_*; semantics: tests/icp_generalized_ref.py) ----
     def icp_generalized_refine(self, sources, targets, inits, radius=0.1, normal_radius=0.3, its=30, constrained=True):
         """Generalized ICP (Segal, Haehnel, Thrun 2009): icp_plane_refine's loop, arguments and return dict with every correspondence weighted by
         the inverse of the sum of the two surface covariances (1e-3 along the normal, 1 across it).  Normals of BOTH clouds are computed once per
         call, each cloud on its own within `normal_radius`, the source's in its own frame.  A single plane gives a regular system."""
-        B = len(sources)
-        off = np.zeros((B + 1, 2), np.int64)
-        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
-        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
-        p1, p2 = cat(sources), cat(targets)
-        init, out, fit, rmse, it, dp = self._icp_bufs(inits, B)
-        offp, itp = off.ctypes.data_as(C.POINTER(C.c_int64)), it.ctypes.data_as(C.POINTER(C.c_int32))
-        fn = self._register_fn("alignnet_icp_generalized_register")
-        self._check(fn(self._h, _fp(p1), _fp(p2), offp, B, dp(init), float(radius), float(normal_radius), int(its),
-                       0 if constrained else ICP_FULL_ROTATION, dp(out), dp(fit), dp(rmse), itp))
-        return dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+        p1, p2, off = _pack_pairs(sources, targets)
+        return self._icp_surface(self._register_fn("alignnet_icp_generalized_register"), (_fp(p1), _fp(p2), _lp(off)), inits, len(sources), radius,
+                                 normal_radius, its, constrained)
 
     def icp_generalized_refine_rows(self, rows, inits, radius=0.1, normal_radius=0.3, its=30, constrained=True):
         """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows."""
         r, rp = self._rows(rows)
-        init, out, fit, rmse, it, dp = self._icp_bufs(inits, r.size)
-        itp = it.ctypes.data_as(C.POINTER(C.c_int32))
-        fn = self._register_fn("alignnet_icp_generalized_register_dataset")
-        self._check(fn(self._h, rp, r.size, dp(init), float(radius), float(normal_radius), int(its), 0 if constrained else ICP_FULL_ROTATION, dp(out),
-                       dp(fit), dp(rmse), itp))
-        return dict(transforms=out.reshape(r.size, 4, 4), fitness=fit, rmse=rmse, iterations=it)
+        return self._icp_surface(self._register_fn("alignnet_icp_generalized_register_dataset"), (rp,), inits, r.size, radius, normal_radius, its,
+                                 constrained)
 
     # ---- one-call registration: clouds to transforms on the device (csrc/alignnet_register.hip; DESIGN.md 4.8b) ----
     REFINE = {None: 0, "point": 1, "plane": 2, "generalized": 4}   # (the option values of alignnet_register_options.refine; 3 is not assigned)
@@ -549,13 +542,12 @@ class Engine:
                                     float(normal_radius))
         n = max(B, 0)
         res = dict(transforms=np.empty((n, 4, 4), np.float64), network_transforms=np.empty((n, 4, 4), np.float64), angles=np.empty((n, 4), np.float64))
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
         out = _capi.RegisterOutputs()
-        out.transforms, out.network_transforms, out.angles = dp(res["transforms"]), dp(res["network_transforms"]), dp(res["angles"])
+        out.transforms, out.network_transforms, out.angles = _dp(res["transforms"]), _dp(res["network_transforms"]), _dp(res["angles"])
         keep = []
         if refine:
             res.update(fitness=np.empty(n, np.float64), rmse=np.empty(n, np.float64), iterations=np.empty(n, np.int32))
-            out.fitness, out.rmse, out.iterations = dp(res["fitness"]), dp(res["rmse"]), res["iterations"].ctypes.data_as(C.POINTER(C.c_int32))
+            out.fitness, out.rmse, out.iterations = _dp(res["fitness"]), _dp(res["rmse"]), _ip(res["iterations"])
         if want_net:
             arrs, o = self._alloc_outputs(n)
             res.update(arrs)
@@ -583,18 +575,14 @@ class Engine:
         B = len(sources)
         if len(targets) != B:
             raise ValueError("register: %d sources and %d targets" % (B, len(targets)))
-        off = np.zeros((B + 1, 2), np.int64)
-        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
-        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
-        p1, p2 = cat(sources), cat(targets)
+        p1, p2, off = _pack_pairs(sources, targets)
         st = None
         if streams is not None:
             st = np.ascontiguousarray(streams, np.int64).ravel()
             if st.size != B:
                 raise ValueError("register: %d streams for %d pairs" % (st.size, B))
         opt, out, res, loss, keep = self._register_bufs(B, refine, radius, normal_radius, its, constrained, want_net, False)
-        self._check(fn(self._h, _fp(p1), _fp(p2), off.ctypes.data_as(C.POINTER(C.c_int64)), B, int(seed),
-                       st.ctypes.data_as(C.POINTER(C.c_int64)) if st is not None else None, C.byref(opt), C.byref(out)))
+        self._check(fn(self._h, _fp(p1), _fp(p2), _lp(off), B, int(seed), _lp(st), C.byref(opt), C.byref(out)))
         return self._register_finish(res, loss)
 
     def register_rows(self, rows, seed, refine=None, radius=0.1, normal_radius=0.3, its=30, constrained=True, want_net=False, want_loss=False):
@@ -611,17 +599,14 @@ class Engine:
         4x4 `T` and the estimate that follows.  Returns dict(normals [n2, 3], neighbours [n2], index [n1] (-1 without a candidate), dist2 [n1]
         (inf without), inlier [n1] bool, residual [n1] (0 for outliers), sums [29] (count, sum dist2, upper triangle of J^T J, J^T r; 16 used
         by the z-constrained estimate), update [4, 4], fitness, rmse)."""
-        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
-        Tm = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+        p1, p2, Tm = _one_pair(source, target, T)
         n, m = max(len(p1), 1), max(len(p2), 1)
         nrm, nbr = np.zeros((m, 3), np.float64), np.zeros(m, np.int32)
         idx, d2, inl, res = np.full(n, -1, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.float64)
         sums, upd, fit, rmse = np.zeros(29, np.float64), np.zeros(16, np.float64), np.zeros(1, np.float64), np.zeros(1, np.float64)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        self._check(self._lib.alignnet_debug_icp_plane(self._h, _fp(p1), len(p1), _fp(p2), len(p2), dp(Tm), float(radius), float(normal_radius),
-                                                       0 if constrained else ICP_FULL_ROTATION, dp(nrm), ip(nbr), ip(idx), dp(d2), ip(inl), dp(res),
-                                                       dp(sums), dp(upd), dp(fit), dp(rmse)))
+        self._check(self._lib.alignnet_debug_icp_plane(self._h, _fp(p1), len(p1), _fp(p2), len(p2), _dp(Tm), float(radius), float(normal_radius),
+                                                       0 if constrained else ICP_FULL_ROTATION, _dp(nrm), _ip(nbr), _ip(idx), _dp(d2), _ip(inl), _dp(res),
+                                                       _dp(sums), _dp(upd), _dp(fit), _dp(rmse)))
         n1, n2 = len(p1), len(p2)
         return dict(normals=nrm[:n2].copy(), neighbours=nbr[:n2].copy(), index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1,
                     residual=res[:n1].copy(), sums=sums, update=upd.reshape(4, 4), fitness=float(fit[0]), rmse=float(rmse[0]))
@@ -631,17 +616,14 @@ class Engine:
         4x4 `T` and the estimate that follows.  Returns dict(normals [n2, 3], neighbours [n2] (the target's), source_normals [n1, 3],
         source_neighbours [n1], index [n1] (-1 without a candidate), dist2 [n1] (inf without), inlier [n1] bool, sums [29] (count, sum dist2, upper
         triangle of J^T M J, J^T M d; 16 used by the z-constrained estimate), update [4, 4], fitness, rmse)."""
-        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
-        Tm = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+        p1, p2, Tm = _one_pair(source, target, T)
         n, m = max(len(p1), 1), max(len(p2), 1)
         nrm, nbr, snrm, snbr = np.zeros((m, 3), np.float64), np.zeros(m, np.int32), np.zeros((n, 3), np.float64), np.zeros(n, np.int32)
         idx, d2, inl = np.full(n, -1, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32)
         sums, upd, fit, rmse = np.zeros(29, np.float64), np.zeros(16, np.float64), np.zeros(1, np.float64), np.zeros(1, np.float64)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        self._check(self._lib.alignnet_debug_icp_generalized(self._h, _fp(p1), len(p1), _fp(p2), len(p2), dp(Tm), float(radius), float(normal_radius),
-                                                             0 if constrained else ICP_FULL_ROTATION, dp(nrm), ip(nbr), dp(snrm), ip(snbr), ip(idx), dp(d2),
-                                                             ip(inl), dp(sums), dp(upd), dp(fit), dp(rmse)))
+        self._check(self._lib.alignnet_debug_icp_generalized(self._h, _fp(p1), len(p1), _fp(p2), len(p2), _dp(Tm), float(radius), float(normal_radius),
+                                                             0 if constrained else ICP_FULL_ROTATION, _dp(nrm), _ip(nbr), _dp(snrm), _ip(snbr), _ip(idx),
+                                                             _dp(d2), _ip(inl), _dp(sums), _dp(upd), _dp(fit), _dp(rmse)))
         n1, n2 = len(p1), len(p2)
         return dict(normals=nrm[:n2].copy(), neighbours=nbr[:n2].copy(), source_normals=snrm[:n1].copy(), source_neighbours=snbr[:n1].copy(),
                     index=idx[:n1].copy(), dist2=d2[:n1].copy(), inlier=inl[:n1] == 1, sums=sums, update=upd.reshape(4, 4), fitness=float(fit[0]),
@@ -656,8 +638,7 @@ class Engine:
         out = np.empty((B, 16), np.float64)
         fit, rmse = np.empty(B, np.float64), np.empty(B, np.float64)
         it, val = np.empty(B, np.int64), np.empty(B, np.int32)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        tail = (dp(out), dp(fit), dp(rmse), it.ctypes.data_as(C.POINTER(C.c_int64)), val.ctypes.data_as(C.POINTER(C.c_int32)))
+        tail = (_dp(out), _dp(fit), _dp(rmse), _lp(it), _ip(val))
         return st, tail, lambda: dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, iterations=it, validations=val)
 
     def global_register(self, sources, targets, constrained=True, seed=0, streams=None, max_iteration=4000000, max_validation=500):
@@ -666,40 +647,34 @@ class Engine:
         streams: one non-negative id per pair selecting its random draws under `seed` (default 0 .. B - 1); a pair's result
         depends on (seed, stream, clouds, arguments) only.  Returns dict(transforms, fitness, rmse, iterations, validations)."""
         B = len(sources)
-        off = np.zeros((B + 1, 2), np.int64)
-        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
-        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
-        p1, p2 = cat(sources), cat(targets)
+        p1, p2, off = _pack_pairs(sources, targets)
         st, tail, result = self._global_bufs(B, streams, np.arange(B))
-        self._check(self._lib.alignnet_global_register(self._h, _fp(p1), _fp(p2), off.ctypes.data_as(C.POINTER(C.c_int64)), B,
-                                                       0 if constrained else ICP_FULL_ROTATION, int(seed), st.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                       int(max_iteration), int(max_validation), *tail))
+        self._check(self._lib.alignnet_global_register(self._h, _fp(p1), _fp(p2), _lp(off), B, 0 if constrained else ICP_FULL_ROTATION, int(seed),
+                                                       _ip(st), int(max_iteration), int(max_validation), *tail))
         return result()
 
     def global_register_rows(self, rows, constrained=True, seed=0, streams=None, max_iteration=4000000, max_validation=500):
         """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows; streams default to the rows."""
         r, rp = self._rows(rows)
         st, tail, result = self._global_bufs(r.size, streams, r)
-        self._check(self._lib.alignnet_global_register_dataset(self._h, rp, r.size, 0 if constrained else ICP_FULL_ROTATION, int(seed),
-                                                               st.ctypes.data_as(C.POINTER(C.c_int32)), int(max_iteration), int(max_validation), *tail))
+        self._check(self._lib.alignnet_global_register_dataset(self._h, rp, r.size, 0 if constrained else ICP_FULL_ROTATION, int(seed), _ip(st),
+                                                               int(max_iteration), int(max_validation), *tail))
         return result()
 
     def debug_global_stages(self, source, target, constrained=True, seed=0, stream=0, max_iteration=4000000, max_validation=500):
         """Test hook: global_register of one pair, with the stage outputs.  Returns the result dict (scalars, transform [4, 4]) plus
         per cloud (index 0 = source, 1 = target) lists points / voxels / voxel_points / normals / spfh / fpfh, `matches` (target index
         of every downsampled source point) and `winning_iteration` (-1: no hypothesis was validated)."""
-        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+        p1, p2, _ = _one_pair(source, target)
         cap = max(len(p1), len(p2), 1)
         counts = np.zeros(2, np.int32)
         pts, vox, npt = np.zeros((2, cap, 3), np.float64), np.zeros((2, cap, 3), np.int32), np.zeros((2, cap), np.int32)
         nrm, spfh, fpfh = np.zeros((2, cap, 3), np.float64), np.zeros((2, cap, 33), np.float64), np.zeros((2, cap, 33), np.float64)
         match, win = np.zeros(cap, np.int32), np.zeros(1, np.int64)
         st, tail, result = self._global_bufs(1, [stream], None)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.alignnet_debug_global_stages(self._h, _fp(p1), len(p1), _fp(p2), len(p2), 0 if constrained else ICP_FULL_ROTATION, int(seed),
-                                                           int(stream), int(max_iteration), int(max_validation), cap, ip(counts), dp(pts), ip(vox), ip(npt),
-                                                           dp(nrm), dp(spfh), dp(fpfh), ip(match), win.ctypes.data_as(C.POINTER(C.c_int64)), *tail))
+                                                           int(stream), int(max_iteration), int(max_validation), cap, _ip(counts), _dp(pts), _ip(vox), _ip(npt),
+                                                           _dp(nrm), _dp(spfh), _dp(fpfh), _ip(match), _lp(win), *tail))
         res = result()
         out = dict(transform=res["transforms"][0], fitness=float(res["fitness"][0]), rmse=float(res["rmse"][0]), iterations=int(res["iterations"][0]),
                    validations=int(res["validations"][0]), winning_iteration=int(win[0]), counts=counts.copy(), matches=match[: counts[0]].copy())
@@ -717,10 +692,9 @@ class Engine:
         out = np.empty((B, 16), np.float64)
         fit, rmse = np.empty(B, np.float64), np.empty(B, np.float64)
         corr, trials = np.empty(B, np.int32), np.empty(B, np.int64)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
         flags = (0 if constrained else ICP_FULL_ROTATION) | (FGR_DECREASE_MU if decrease_mu else 0)
         options = (float(division_factor), float(maximum_correspondence_distance), int(iteration_number), float(tuple_scale), int(maximum_tuple_count))
-        tail = (dp(out), dp(fit), dp(rmse), corr.ctypes.data_as(C.POINTER(C.c_int32)), trials.ctypes.data_as(C.POINTER(C.c_int64)))
+        tail = (_dp(out), _dp(fit), _dp(rmse), _ip(corr), _lp(trials))
         return st, flags, options, tail, lambda: dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, correspondences=corr, trials=trials)
 
     def fgr_register(self, sources, targets, constrained=True, decrease_mu=False, seed=0, streams=None, division_factor=1.4,
@@ -731,14 +705,10 @@ class Engine:
         its tuple draws under `seed` (default 0 .. B - 1); a pair's result depends on (seed, stream, clouds, arguments) only.
         Returns dict(transforms, fitness, rmse, correspondences, trials)."""
         B = len(sources)
-        off = np.zeros((B + 1, 2), np.int64)
-        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
-        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
-        p1, p2 = cat(sources), cat(targets)
+        p1, p2, off = _pack_pairs(sources, targets)
         st, flags, options, tail, result = self._fgr_bufs(B, streams, np.arange(B), constrained, decrease_mu, division_factor,
                                                           maximum_correspondence_distance, iteration_number, tuple_scale, maximum_tuple_count)
-        self._check(self._lib.alignnet_fgr_register(self._h, _fp(p1), _fp(p2), off.ctypes.data_as(C.POINTER(C.c_int64)), B, flags, int(seed),
-                                                    st.ctypes.data_as(C.POINTER(C.c_int32)), *options, *tail))
+        self._check(self._lib.alignnet_fgr_register(self._h, _fp(p1), _fp(p2), _lp(off), B, flags, int(seed), _ip(st), *options, *tail))
         return result()
 
     def fgr_register_rows(self, rows, constrained=True, decrease_mu=False, seed=0, streams=None, division_factor=1.4,
@@ -747,8 +717,7 @@ class Engine:
         r, rp = self._rows(rows)
         st, flags, options, tail, result = self._fgr_bufs(r.size, streams, r, constrained, decrease_mu, division_factor,
                                                           maximum_correspondence_distance, iteration_number, tuple_scale, maximum_tuple_count)
-        self._check(self._lib.alignnet_fgr_register_dataset(self._h, rp, r.size, flags, int(seed), st.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                            *options, *tail))
+        self._check(self._lib.alignnet_fgr_register_dataset(self._h, rp, r.size, flags, int(seed), _ip(st), *options, *tail))
         return result()
 
     def debug_fgr_stages(self, source, target, constrained=True, decrease_mu=False, seed=0, stream=0, division_factor=1.4,
@@ -759,7 +728,7 @@ class Engine:
         `tuple_target` (the correspondences the tuple test kept, 3 per accepted trial, in trial order), `tuple_trials` (the trial of every
         accepted tuple), `means` [2, 3], `scale`, and `trace` [iteration_number, 4, 4]: the transform after every iteration, in the normalised
         frame, moving the target onto the source."""
-        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+        p1, p2, _ = _one_pair(source, target)
         cap = max(len(p1), len(p2), 1)
         mtc, its = max(int(maximum_tuple_count), 0), max(int(iteration_number), 0)
         counts = np.zeros(4, np.int32)
@@ -769,11 +738,9 @@ class Engine:
         norm, trace = np.zeros(7, np.float64), np.zeros((its + 1, 16), np.float64)
         st, flags, options, tail, result = self._fgr_bufs(1, [stream], None, constrained, decrease_mu, division_factor,
                                                           maximum_correspondence_distance, iteration_number, tuple_scale, maximum_tuple_count)
-        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self._lib.alignnet_debug_fgr_stages(self._h, _fp(p1), len(p1), _fp(p2), len(p2), flags, int(seed), int(stream), *options, cap,
-                                                        ip(counts), dp(pts), dp(fpfh), ip(match), ip(rmatch), ip(cross), ip(ts), ip(tt),
-                                                        ttr.ctypes.data_as(C.POINTER(C.c_int64)), dp(norm), dp(trace), *tail))
+                                                        _ip(counts), _dp(pts), _dp(fpfh), _ip(match), _ip(rmatch), _ip(cross), _ip(ts), _ip(tt),
+                                                        _lp(ttr), _dp(norm), _dp(trace), *tail))
         res = result()
         na = int(counts[3])
         out = dict(transform=res["transforms"][0], fitness=float(res["fitness"][0]), rmse=float(res["rmse"][0]),
@@ -822,8 +789,7 @@ class Engine:
         L = _capi.GOICP_MAX_LEVELS
         out, err, low, fit = np.empty((B, 16), np.float64), np.empty(B, np.float64), np.empty(B, np.float64), np.empty(B, np.float64)
         st, ev, sv = np.empty(B, np.int32), np.empty((B, L), np.int32), np.empty((B, L), np.int32)
-        dp, ip = (lambda a: a.ctypes.data_as(C.POINTER(C.c_double))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)))
-        tail = (dp(out), dp(err), dp(low), dp(fit), ip(st), ip(ev), ip(sv))
+        tail = (_dp(out), _dp(err), _dp(low), _dp(fit), _ip(st), _ip(ev), _ip(sv))
         return tail, lambda: dict(transforms=out.reshape(B, 4, 4), error=err, lower_bound=low, fitness=fit, status=st, evaluated=ev, survived=sv)
 
     def goicp_register(self, sources, targets, constrained=True, refine=None, **params):
@@ -840,12 +806,9 @@ class Engine:
         B = len(sources)
         if len(targets) != B:
             raise ValueError("goicp_register: %d sources and %d targets" % (B, len(targets)))
-        off = np.zeros((B + 1, 2), np.int64)
-        off[1:, 0] = np.cumsum([len(s) for s in sources]); off[1:, 1] = np.cumsum([len(t) for t in targets])
-        cat = lambda L: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 3) for x in L], 0)) if L else np.zeros((0, 3), np.float32)
-        p1, p2 = cat(sources), cat(targets)
+        p1, p2, off = _pack_pairs(sources, targets)
         tail, result = self._goicp_bufs(B)
-        self._check(fn(self._h, _fp(p1), _fp(p2), off.ctypes.data_as(C.POINTER(C.c_int64)), B, C.byref(p), *tail))
+        self._check(fn(self._h, _fp(p1), _fp(p2), _lp(off), B, C.byref(p), *tail))
         res = result()
         if refine == "p2p":
             ref = self.icp_refine(sources, targets, res["transforms"], radius=self.GOICP_REFINE_RADIUS, its=self.GOICP_REFINE_ITS)
@@ -869,12 +832,11 @@ class Engine:
         """Test hook: (ub [K], lb [K]) of K nodes of one pair, given as integer coordinates coords [K, 4] at the halvings depth [4] of
         (theta, x, y, z), by the search's own evaluation kernel."""
         p = self._goicp_params(True, None, params)
-        p1 = np.ascontiguousarray(np.asarray(source, np.float32).reshape(-1, 3)); p2 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 3))
+        p1, p2, _ = _one_pair(source, target)
         d = np.ascontiguousarray(depth, np.int32).reshape(4)
         c = np.ascontiguousarray(coords, np.int32).reshape(-1, 4)
         ub, lb = np.empty(len(c), np.float64), np.empty(len(c), np.float64)
-        dp, ip = (lambda a: a.ctypes.data_as(C.POINTER(C.c_double))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)))
-        self._check(self._lib.alignnet_debug_goicp_nodes(self._h, _fp(p1), len(p1), _fp(p2), len(p2), C.byref(p), ip(d), ip(c), len(c), dp(ub), dp(lb)))
+        self._check(self._lib.alignnet_debug_goicp_nodes(self._h, _fp(p1), len(p1), _fp(p2), len(p2), C.byref(p), _ip(d), _ip(c), len(c), _dp(ub), _dp(lb)))
         return ub, lb
 
     # ---- multiway registration: pose-graph optimisation (csrc/alignnet_posegraph.hip; semantics: tests/pose_graph_ref.py) ----

@@ -216,6 +216,18 @@ __device__ __forceinline__ void block_reduce(double (&v)[N], double* red /*[wave
   __syncthreads();
 }
 
+// pair b of a launch: where its source and its target start in the blobs, and their sizes (a kernel that reads one cloud takes those fields alone).
+// Used where it leaves the kernel's instructions as they were: the loop kernel of the two surface estimates and the two grid builds
+struct IcpPair { long long s_lo, n1, t_lo, n2; };
+__device__ __forceinline__ IcpPair icp_pair(const IcpArgs& a, int b)
+{
+  const long long row = a.rows ? a.rows[b] : b;
+  IcpPair p;
+  p.s_lo = a.off[row * 2]; p.n1 = a.off[(row + 1) * 2] - p.s_lo;
+  p.t_lo = a.off[row * 2 + 1]; p.n2 = a.off[(row + 1) * 2 + 1] - p.t_lo;
+  return p;
+}
+
 // kTrace: the SAME scan, and behind the quad's merge one record per source point (IcpArgs::tr_*) -- the test hook's instantiations; the
 // shipped ones (kTrace = false) compile to what they were without it (per-kernel resource remarks unchanged)
 // kGrid: the grid search in place of the scan (one lane per source point, the bucket table in LDS); loop, sums, estimate and stop are the same source
@@ -534,9 +546,8 @@ __device__ __forceinline__ void icp_grid_build_cloud(const float* dst, long long
 __global__ __launch_bounds__(kIcpThreads) void icp_grid_build_kernel(const IcpGridArgs a)
 {
   const int b = blockIdx.x;
-  const long long row = a.rows ? a.rows[b] : b;
-  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
-  icp_grid_build_cloud(a.pts[1] + t_lo * 3, n2, a.ws + a.ws_off[b], a.radius);
+  const IcpPair pr = icp_pair(a, b);
+  icp_grid_build_cloud(a.pts[1] + pr.t_lo * 3, pr.n2, a.ws + a.ws_off[b], a.radius);
 }
 
 // shared driver: tables already on the device
@@ -651,6 +662,50 @@ int plan_search(alignnet_handle* h, int mode, const std::vector<long long>& n2, 
   return 0;
 }
 
+// the launches over plan_search's result, in order: pairs [lo, hi) are a run of scan pairs or one chunk of grid pairs (a chunk's first pair sits at
+// offset 0); big: the chunk's largest target; lds: the dynamic LDS of the run's kernels.  Starts from {0, 0}
+struct IcpRun { int lo, hi; bool grid; long long big; size_t lds; };
+bool next_run(const std::vector<char>& grid, const std::vector<long long>& ws_off, const std::vector<long long>& n2, int lds_points, IcpRun* r)
+{
+  const int B = (int)grid.size();
+  r->lo = r->hi;
+  if (r->lo >= B) return false;
+  r->hi = r->lo + 1; r->grid = grid[r->lo]; r->big = n2[r->lo];
+  if (!r->grid) {
+    while (r->hi < B && !grid[r->hi]) ++r->hi;
+    r->lds = icp_lds_bytes(lds_points);
+  } else {
+    while (r->hi < B && grid[r->hi] && ws_off[r->hi] != 0) { r->big = std::max(r->big, n2[r->hi]); ++r->hi; }
+    r->lds = ((size_t)icp_grid_buckets(r->big) + 1) * 4;
+  }
+  return true;
+}
+
+// the grids of a chunk's targets (the build reads the clouds, the radius and the workspace)
+void launch_grid_build(alignnet_handle* h, const IcpGridArgs& g, const IcpRun& r)
+{
+  alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID_BUILD);
+  hipLaunchKernelGGL(icp_grid_build_kernel, dim3(r.hi - r.lo), dim3(kIcpThreads), r.lds, h->stream, g);
+}
+
+// the loop kernels by argument type: one entry serves the attribute call and the launch
+using Scan = void (*)(const IcpArgs);
+using Grid = void (*)(const IcpGridArgs);
+using Eval = void (*)(const IcpEvalArgs);
+constexpr Scan kIcpScan[2][2] = {{icp_kernel<false>, icp_kernel<true>}, {icp_kernel<false, true>, icp_kernel<true, true>}};   // [trace][full]
+constexpr Grid kIcpGrid[2][2] = {{icp_kernel<false, false, true>, icp_kernel<true, false, true>}, {icp_kernel<false, true, true>, icp_kernel<true, true, true>}};
+constexpr Eval kIcpEval[2] = {icp_kernel<false, false, false, true>, icp_kernel<false, false, true, true>};   // [grid]
+
+// a kernel's dynamic-LDS ceiling, raised once per device
+template <class Kernel>
+int raise_lds(alignnet_handle* h, alignnet::PerDeviceOnce* once, Kernel kernel)
+{
+  if (!once->need(h->cfg.device)) return 0;
+  HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+  once->mark(h->cfg.device);
+  return 0;
+}
+
 // stage_n2: what the scan's LDS stage is sized for
 int run_icp(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, const double* init, double radius, int its, bool full, double* out,
             double* fitness, double* rmse, int* iters, const IcpTraceOut* trace = nullptr, const alignnet::IcpDeviceIo* dev = nullptr)
@@ -691,54 +746,24 @@ int run_icp(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, c
     a.tr_dist = reinterpret_cast<double*>(tr.p);
     a.tr_index = reinterpret_cast<int*>(tr.p + n * 8); a.tr_inlier = a.tr_index + n; a.tr_paths = a.tr_inlier + n;
   }
-  static alignnet::PerDeviceOnce attr[9];
+  static alignnet::PerDeviceOnce attr[9];   // [which]: scan, [which + 4]: grid, [8]: the build
   const int which = (full ? 1 : 0) + (trace ? 2 : 0);
-  const void* const kernels[9] = {reinterpret_cast<const void*>(icp_kernel<false>), reinterpret_cast<const void*>(icp_kernel<true>),
-                                  reinterpret_cast<const void*>(icp_kernel<false, true>), reinterpret_cast<const void*>(icp_kernel<true, true>),
-                                  reinterpret_cast<const void*>(icp_kernel<false, false, true>), reinterpret_cast<const void*>(icp_kernel<true, false, true>),
-                                  reinterpret_cast<const void*>(icp_kernel<false, true, true>), reinterpret_cast<const void*>(icp_kernel<true, true, true>),
-                                  reinterpret_cast<const void*>(icp_grid_build_kernel)};
-  for (const int kn : {which, which + 4, 8})
-    if ((kn < 4 || need) && attr[kn].need(h->cfg.device)) {
-      HIP_TRY(h, hipFuncSetAttribute(kernels[kn], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
-      attr[kn].mark(h->cfg.device);
-    }
-  for (int lo = 0; lo < B;) {
-    int hi = lo + 1;
-    if (!grid[lo]) {
-      while (hi < B && !grid[hi]) ++hi;
-      const IcpArgs r = icp_args_from<IcpArgs>(a, lo);
-      const size_t lds = icp_lds_bytes(a.lds_points);
-      if (which == 3)
-        hipLaunchKernelGGL((icp_kernel<true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-      else if (which == 2)
-        hipLaunchKernelGGL((icp_kernel<false, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-      else if (full)
-        hipLaunchKernelGGL(icp_kernel<true>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-      else
-        hipLaunchKernelGGL(icp_kernel<false>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-    } else {
-      long long big = n2[lo];
-      while (hi < B && grid[hi] && ws_off[hi] != 0) { big = std::max(big, n2[hi]); ++hi; }   // (a chunk's first pair sits at offset 0)
-      IcpGridArgs r = icp_args_from<IcpGridArgs>(a, lo);
-      r.ws_off += lo;
-      const size_t lds = ((size_t)icp_grid_buckets(big) + 1) * 4;
-      {
-        alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID_BUILD);
-        hipLaunchKernelGGL(icp_grid_build_kernel, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-      }
+  const Scan scan = kIcpScan[trace != nullptr][full];
+  const Grid search = kIcpGrid[trace != nullptr][full];
+  if (raise_lds(h, &attr[which], scan)) return 1;
+  if (need && (raise_lds(h, &attr[which + 4], search) || raise_lds(h, &attr[8], icp_grid_build_kernel))) return 1;
+  for (IcpRun run = {0, 0}; next_run(grid, ws_off, n2, a.lds_points, &run);) {
+    const dim3 pairs(run.hi - run.lo);
+    if (!run.grid)
+      hipLaunchKernelGGL(scan, pairs, dim3(kIcpThreads), run.lds, h->stream, icp_args_from<IcpArgs>(a, run.lo));
+    else {
+      IcpGridArgs r = icp_args_from<IcpGridArgs>(a, run.lo);
+      r.ws_off += run.lo;
+      launch_grid_build(h, r, run);
       alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID);
-      if (which == 3)
-        hipLaunchKernelGGL((icp_kernel<true, true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-      else if (which == 2)
-        hipLaunchKernelGGL((icp_kernel<false, true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-      else if (full)
-        hipLaunchKernelGGL((icp_kernel<true, false, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-      else
-        hipLaunchKernelGGL((icp_kernel<false, false, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      hipLaunchKernelGGL(search, pairs, dim3(kIcpThreads), run.lds, h->stream, r);
     }
     HIP_TRY(h, hipGetLastError());
-    lo = hi;
   }
   if (trace) {
     const size_t n = (size_t)std::max<long long>(trace->n1, 1), m = (size_t)trace->n1;
@@ -817,38 +842,24 @@ int run_eval(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, 
   a.tr_index = a.tr_inlier = a.tr_paths = nullptr; a.tr_dist = nullptr;
   a.ws = static_cast<char*>(h->icp_grid_ws); a.ws_off = tab.p + B;
   a.centers = cen.p; a.info = info.p; a.corr = corr.p; a.corr_off = tab.p;
-  static alignnet::PerDeviceOnce attr[3];
-  const void* const kernels[3] = {reinterpret_cast<const void*>(icp_kernel<false, false, false, true>),
-                                  reinterpret_cast<const void*>(icp_kernel<false, false, true, true>), reinterpret_cast<const void*>(icp_grid_build_kernel)};
-  for (int kn = 0; kn < 3; ++kn)
-    if ((kn == 0 || need) && attr[kn].need(h->cfg.device)) {
-      HIP_TRY(h, hipFuncSetAttribute(kernels[kn], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
-      attr[kn].mark(h->cfg.device);
-    }
-  for (int lo = 0; lo < B;) {
-    int hi = lo + 1;
+  static alignnet::PerDeviceOnce attr[3];   // scan, grid, the build
+  if (raise_lds(h, &attr[0], kIcpEval[0])) return 1;
+  if (need && (raise_lds(h, &attr[1], kIcpEval[1]) || raise_lds(h, &attr[2], icp_grid_build_kernel))) return 1;
+  for (IcpRun run = {0, 0}; next_run(grid, ws_off, c.n2, a.lds_points, &run);) {
+    const int lo = run.lo;
     IcpEvalArgs r = a;   // pairs lo.. as a launch of their own
     r.init += (size_t)lo * 16; r.fitness += lo; r.rmse += lo; r.corr_off += lo; r.ws_off += lo;
     if (r.centers) r.centers += (size_t)lo * 3;
     if (r.info) r.info += (size_t)lo * 36;
     if (r.rows) r.rows += lo; else r.off += (size_t)lo * 2;
-    if (!grid[lo]) {
-      while (hi < B && !grid[hi]) ++hi;
-      hipLaunchKernelGGL((icp_kernel<false, false, false, true>), dim3(hi - lo), dim3(kIcpThreads), icp_lds_bytes(a.lds_points), h->stream, r);
-    } else {
-      long long big = c.n2[lo];
-      while (hi < B && grid[hi] && ws_off[hi] != 0) { big = std::max(big, c.n2[hi]); ++hi; }
-      const size_t lds = ((size_t)icp_grid_buckets(big) + 1) * 4;
-      {
-        alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID_BUILD);
-        const IcpGridArgs g = r;   // (the build reads the clouds, the radius and the workspace)
-        hipLaunchKernelGGL(icp_grid_build_kernel, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, g);
-      }
+    if (!run.grid)
+      hipLaunchKernelGGL(kIcpEval[0], dim3(run.hi - lo), dim3(kIcpThreads), run.lds, h->stream, r);
+    else {
+      launch_grid_build(h, r, run);
       alignnet::ProfScope prof_scope(h, alignnet::PK_ICP_GRID);
-      hipLaunchKernelGGL((icp_kernel<false, false, true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+      hipLaunchKernelGGL(kIcpEval[1], dim3(run.hi - lo), dim3(kIcpThreads), run.lds, h->stream, r);
     }
     HIP_TRY(h, hipGetLastError());
-    lo = hi;
   }
   HIP_TRY(h, hipMemcpyAsync(fitness, fr.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipMemcpyAsync(rmse, fr.p + B, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -867,7 +878,7 @@ int run_eval(alignnet_handle* h, const IcpClouds& c, long long stage_n2, int B, 
 // point itself included, no cap on their number) and writes the unit eigenvector of the smallest eigenvalue of S2 / K - m m^T with n_z >= 0, or
 // (0, 0, 1) for K < 3.  A bucket reached through two of the 27 cells is walked once: sums, unlike the minimum of the search, would count it twice.
 // The cell claim of the grid search (file header) holds for a target as the query and normal_radius as the radius: same arithmetic, same bound.
-// Loop (icp_plane_kernel, one workgroup per pair, always the grid search): evaluate, stop test, estimate, T <- U T exactly as icp_kernel.  Estimate over
+// Loop (icp_surface_kernel<false, .>, one workgroup per pair, always the grid search): evaluate, stop test, estimate, T <- U T exactly as icp_kernel.  Estimate over
 // the inlier correspondences (p, q, n): r = (p - q) . n, a = p - c (c = the pivot, the pair's first target), J = [a x n, n] (full) or [(a x n)_z, n]
 // (z-constrained); J^T J x = -J^T r by Cholesky without pivoting on the diagonally scaled matrix; U = Tr(c) [Rz(g) Ry(b) Rx(a) | t] Tr(-c).  A diagonal
 // entry <= 0, a pivot <= kIcpPlanePivot or no correspondence determines no update: U = I.
@@ -1066,119 +1077,6 @@ __device__ __forceinline__ bool icp_plane_update(const double* tot, double cx, d
   return true;
 }
 
-// kTrace (alignnet_debug_icp_plane, one pair): the same evaluation with one record per source point behind it, then the sums and the update of the
-// estimate that follows, and no further iteration
-template <bool kFull, bool kTrace = false>
-__global__ __launch_bounds__(kIcpThreads) void icp_plane_kernel(const IcpPlaneArgs a)
-{
-  constexpr int kSums = kFull ? kIcpPlaneSumsFull : kIcpPlaneSums;
-  extern __shared__ __attribute__((aligned(16))) int gstart[];   // [H + 1] bucket starts of grid A
-  __shared__ double T[12];
-  __shared__ double red[(kIcpThreads / 64) * kSums], tot[kSums];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const long long row = a.rows ? a.rows[b] : b;
-  const long long s_lo = a.off[row * 2], n1 = a.off[(row + 1) * 2] - s_lo;
-  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
-  const float* src = a.pts[0] + s_lo * 3;
-  const float* dst = a.pts[1] + t_lo * 3;
-  if (tid < 12) T[tid] = a.init[(size_t)b * 16 + tid];
-  IcpGridView g = icp_grid_view(a.ws + a.ws_off[b], n2);
-  const double* const nrm = icp_plane_normals(g, n2);
-  for (int j = tid; j <= g.buckets; j += kIcpThreads) gstart[j] = g.start[j];
-  g.start = gstart;   // the search reads the LDS copy
-  __syncthreads();
-  const double r2 = a.radius * a.radius;
-  const double cx = n2 > 0 ? (double)dst[0] : 0.0, cy = n2 > 0 ? (double)dst[1] : 0.0, cz = n2 > 0 ? (double)dst[2] : 0.0;   // the pivot of icp_kernel
-  double fit_prev = 0.0, rmse_prev = 0.0, fit = 0.0, rmse = 0.0;
-  int k = 0;
-  if (n1 > 0 && n2 > 0)
-    for (k = 0;; ++k) {
-      double v[kSums];
-#pragma unroll
-      for (int q = 0; q < kSums; ++q) v[q] = 0.0;
-      for (long long i = tid; i < n1; i += kIcpThreads) {
-        const double sx = src[i * 3], sy = src[i * 3 + 1], sz = src[i * 3 + 2];
-        const double px = icp_affine_unfused(T[0], T[1], T[2], T[3], sx, sy, sz);
-        const double py = icp_affine_unfused(T[4], T[5], T[6], T[7], sx, sy, sz);
-        const double pz = icp_affine_unfused(T[8], T[9], T[10], T[11], sx, sy, sz);
-        double best = 1e300; int bj = 0x7fffffff;
-        float4 brec = {0.f, 0.f, 0.f, 0.f};
-        int cand = 0;   // (counted by icp_kernel's traced instantiation alone)
-        icp_grid_nearest<false>(px, py, pz, g, best, bj, brec, cand);
-        const bool inlier = best <= r2;
-        double res = 0.0;
-        if (inlier) {
-          const double nx = nrm[(size_t)bj * 3], ny = nrm[(size_t)bj * 3 + 1], nz = nrm[(size_t)bj * 3 + 2];
-          res = icp_dot3_unfused(px - (double)brec.x, nx, py - (double)brec.y, ny, pz - (double)brec.z, nz);
-          const double ax = px - cx, ay = py - cy, az = pz - cz;
-          v[0] += 1.0; v[1] += best;
-          if constexpr (kFull) {
-            const double J[6] = {ay * nz - az * ny, az * nx - ax * nz, ax * ny - ay * nx, nx, ny, nz};
-            int q = 2;
-#pragma unroll
-            for (int i = 0; i < 6; ++i)
-#pragma unroll
-              for (int j = i; j < 6; ++j) v[q++] += J[i] * J[j];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) v[23 + i] += J[i] * res;
-          } else {
-            const double J[4] = {ax * ny - ay * nx, nx, ny, nz};
-            int q = 2;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-              for (int j = i; j < 4; ++j) v[q++] += J[i] * J[j];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[12 + i] += J[i] * res;
-          }
-        }
-        if constexpr (kTrace) {
-          if (k == 0) {
-            const bool found = bj != 0x7fffffff;
-            a.tr_index[i] = found ? bj : -1; a.tr_dist[i] = found ? best : __builtin_huge_val(); a.tr_inlier[i] = inlier; a.tr_resid[i] = res;
-          }
-        }
-      }
-      block_reduce(v, red, tot);
-      const double cnt = tot[0];
-      fit = cnt / (double)n1;
-      rmse = cnt > 0.0 ? sqrt(tot[1] / cnt) : 0.0;
-      if constexpr (kTrace) {
-        if (tid == 0) {
-          double U[12];
-          icp_plane_update<kFull>(tot, cx, cy, cz, U);
-          for (int q = 0; q < kIcpPlaneSumsFull; ++q) a.tr_sums[q] = q < kSums ? tot[q] : 0.0;
-          for (int q = 0; q < 12; ++q) a.tr_update[q] = U[q];
-        }
-        break;
-      }
-      if (k > 0 && fabs(fit - fit_prev) < 1e-6 && fabs(rmse - rmse_prev) < 1e-6) break;
-      if (k == a.its) break;
-      fit_prev = fit; rmse_prev = rmse;
-      if (tid == 0) {
-        double U[12], n[12];
-        if (icp_plane_update<kFull>(tot, cx, cy, cz, U)) {   // T <- U T
-#pragma unroll
-          for (int r = 0; r < 3; ++r) {
-#pragma unroll
-            for (int col = 0; col < 4; ++col) n[r * 4 + col] = U[r * 4] * T[col] + U[r * 4 + 1] * T[4 + col] + U[r * 4 + 2] * T[8 + col];
-            n[r * 4 + 3] += U[r * 4 + 3];
-          }
-          for (int q = 0; q < 12; ++q) T[q] = n[q];
-        }
-      }
-      __syncthreads();
-    }
-  __syncthreads();
-  if (tid < 12) a.out[(size_t)b * 16 + tid] = T[tid];
-  if (tid >= 12 && tid < 16) a.out[(size_t)b * 16 + tid] = tid == 15 ? 1.0 : 0.0;
-  if (tid == 0) {
-    if (a.fitness) a.fitness[b] = fit;
-    if (a.rmse) a.rmse[b] = rmse;
-    if (a.iters) a.iters[b] = k;
-  }
-}
-
 // ---- generalized (plane-to-plane) ICP (alignnet_icp_generalized_register*): normals of BOTH clouds once per call, every correspondence weighted by
 // the inverse of the sum of the two surface covariances ---------------------------------------------------------------------------------------------
 // Semantics: tests/icp_generalized_ref.py (Segal, Haehnel, Thrun 2009; the covariances of Open3D's registration_generalized_icp, epsilon 1e-3).  A
@@ -1186,8 +1084,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_plane_kernel(const IcpPlaneAr
 // target (grid A, grid B, ordered records, normals, counts: the same kernels, the same layout at the head of the pair's part) and behind it a third
 // grid over the SOURCE with cells of normal_radius, its ordered records, normals and counts (icp_generalized_*_source_kernel: the bodies of the
 // target's kernels on the other cloud; the normals are taken in the source's own frame) and one int per source point for the loop.
-// Loop (icp_generalized_kernel, one workgroup of 1024 lanes per pair, bucket starts of grid A in LDS, icp_grid_nearest): evaluate, stop test, estimate,
-// T <- U T as icp_plane_kernel.  Estimate over the inliers (p, q, n_q, n_p), R = the rotation of the current T: m = R n_p,
+// Loop (icp_surface_kernel<true, .>, one workgroup of 1024 lanes per pair, bucket starts of grid A in LDS, icp_grid_nearest): evaluate, stop test, estimate,
+// T <- U T as point-to-plane.  Estimate over the inliers (p, q, n_q, n_p), R = the rotation of the current T: m = R n_p,
 // A = 2 I - (1 - eps)(n_q n_q^T + m m^T) = C_q + R C_p R^T, M = A^-1 by cofactors, d = p - q, a = p - c, J = [e_x x a, e_y x a, e_z x a, I] (full) or
 // [e_z x a, I] (z-constrained); the sums are count, sum |d|^2, the upper triangle of sum J^T M J row by row and sum J^T M d: point-to-plane's 16 / 29
 // slots, reduced by block_reduce and solved by icp_plane_update as they are.  Everything per correspondence is evaluated without contraction in the
@@ -1214,10 +1112,8 @@ __host__ __device__ inline size_t icp_gen_pair_bytes(long long n1, long long n2)
 __global__ __launch_bounds__(kIcpThreads) void icp_generalized_build_source_kernel(const IcpPlaneArgs a)
 {
   const int b = blockIdx.x;
-  const long long row = a.rows ? a.rows[b] : b;
-  const long long s_lo = a.off[row * 2], n1 = a.off[(row + 1) * 2] - s_lo;
-  const long long n2 = a.off[(row + 1) * 2 + 1] - a.off[row * 2 + 1];
-  icp_grid_build_cloud(a.pts[0] + s_lo * 3, n1, a.ws + a.ws_off[b] + icp_gen_source_off(n2), a.normal_radius);
+  const IcpPair pr = icp_pair(a, b);
+  icp_grid_build_cloud(a.pts[0] + pr.s_lo * 3, pr.n1, a.ws + a.ws_off[b] + icp_gen_source_off(pr.n2), a.normal_radius);
 }
 
 __global__ __launch_bounds__(kIcpPlaneLanes) void icp_generalized_sort_source_kernel(const IcpPlaneArgs a)
@@ -1291,26 +1187,32 @@ __device__ __forceinline__ void icp_generalized_terms(double px, double py, doub
   for (int s = kLo; s < kHi; ++s) v[s - kLo] += t[s];
 }
 
-// kTrace (alignnet_debug_icp_generalized, one pair): as icp_plane_kernel's
-template <bool kFull, bool kTrace = false>
-__global__ __launch_bounds__(kIcpThreads) void icp_generalized_kernel(const IcpPlaneArgs a)
+// The loop of both normal-equation estimates: kGen = false point-to-plane (its terms stand in the loop), kGen = true generalized (icp_generalized_terms, and with
+// kFull its second pass); everything around the terms of a correspondence is one source.
+// kTrace (alignnet_debug_icp_plane / _generalized, one pair): the same evaluation with one record per source point behind it, then the sums and the
+// update of the estimate that follows, and no further iteration
+template <bool kGen, bool kFull, bool kTrace = false>
+__global__ __launch_bounds__(kIcpThreads) void icp_surface_kernel(const IcpPlaneArgs a)
 {
-  constexpr int kSums = kFull ? kIcpPlaneSumsFull : kIcpPlaneSums, kFirst = kFull ? kIcpGenSplit : kSums;   // kFirst: the slots of pass 0
+  constexpr int kSums = kFull ? kIcpPlaneSumsFull : kIcpPlaneSums, kFirst = kGen && kFull ? kIcpGenSplit : kSums;   // kFirst: the slots of pass 0
   extern __shared__ __attribute__((aligned(16))) int gstart[];   // [H + 1] bucket starts of grid A
   __shared__ double T[12];
   __shared__ double red[(kIcpThreads / 64) * kFirst], tot[kSums];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const long long row = a.rows ? a.rows[b] : b;
-  const long long s_lo = a.off[row * 2], n1 = a.off[(row + 1) * 2] - s_lo;
-  const long long t_lo = a.off[row * 2 + 1], n2 = a.off[(row + 1) * 2 + 1] - t_lo;
-  const float* src = a.pts[0] + s_lo * 3;
-  const float* dst = a.pts[1] + t_lo * 3;
+  const IcpPair pr = icp_pair(a, b);
+  const long long n1 = pr.n1, n2 = pr.n2;
+  const float* src = a.pts[0] + pr.s_lo * 3;
+  const float* dst = a.pts[1] + pr.t_lo * 3;
   if (tid < 12) T[tid] = a.init[(size_t)b * 16 + tid];
   IcpGridView g = icp_grid_view(a.ws + a.ws_off[b], n2);
   const double* const nrm = icp_plane_normals(g, n2);
-  const char* const sws = g.ws + icp_gen_source_off(n2);
-  const double* const snrm = reinterpret_cast<const double*>(sws + icp_gen_normals_off(n1));
-  [[maybe_unused]] int* const corr = reinterpret_cast<int*>(g.ws + icp_gen_source_off(n2) + icp_gen_corr_off(n1));
+  [[maybe_unused]] const double* snrm = nullptr;   // kGen: the source's normals and the correspondences of pass 0 (point-to-plane has no source part)
+  [[maybe_unused]] int* corr = nullptr;
+  if constexpr (kGen) {
+    const char* const sws = g.ws + icp_gen_source_off(n2);
+    snrm = reinterpret_cast<const double*>(sws + icp_gen_normals_off(n1));
+    corr = reinterpret_cast<int*>(g.ws + icp_gen_source_off(n2) + icp_gen_corr_off(n1));
+  }
   for (int j = tid; j <= g.buckets; j += kIcpThreads) gstart[j] = g.start[j];
   g.start = gstart;   // the search reads the LDS copy
   __syncthreads();
@@ -1334,20 +1236,50 @@ __global__ __launch_bounds__(kIcpThreads) void icp_generalized_kernel(const IcpP
           int cand = 0;   // (counted by icp_kernel's traced instantiation alone)
           icp_grid_nearest<false>(px, py, pz, g, best, bj, brec, cand);
           const bool inlier = best <= r2;
-          if constexpr (kFull) corr[i] = inlier ? bj : -1;
-          if (inlier)
-            icp_generalized_terms<kFull, 0, kFirst>(px, py, pz, (double)brec.x, (double)brec.y, (double)brec.z, nrm + (size_t)bj * 3, snrm + (size_t)i * 3, T,
-                                                    cx, cy, cz, best, v);
+          [[maybe_unused]] double res = 0.0;
+          if constexpr (kGen && kFull) corr[i] = inlier ? bj : -1;
+          if (inlier) {
+            if constexpr (kGen)
+              icp_generalized_terms<kFull, 0, kFirst>(px, py, pz, (double)brec.x, (double)brec.y, (double)brec.z, nrm + (size_t)bj * 3, snrm + (size_t)i * 3, T,
+                                                      cx, cy, cz, best, v);
+            else
+            {   // point-to-plane's terms, written out here: as a function like icp_generalized_terms they compile to another order
+              const double nx = nrm[(size_t)bj * 3], ny = nrm[(size_t)bj * 3 + 1], nz = nrm[(size_t)bj * 3 + 2];
+              res = icp_dot3_unfused(px - (double)brec.x, nx, py - (double)brec.y, ny, pz - (double)brec.z, nz);
+              const double ax = px - cx, ay = py - cy, az = pz - cz;
+              v[0] += 1.0; v[1] += best;
+              if constexpr (kFull) {
+                const double J[6] = {ay * nz - az * ny, az * nx - ax * nz, ax * ny - ay * nx, nx, ny, nz};
+                int q = 2;
+#pragma unroll
+                for (int i = 0; i < 6; ++i)
+#pragma unroll
+                  for (int j = i; j < 6; ++j) v[q++] += J[i] * J[j];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) v[23 + i] += J[i] * res;
+              } else {
+                const double J[4] = {ax * ny - ay * nx, nx, ny, nz};
+                int q = 2;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                  for (int j = i; j < 4; ++j) v[q++] += J[i] * J[j];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[12 + i] += J[i] * res;
+              }
+            }
+          }
           if constexpr (kTrace) {
             if (k == 0) {
               const bool found = bj != 0x7fffffff;
               a.tr_index[i] = found ? bj : -1; a.tr_dist[i] = found ? best : __builtin_huge_val(); a.tr_inlier[i] = inlier;
+              if constexpr (!kGen) a.tr_resid[i] = res;
             }
           }
         }
         block_reduce(v, red, tot);
       }
-      if constexpr (kFull) {   // pass 1: the lane's own correspondences again, the other slots
+      if constexpr (kGen && kFull) {   // pass 1: the lane's own correspondences again, the other slots
         double v[kSums - kFirst];
 #pragma unroll
         for (int q = 0; q < kSums - kFirst; ++q) v[q] = 0.0;
@@ -1401,6 +1333,11 @@ __global__ __launch_bounds__(kIcpThreads) void icp_generalized_kernel(const IcpP
     if (a.iters) a.iters[b] = k;
   }
 }
+
+using Loop = void (*)(const IcpPlaneArgs);
+constexpr Loop kIcpSurface[2][2][2] = {   // [gen][trace][full]
+    {{icp_surface_kernel<false, false>, icp_surface_kernel<false, true>}, {icp_surface_kernel<false, false, true>, icp_surface_kernel<false, true, true>}},
+    {{icp_surface_kernel<true, false>, icp_surface_kernel<true, true>}, {icp_surface_kernel<true, false, true>, icp_surface_kernel<true, true, true>}}};
 
 // alignnet_debug_icp_plane / _generalized: host arrays of the one pair (resid: point-to-plane; src_normals / src_neighbours: generalized; else null)
 struct IcpPlaneTrace {
@@ -1463,14 +1400,10 @@ int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* i
     a.tr_index = tri.p; a.tr_inlier = tri.p + tn;
   }
   static alignnet::PerDeviceOnce attr[8];
-  const int which = (full ? 1 : 0) + (trace ? 2 : 0), slot = which + (gen ? 4 : 0);
-  const void* const kernels[8] = {reinterpret_cast<const void*>(icp_plane_kernel<false>), reinterpret_cast<const void*>(icp_plane_kernel<true>),
-                                  reinterpret_cast<const void*>(icp_plane_kernel<false, true>), reinterpret_cast<const void*>(icp_plane_kernel<true, true>),
-                                  reinterpret_cast<const void*>(icp_generalized_kernel<false>), reinterpret_cast<const void*>(icp_generalized_kernel<true>),
-                                  reinterpret_cast<const void*>(icp_generalized_kernel<false, true>),
-                                  reinterpret_cast<const void*>(icp_generalized_kernel<true, true>)};
+  const int slot = (full ? 1 : 0) + (trace ? 2 : 0) + (gen ? 4 : 0);
+  const Loop loop = kIcpSurface[gen][trace != nullptr][full];
   if (attr[slot].need(h->cfg.device)) {
-    HIP_TRY(h, hipFuncSetAttribute(kernels[slot], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(loop), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(icp_grid_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096));
     if (gen)
       HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(icp_generalized_build_source_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1509,24 +1442,7 @@ int run_icp_plane(alignnet_handle* h, const IcpClouds& c, int B, const double* i
       hipLaunchKernelGGL(icp_generalized_normals_source_kernel, blocks, dim3(kIcpPlaneLanes), 0, h->stream, r);
     }
     alignnet::ProfScope prof_scope(h, gen ? alignnet::PK_ICP_GENERALIZED : alignnet::PK_ICP_PLANE);
-    if (gen) {
-      if (which == 3)
-        hipLaunchKernelGGL((icp_generalized_kernel<true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-      else if (which == 2)
-        hipLaunchKernelGGL((icp_generalized_kernel<false, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-      else if (full)
-        hipLaunchKernelGGL(icp_generalized_kernel<true>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-      else
-        hipLaunchKernelGGL(icp_generalized_kernel<false>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-    } else
-    if (which == 3)
-      hipLaunchKernelGGL((icp_plane_kernel<true, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-    else if (which == 2)
-      hipLaunchKernelGGL((icp_plane_kernel<false, true>), dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-    else if (full)
-      hipLaunchKernelGGL(icp_plane_kernel<true>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
-    else
-      hipLaunchKernelGGL(icp_plane_kernel<false>, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
+    hipLaunchKernelGGL(loop, dim3(hi - lo), dim3(kIcpThreads), lds, h->stream, r);
     HIP_TRY(h, hipGetLastError());
   }
   if (trace) {
@@ -1563,12 +1479,28 @@ int icp_plane_host(alignnet_handle* h, const char* fn, const float* points1, con
   return run_icp_plane(h, c, B, init, radius, normal_radius, its, full, gen, out, fitness, rmse, iterations, trace);
 }
 
-// flags of alignnet_icp_register*: bit 0 = full rotation; no other bit is defined
-int icp_flags(alignnet_handle* h, const char* fn, int32_t flags, bool* full)
+// what every entry point with flags checks first: the handle, then the flags of alignnet_icp_register* (bit 0 = full rotation; no other bit is defined)
+int icp_flags(alignnet_handle* h, const std::string& fn, int32_t flags, bool* full)
 {
-  if (flags & ~1) return fail(h, std::string(fn) + ": unknown flags " + std::to_string(flags) + " (bit 0 = full rotation is the only one)");
+  if (!h) return 1;
+  if (flags & ~1) return fail(h, fn + ": unknown flags " + std::to_string(flags) + " (bit 0 = full rotation is the only one)");
   *full = (flags & 1) != 0;
   return 0;
+}
+
+// the read-backs of one pair (alignnet_debug_icp_*): handle, flags, the sizes' range; off: the pair's offsets table
+int debug_arguments(alignnet_handle* h, const std::string& fn, int32_t flags, int64_t n1, int64_t n2, bool* full, int64_t* off /*[4]*/)
+{
+  if (icp_flags(h, fn, flags, full)) return 1;
+  if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(h, fn + ": n1 / n2 out of range");
+  off[0] = off[1] = 0; off[2] = n1; off[3] = n2;
+  return 0;
+}
+
+// the traced kernel's update (rows 0..2) as the 4x4 the read-backs return; ran = false (an empty cloud: no evaluation, no update): the identity
+void debug_update(const double* up /*[12]*/, bool ran, double* update /*[16]*/)
+{
+  for (int q = 0; q < 16; ++q) update[q] = q < 12 && ran ? up[q] : (q % 5 == 0 ? 1.0 : 0.0);
 }
 
 }  // namespace
@@ -1604,7 +1536,6 @@ extern "C" int alignnet_icp_register(alignnet_handle* h, const float* points1, c
                                      const double* init, double radius, int32_t its, int32_t flags, double* out, double* fitness, double* rmse,
                                      int32_t* iterations)
 {
-  if (!h) return 1;
   bool full = false;
   if (icp_flags(h, "alignnet_icp_register", flags, &full)) return 1;
   return icp_host(h, "alignnet_icp_register", points1, points2, offsets, B, init, radius, its, full, out, fitness, rmse, iterations);
@@ -1613,7 +1544,6 @@ extern "C" int alignnet_icp_register(alignnet_handle* h, const float* points1, c
 extern "C" int alignnet_icp_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, double radius,
                                              int32_t its, int32_t flags, double* out, double* fitness, double* rmse, int32_t* iterations)
 {
-  if (!h) return 1;
   bool full = false;
   if (icp_flags(h, "alignnet_icp_register_dataset", flags, &full)) return 1;
   return icp_rows(h, "alignnet_icp_register_dataset", rows, B, init, radius, its, full, out, fitness, rmse, iterations);
@@ -1655,14 +1585,12 @@ extern "C" int alignnet_debug_icp_scan(alignnet_handle* h, const float* points1,
                                        double radius, int32_t flags, int32_t lds_points, int32_t* index, double* dist2, int32_t* inlier,
                                        int32_t* paths, int32_t* lds_points_used, double* fitness, double* rmse)
 {
-  if (!h) return 1;
   const std::string name("alignnet_debug_icp_scan");
   bool full = false;
-  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
-  if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(h, name + ": n1 / n2 out of range");
+  int64_t off[4];
+  if (debug_arguments(h, name, flags, n1, n2, &full, off)) return 1;
   if (lds_points < 0 || lds_points > kIcpLdsBudget) return fail(h, name + ": lds_points must be in [0, " + std::to_string(kIcpLdsBudget) + "] (0 = as shipped)");
   if (!index || !dist2 || !inlier || !paths || !lds_points_used) return fail(h, name + ": null output");
-  const int64_t off[4] = {0, 0, n1, n2};
   const IcpTraceOut tr = {n1, lds_points, index, dist2, inlier, paths, lds_points_used, false, nullptr};
   double out[16];
   return icp_host(h, name.c_str(), points1, points2, off, 1, T, radius, 0, full, out, fitness, rmse, nullptr, &tr);
@@ -1672,13 +1600,11 @@ extern "C" int alignnet_debug_icp_grid(alignnet_handle* h, const float* points1,
                                        double radius, int32_t flags, int32_t* index, double* dist2, int32_t* inlier, int32_t* candidates,
                                        double* cell_edge, int32_t* buckets_occupied, int32_t* largest_bucket, double* fitness, double* rmse)
 {
-  if (!h) return 1;
   const std::string name("alignnet_debug_icp_grid");
   bool full = false;
-  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
-  if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(h, name + ": n1 / n2 out of range");
+  int64_t off[4];
+  if (debug_arguments(h, name, flags, n1, n2, &full, off)) return 1;
   if (!index || !dist2 || !inlier || !candidates || !cell_edge || !buckets_occupied || !largest_bucket) return fail(h, name + ": null output");
-  const int64_t off[4] = {0, 0, n1, n2};
   IcpGridInfo info = {0.0, 0, 0, 0, 0};
   const IcpTraceOut tr = {n1, 0, index, dist2, inlier, candidates, nullptr, true, &info};
   double out[16];
@@ -1691,7 +1617,6 @@ extern "C" int alignnet_icp_plane_register(alignnet_handle* h, const float* poin
                                            const double* init, double radius, double normal_radius, int32_t its, int32_t flags, double* out,
                                            double* fitness, double* rmse, int32_t* iterations)
 {
-  if (!h) return 1;
   bool full = false;
   if (icp_flags(h, "alignnet_icp_plane_register", flags, &full)) return 1;
   return icp_plane_host(h, "alignnet_icp_plane_register", points1, points2, offsets, B, init, radius, normal_radius, its, full, false, out, fitness, rmse, iterations);
@@ -1701,10 +1626,9 @@ extern "C" int alignnet_icp_plane_register_dataset(alignnet_handle* h, const int
                                                    double normal_radius, int32_t its, int32_t flags, double* out, double* fitness, double* rmse,
                                                    int32_t* iterations)
 {
-  if (!h) return 1;
   const std::string name("alignnet_icp_plane_register_dataset");
   bool full = false;
-  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
+  if (icp_flags(h, name, flags, &full)) return 1;
   IcpClouds c;
   if (stage_rows(h, name, rows, B, &c)) return 1;
   return run_icp_plane(h, c, B, init, radius, normal_radius, its, full, false, out, fitness, rmse, iterations);
@@ -1714,19 +1638,16 @@ extern "C" int alignnet_debug_icp_plane(alignnet_handle* h, const float* points1
                                         double radius, double normal_radius, int32_t flags, double* normals, int32_t* neighbours, int32_t* index,
                                         double* dist2, int32_t* inlier, double* residual, double* sums, double* update, double* fitness, double* rmse)
 {
-  if (!h) return 1;
   const std::string name("alignnet_debug_icp_plane");
   bool full = false;
-  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
-  if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(h, name + ": n1 / n2 out of range");
+  int64_t off[4];
+  if (debug_arguments(h, name, flags, n1, n2, &full, off)) return 1;
   if (!normals || !neighbours || !index || !dist2 || !inlier || !residual || !sums || !update) return fail(h, name + ": null output");
-  const int64_t off[4] = {0, 0, n1, n2};
   double up[12];
   const IcpPlaneTrace tr = {n1, n2, normals, neighbours, index, dist2, inlier, residual, sums, up};
   double out[16];
   if (icp_plane_host(h, name.c_str(), points1, points2, off, 1, T, radius, normal_radius, 0, full, false, out, fitness, rmse, nullptr, &tr)) return 1;
-  const bool ran = n1 > 0 && n2 > 0;   // (an empty cloud: no evaluation, no update)
-  for (int q = 0; q < 16; ++q) update[q] = q < 12 && ran ? up[q] : (q % 5 == 0 ? 1.0 : 0.0);
+  debug_update(up, n1 > 0 && n2 > 0, update);
   return 0;
 }
 
@@ -1734,7 +1655,6 @@ extern "C" int alignnet_icp_generalized_register(alignnet_handle* h, const float
                                                  const double* init, double radius, double normal_radius, int32_t its, int32_t flags, double* out,
                                                  double* fitness, double* rmse, int32_t* iterations)
 {
-  if (!h) return 1;
   bool full = false;
   if (icp_flags(h, "alignnet_icp_generalized_register", flags, &full)) return 1;
   return icp_plane_host(h, "alignnet_icp_generalized_register", points1, points2, offsets, B, init, radius, normal_radius, its, full, true, out, fitness,
@@ -1745,10 +1665,9 @@ extern "C" int alignnet_icp_generalized_register_dataset(alignnet_handle* h, con
                                                          double normal_radius, int32_t its, int32_t flags, double* out, double* fitness, double* rmse,
                                                          int32_t* iterations)
 {
-  if (!h) return 1;
   const std::string name("alignnet_icp_generalized_register_dataset");
   bool full = false;
-  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
+  if (icp_flags(h, name, flags, &full)) return 1;
   IcpClouds c;
   if (stage_rows(h, name, rows, B, &c)) return 1;
   return run_icp_plane(h, c, B, init, radius, normal_radius, its, full, true, out, fitness, rmse, iterations);
@@ -1759,21 +1678,18 @@ extern "C" int alignnet_debug_icp_generalized(alignnet_handle* h, const float* p
                                               double* source_normals, int32_t* source_neighbours, int32_t* index, double* dist2, int32_t* inlier,
                                               double* sums, double* update, double* fitness, double* rmse)
 {
-  if (!h) return 1;
   const std::string name("alignnet_debug_icp_generalized");
   bool full = false;
-  if (icp_flags(h, name.c_str(), flags, &full)) return 1;
-  if (n1 < 0 || n2 < 0 || n1 > 0x7fffffff || n2 > 0x7fffffff) return fail(h, name + ": n1 / n2 out of range");
+  int64_t off[4];
+  if (debug_arguments(h, name, flags, n1, n2, &full, off)) return 1;
   if (!target_normals || !target_neighbours || !source_normals || !source_neighbours || !index || !dist2 || !inlier || !sums || !update)
     return fail(h, name + ": null output");
-  const int64_t off[4] = {0, 0, n1, n2};
   double up[12];
   IcpPlaneTrace tr = {n1, n2, target_normals, target_neighbours, index, dist2, inlier, nullptr, sums, up};
   tr.src_normals = source_normals; tr.src_neighbours = source_neighbours;
   double out[16];
   if (icp_plane_host(h, name.c_str(), points1, points2, off, 1, T, radius, normal_radius, 0, full, true, out, fitness, rmse, nullptr, &tr)) return 1;
-  const bool ran = n1 > 0 && n2 > 0;   // (an empty cloud: no evaluation, no update)
-  for (int q = 0; q < 16; ++q) update[q] = q < 12 && ran ? up[q] : (q % 5 == 0 ? 1.0 : 0.0);
+  debug_update(up, n1 > 0 && n2 > 0, update);
   return 0;
 }
 

@@ -4,7 +4,7 @@
 // (train.py:447-481): eight tensors come down, three list comprehensions decode the yaws (models/tp8.py:55-65), get_mat_angle runs once per
 // sample (evaluation.py:46-57) and the 4x4 inits go up again for the ICP call.  Here the same chain is queued on the handle's stream in one piece:
 //   dataset_sample_kernel (alignnet_dataset.hip) -> the eval forward (alignnet_forward_device) -> register_decode_kernel -> register_init_kernel
-//   -> [the loss of alignnet_eval_loss on the dataset's labels] -> [icp_kernel / icp_plane_kernel / icp_generalized_kernel from the device-resident T_net] -> downloads
+//   -> [the loss of alignnet_eval_loss on the dataset's labels] -> [icp_kernel / icp_surface_kernel from the device-resident T_net] -> downloads
 // and the host waits once, at the end.  Every buffer lives in RegisterWS on the handle: it grows when B grows (and, for clouds from the host, when
 // they do), so a steady-state call allocates nothing.  The two kernels here are a few hundred flops per pair; what matters is that they are two
 // launches between two latency-critical stages and that their fp64 arithmetic is NumPy's to the last bit (no contraction).

@@ -1,5 +1,5 @@
 """fp64 restatement of GENERALIZED (plane-to-plane) ICP, the definition of alignnet_icp_generalized_register* (csrc/alignnet_icp.hip:
-icp_generalized_kernel and the normals kernels run on both clouds) -- tests/test_icp_generalized_cpu.py and tests/test_icp_generalized_gpu.py.
+icp_surface_kernel<true, .> and the normals kernels run on both clouds) -- tests/test_icp_generalized_cpu.py and tests/test_icp_generalized_gpu.py.
 TEST INFRASTRUCTURE ONLY; NumPy fp64 throughout.  Normals, evaluation, transform, solve and the input builders are tests/icp_plane_ref.py's.
 
 Method: Segal, Haehnel, Thrun, "Generalized-ICP" (2009), with the surface covariances of Open3D's registration_generalized_icp (epsilon = 1e-3).

@@ -1,5 +1,5 @@
 """fp64 restatement of POINT-TO-PLANE ICP, the definition of alignnet_icp_plane_register* (csrc/alignnet_icp.hip: icp_plane_normals_kernel,
-icp_plane_kernel) -- tests/test_icp_plane_cpu.py and tests/test_icp_plane_gpu.py.  TEST INFRASTRUCTURE ONLY; NumPy fp64 throughout (scipy's cKDTree
+icp_surface_kernel<false, .>) -- tests/test_icp_plane_cpu.py and tests/test_icp_plane_gpu.py.  TEST INFRASTRUCTURE ONLY; NumPy fp64 throughout (scipy's cKDTree
 only proposes neighbour candidates, every decision is taken on distances computed here).
 
 The reference names the method and leaves it `assert False` (icp.py:81-82), so nothing pins the arithmetic but this file.

@@ -1,4 +1,4 @@
-"""GPU: generalized ICP (Engine.icp_generalized_refine*, csrc/alignnet_icp.hip: the normals kernels on both clouds, icp_generalized_kernel) against
+"""GPU: generalized ICP (Engine.icp_generalized_refine*, csrc/alignnet_icp.hip: the normals kernels on both clouds, icp_surface_kernel<true, .>) against
 the fp64 restatement tests/icp_generalized_ref.py.  Stage by stage through Engine.debug_icp_generalized (the shipped source compiled with a record
 behind it), every stage fed the DEVICE's own upstream outputs: both clouds' neighbour counts equal, normals to 1e-8, index / inlier / fitness equal,
 squared distances to 1e-12 relative, every sum within 64 n u sum |term| (n = the inliers, u = 2^-53: the terms are the restatement's to the bit, the

@@ -1,4 +1,4 @@
-"""GPU: point-to-plane ICP (Engine.icp_plane_refine*, csrc/alignnet_icp.hip: icp_plane_sort_kernel, icp_plane_normals_kernel, icp_plane_kernel)
+"""GPU: point-to-plane ICP (Engine.icp_plane_refine*, csrc/alignnet_icp.hip: icp_plane_sort_kernel, icp_plane_normals_kernel, icp_surface_kernel<false, .>)
 against the fp64 restatement tests/icp_plane_ref.py.  Stage by stage through Engine.debug_icp_plane (the shipped source compiled with a record behind
 it), every stage fed the DEVICE's own upstream outputs: neighbour counts equal, normals to 1e-8, index / inlier / fitness equal, squared distances and
 residuals to 1e-12 relative, every sum within 4 n u sum |term| (the rounding bound of an n-term fp64 sum, u = 2^-53), the update within 1e-9 of the
