@@ -155,6 +155,16 @@ SYMBOLS = {
     "alignnet_icp_generalized_register_dataset": (C.c_int, [H, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int32,
                                                             C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                             C.POINTER(C.c_int32)]),
+    "alignnet_icp_multiscale_register": (C.c_int, [H, FP, FP, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32,
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32)]),
+    "alignnet_icp_multiscale_register_dataset": (C.c_int, [H, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double),
+                                                           C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32,
+                                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                                           C.POINTER(C.c_int32)]),
+    "alignnet_debug_voxel_pyramid": (C.c_int, [H, FP, C.c_int64, C.c_int32, C.POINTER(C.c_double), FP, C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "alignnet_debug_icp_generalized": (C.c_int, [H, FP, C.c_int64, FP, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int32,
                                                  C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                  C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -225,7 +235,8 @@ SYMBOLS = {
 # symbols added after ABI version 1 was fixed: an earlier build named by ALIGNNET_HIP_LIB loads without them
 LATE_SYMBOLS = ("alignnet_register", "alignnet_register_dataset", "alignnet_tracklet_extract_frustum", "alignnet_goicp_register",
                 "alignnet_goicp_register_dataset", "alignnet_evaluate_registration", "alignnet_evaluate_registration_dataset",
-                "alignnet_icp_generalized_register", "alignnet_icp_generalized_register_dataset", "alignnet_pose_graph_optimize")
+                "alignnet_icp_generalized_register", "alignnet_icp_generalized_register_dataset", "alignnet_pose_graph_optimize", "alignnet_icp_multiscale_register",
+                "alignnet_icp_multiscale_register_dataset")
 
 _lib = None
 

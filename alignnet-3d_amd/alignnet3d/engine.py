@@ -525,6 +525,62 @@ class Engine:
         return self._icp_surface(self._register_fn("alignnet_icp_generalized_register_dataset"), (rp,), inits, r.size, radius, normal_radius, its,
                                  constrained)
 
+    # ---- multi-scale (coarse-to-fine) ICP (csrc/alignnet_multiscale.hip; definition: tests/icp_multiscale_ref.py) ----
+    def _icp_multiscale(self, fn, lead, inits, B, voxel_sizes, radii, its, estimate, normal_radius, constrained):
+        """One multi-scale call through `fn`: the schedule's three lists go down as arrays of L, normal_radius as a scalar or a list of L."""
+        if estimate not in ("point", "plane", "generalized"):
+            raise ValueError("estimate must be one of point, plane, generalized, got %r" % (estimate,))
+        vs = np.ascontiguousarray(voxel_sizes, np.float64).reshape(-1)
+        rd = np.ascontiguousarray(radii, np.float64).reshape(-1)
+        it = np.ascontiguousarray(its, np.int32).reshape(-1)
+        L = vs.size
+        if rd.size != L or it.size != L:
+            raise ValueError("voxel_sizes, radii and its must have one entry per level (%d, %d, %d)" % (L, rd.size, it.size))
+        nr = np.ascontiguousarray(np.broadcast_to(np.asarray(normal_radius, np.float64).reshape(-1), (L,)) if L else np.zeros(0))
+        init = np.ascontiguousarray(inits, np.float64).reshape(B, 16)
+        out = np.empty((B, 16), np.float64)
+        fit, rmse = np.empty(B, np.float64), np.empty(B, np.float64)
+        iters, sizes = np.zeros((B, max(L, 1)), np.int32), np.zeros((B, max(L, 1), 2), np.int32)
+        self._check(fn(self._h, *lead, B, _dp(init), L, _dp(vs), _dp(rd), _ip(it), _dp(nr), self.REFINE[estimate],
+                       0 if constrained else ICP_FULL_ROTATION, _dp(out), _dp(fit), _dp(rmse), _ip(iters), _ip(sizes)))
+        return dict(transforms=out.reshape(B, 4, 4), fitness=fit, rmse=rmse, iterations=iters, level_sizes=sizes)
+
+    def icp_multiscale_refine(self, sources, targets, inits, voxel_sizes, radii, its, estimate="point", normal_radius=0.3, constrained=True):
+        """Coarse-to-fine ICP (Open3D's multi_scale_icp): level l voxel-downsamples both clouds of every pair at voxel_sizes[l] (<= 0: the raw
+        clouds) and runs icp_refine / icp_plane_refine / icp_generalized_refine (`estimate`) on them with radii[l] and its[l], from the
+        transform of the level before (level 0: `inits`).  The level clouds and the transforms between levels stay on the device.  Returns
+        dict(transforms, fitness, rmse: the last level's, on its clouds at its radius; iterations [B, L]; level_sizes [B, L, 2])."""
+        p1, p2, off = _pack_pairs(sources, targets)
+        return self._icp_multiscale(self._register_fn("alignnet_icp_multiscale_register"), (_fp(p1), _fp(p2), _lp(off)), inits, len(sources),
+                                    voxel_sizes, radii, its, estimate, normal_radius, constrained)
+
+    def icp_multiscale_refine_rows(self, rows, inits, voxel_sizes, radii, its, estimate="point", normal_radius=0.3, constrained=True):
+        """Same on the clouds of the uploaded dataset (upload_dataset), addressed by example rows."""
+        r, rp = self._rows(rows)
+        return self._icp_multiscale(self._register_fn("alignnet_icp_multiscale_register_dataset"), (rp,), inits, r.size, voxel_sizes, radii, its,
+                                    estimate, normal_radius, constrained)
+
+    def debug_voxel_pyramid(self, cloud, voxel_sizes):
+        """Test hook: the level clouds of one cloud as the multi-scale ICP builds them, through the shipped kernels.  Returns a list with one
+        dict per level: points [m, 3] float32 (what the ICP reads), means [m, 3] float64 (before the rounding), voxels [m, 3] int32 in
+        ascending (ix, iy, iz), counts [m] int32.  A level with voxel <= 0 is the raw cloud: voxels None, counts all 1."""
+        p = np.ascontiguousarray(np.asarray(cloud, np.float32).reshape(-1, 3))
+        vs = np.ascontiguousarray(voxel_sizes, np.float64).reshape(-1)
+        n, L = len(p), vs.size
+        cap = max(n, 1)
+        pts, mean = np.zeros((max(L, 1), cap, 3), np.float32), np.zeros((max(L, 1), cap, 3), np.float64)
+        vox, cnt, sizes = np.zeros((max(L, 1), cap, 3), np.int32), np.zeros((max(L, 1), cap), np.int32), np.zeros(max(L, 1), np.int64)
+        # (the library lays the levels out [L][n]: with n = 0 nothing is written)
+        self._check(self._register_fn("alignnet_debug_voxel_pyramid")(self._h, _fp(p), n, L, _dp(vs), _fp(pts), _dp(mean), _ip(vox), _ip(cnt), _lp(sizes)))
+        levels = []
+        for l in range(L):
+            if not vs[l] > 0:
+                levels.append(dict(points=p.copy(), means=p.astype(np.float64), voxels=None, counts=np.ones(n, np.int32)))
+                continue
+            m = int(sizes[l])
+            levels.append(dict(points=pts[l, :m].copy(), means=mean[l, :m].copy(), voxels=vox[l, :m].copy(), counts=cnt[l, :m].copy()))
+        return levels
+
     # ---- one-call registration: clouds to transforms on the device (csrc/alignnet_register.hip; DESIGN.md 4.8b) ----
     REFINE = {None: 0, "point": 1, "plane": 2, "generalized": 4}   # (the option values of alignnet_register_options.refine; 3 is not assigned)
 
@@ -1319,7 +1375,7 @@ class Engine:
     PROFILED_KERNELS = ("backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2", "train_bwd_b1",
                         "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact",
                         "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band",
-                        "tracklet_test", "tracklet_compact", "icp_generalized_normals", "icp_generalized", "pose_graph")
+                        "tracklet_test", "tracklet_compact", "icp_generalized_normals", "icp_generalized", "pose_graph", "icp_pyramid")
 
     def profile_kernels(self):
         """{kernel: (ms, launches)} accumulated since the last profile_read(reset=True); call BEFORE that reset."""

@@ -205,6 +205,7 @@ extern "C" void alignnet_destroy(alignnet_handle* h)
   alignnet_goicp_free(h);
   alignnet_posegraph_free(h);
   alignnet_register_free(h);
+  alignnet_multiscale_free(h);
   pipe_free(h);
   free_ws(h);
   for (auto& pr : h->prof_pending) { hipEventDestroy(pr.a); hipEventDestroy(pr.b); }
@@ -1085,6 +1086,7 @@ extern "C" int alignnet_get_option(alignnet_handle* h, const char* key, int64_t*
   if (k == "pose_graph_lds_budget") { *value = h->pose_graph_lds_budget; return 0; }
   if (k == "pose_graph_lds_graphs") { *value = h->pose_graph_lds_graphs; return 0; }
   if (k == "icp_grid_ws_bytes") { *value = (int64_t)h->icp_grid_ws_used; return 0; }
+  if (k == "icp_multiscale_ws_bytes") { *value = (int64_t)h->multiscale_ws_used; return 0; }
   if (k == "scene_cast") { *value = h->scene_cast; return 0; }
   if (k == "scene_rows") { *value = h->scene_rows; return 0; }
   if (k == "scene_binned_clouds") { *value = h->scene_binned_clouds; return 0; }

@@ -37,9 +37,9 @@ struct Stack { int first, n; };   // range of layers
 // Kernels whose launches are bracketed with HIP events on the handle's stream while profiling is enabled
 // (alignnet_profile_enable; read back by name through alignnet_profile_read_kernel -- bench.py's roofline legs).
 enum ProfKernel { PK_BACKBONE = 0, PK_KNN, PK_TRAIN_PHASE2, PK_TRAIN_PHASE3, PK_TRAIN_GRAM, PK_TRAIN_B2, PK_TRAIN_B1, PK_DG_FWD, PK_DG_BWD_EDGE,
-                  PK_ALLREDUCE, PK_OPTIMIZER, PK_SCENE_WINDOW, PK_SCENE_CAST, PK_SCENE_COMPACT, PK_ICP_GRID_BUILD, PK_ICP_GRID, PK_SCENE_BIN, PK_ICP_PLANE_NORMALS, PK_ICP_PLANE, PK_SCENE_BAND, PK_TRACKLET_TEST, PK_TRACKLET_COMPACT, PK_ICP_GENERALIZED_NORMALS, PK_ICP_GENERALIZED, PK_POSE_GRAPH, PK_COUNT };
+                  PK_ALLREDUCE, PK_OPTIMIZER, PK_SCENE_WINDOW, PK_SCENE_CAST, PK_SCENE_COMPACT, PK_ICP_GRID_BUILD, PK_ICP_GRID, PK_SCENE_BIN, PK_ICP_PLANE_NORMALS, PK_ICP_PLANE, PK_SCENE_BAND, PK_TRACKLET_TEST, PK_TRACKLET_COMPACT, PK_ICP_GENERALIZED_NORMALS, PK_ICP_GENERALIZED, PK_POSE_GRAPH, PK_ICP_PYRAMID, PK_COUNT };
 static const char* const kProfKernelNames[PK_COUNT] = {"backbone", "knn", "train_fwd_phase2", "train_fwd_phase3", "train_gram_h2", "train_bwd_b2",
-                                                       "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact", "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band", "tracklet_test", "tracklet_compact", "icp_generalized_normals", "icp_generalized", "pose_graph"};
+                                                       "train_bwd_b1", "dg_train_fwd", "dg_train_bwd_edge", "allreduce", "optimizer", "scene_window", "scene_cast", "scene_compact", "icp_grid_build", "icp_grid", "scene_bin", "icp_plane_normals", "icp_plane", "scene_band", "tracklet_test", "tracklet_compact", "icp_generalized_normals", "icp_generalized", "pose_graph", "icp_pyramid"};
 
 // KITTI tracklet extraction (alignnet_crop.hip); read back as the options "tracklet_chunk" / "tracklet_jobs_per_pass"
 constexpr int kTrackletChunk = 1024;        // points of a frame per workgroup
@@ -116,6 +116,7 @@ int alignnet_icp_run_device(alignnet_handle* h, const float* const pts[2], const
 size_t alignnet_eval_loss_work_floats(int B);
 int alignnet_eval_loss_launch(alignnet_handle* h, const alignnet_labels* d_labels, int B, float* d_work);
 void alignnet_register_free(alignnet_handle* h);   // alignnet_register.hip
+void alignnet_multiscale_free(alignnet_handle* h); // alignnet_multiscale.hip
 int alignnet_drain_profile(alignnet_handle* h);
 // options that live with the training / communicator code (alignnet_train.hip); -1 = not one of its keys
 int alignnet_train_set_option(alignnet_handle* h, const std::string& key, int64_t value);
@@ -177,6 +178,8 @@ struct alignnet_handle {
   int icp_plane_chunks = 0;        // "icp_plane_chunks" (read-only): chunks the last point-to-plane call ran
   size_t icp_generalized_ws_budget = 0;  // "icp_generalized_ws_budget": the same for a chunk of generalized-ICP pairs
   int icp_generalized_chunks = 0;        // "icp_generalized_chunks" (read-only): chunks the last generalized-ICP call ran
+  void* multiscale_ws = nullptr;   // sort records, level clouds and tables, chained results of the multi-scale ICP (alignnet_multiscale.hip), grown on demand
+  size_t multiscale_ws_bytes = 0, multiscale_ws_used = 0;   // allocated; carved by the last call ("icp_multiscale_ws_bytes")
   void* pose_graph_ws = nullptr;   // inputs, results and per-graph working arrays of the pose-graph optimisation (alignnet_posegraph.hip), grown on demand
   size_t pose_graph_ws_bytes = 0;
   size_t pose_graph_ws_budget = 0; // "pose_graph_ws_budget": per-graph working arrays of one chunk of graphs; 0 = 1 GiB

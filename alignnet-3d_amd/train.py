@@ -494,10 +494,54 @@ def icp_estimate_option(config=None, environ=None):
     return name, radius
 
 
+ICP_MULTISCALE_MAX_LEVELS = 8
+
+
+def icp_multiscale_option(config=None):
+    """Optional, not a reference key: "evaluation": {"icp_multiscale": {"voxel_sizes": [...], "radii": [...], "its": [...]}} runs every ICP call of
+    icp_rows() coarse to fine (Engine.icp_multiscale_refine_rows): one level per list entry, voxel_sizes[l] <= 0 = the full clouds.
+    No default schedule: the three lists are required.  Absent or false: off, every call as it was.  Returns (voxel_sizes, radii, its), or None."""
+    config = cfg if config is None else config
+    opt = getattr(getattr(config, "evaluation", None), "icp_multiscale", None)
+    if opt is None or opt is False:
+        return None
+    key = "evaluation.icp_multiscale"
+    get = (lambda k: opt.get(k)) if isinstance(opt, dict) else (lambda k: getattr(opt, k, None))
+    lists = []
+    for k in ("voxel_sizes", "radii", "its"):
+        v = get(k)
+        if not isinstance(v, (list, tuple)) or len(v) == 0:
+            raise ValueError("%s.%s: expected a non-empty list with one entry per level" % (key, k))
+        lists.append(list(v))
+    voxel_sizes, radii, its = lists
+    if not (len(voxel_sizes) == len(radii) == len(its)):
+        raise ValueError("%s: voxel_sizes, radii and its must have equal lengths (%d, %d, %d)" % (key, len(voxel_sizes), len(radii), len(its)))
+    if len(voxel_sizes) > ICP_MULTISCALE_MAX_LEVELS:
+        raise ValueError("%s: at most %d levels, got %d" % (key, ICP_MULTISCALE_MAX_LEVELS, len(voxel_sizes)))
+    try:
+        voxel_sizes, radii = [float(v) for v in voxel_sizes], [float(r) for r in radii]
+        if any(int(i) != i for i in its):
+            raise TypeError
+        its = [int(i) for i in its]
+    except (TypeError, ValueError):
+        raise ValueError("%s: voxel_sizes and radii must be numbers, its integers" % key)
+    if any(not r > 0.0 for r in radii):
+        raise ValueError("%s.radii = %r: every radius must be > 0" % (key, radii))
+    if any(i < 0 for i in its):
+        raise ValueError("%s.its = %r: every budget must be >= 0" % (key, its))
+    if any(v != v or v in (float("inf"), float("-inf")) for v in voxel_sizes):
+        raise ValueError("%s.voxel_sizes = %r: every voxel size must be finite" % (key, voxel_sizes))
+    return voxel_sizes, radii, its
+
+
 def icp_rows(engine, rows, inits, radius, its, constrained=True):
     """The ICP call of the --refineICP refinement and of the ICP mode: point-to-point, or point-to-plane / generalized when icp_estimate_option()
-    says so."""
+    says so; coarse to fine when icp_multiscale_option() gives a schedule (its radii and budgets then supersede `radius` and `its`)."""
     name, normal_radius = icp_estimate_option()
+    schedule = icp_multiscale_option()
+    if schedule is not None:
+        return engine.icp_multiscale_refine_rows(rows, inits, schedule[0], schedule[1], schedule[2], estimate=name, normal_radius=normal_radius,
+                                                 constrained=constrained)
     if name == "plane":
         return engine.icp_plane_refine_rows(rows, inits, radius=radius, normal_radius=normal_radius, its=its, constrained=constrained)
     if name == "generalized":
@@ -507,6 +551,9 @@ def icp_rows(engine, rows, inits, radius, its, constrained=True):
 
 def log_icp_estimate():
     name, normal_radius = icp_estimate_option()
+    schedule = icp_multiscale_option()
+    if schedule is not None:
+        logger.info("ICP multi-scale: voxel sizes %s, radii %s, iterations %s (supersede the call's radius and --its)" % schedule)
     if name == "plane":
         logger.info("ICP estimate: point-to-plane (target normals within %g m)" % normal_radius)
     if name == "generalized":

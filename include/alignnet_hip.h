@@ -444,6 +444,37 @@ int alignnet_debug_icp_generalized(alignnet_handle* h, const float* points1, int
                                    int32_t* source_neighbours, int32_t* index, double* dist2, int32_t* inlier,
                                    double* sums, double* update, double* fitness, double* rmse);
 
+/* ---- multi-scale (coarse-to-fine) ICP (Open3D's multi_scale_icp; definition: tests/icp_multiscale_ref.py) --
+ * Clouds, offsets, init / out, fitness and rmse as alignnet_icp_register.  The call has L levels, 1 <= L <= 8, described by
+ * three arrays of L: voxel_sizes[l] > 0 voxel-downsamples both clouds of every pair at that edge (origin = the cloud's
+ * float32 minimum per axis as a double minus half an edge, floor((p - origin) / edge) in fp64, output in ascending (ix, iy,
+ * iz), the mean of a voxel's points summed in fp64 in ascending point index, divided by their number and rounded to
+ * float32), <= 0 takes the raw clouds; radii[l] > 0 is the level's correspondence radius; its[l] >= 0 its iteration budget
+ * (0: evaluate only).  Level l runs the ICP named by `estimate` -- 1 alignnet_icp_register, 2 alignnet_icp_plane_register,
+ * 4 alignnet_icp_generalized_register, the values of alignnet_register_options.refine -- on its clouds from the transform
+ * of level l - 1 (level 0: init), with normals (2, 4) taken on the level's own clouds within normal_radii[l] (> 0; may be
+ * NULL for estimate 1).  flags: bit 0 = full rotation.  out / fitness / rmse are the last level's, on its clouds at its
+ * radius; iterations [B][L] and level_sizes [B][L][2] (source, target points of the level) may be NULL.  The level clouds
+ * and the transforms between levels stay on the device: the host waits twice, for the levels' sizes and for the results.
+ * A cloud wider than 2^21 voxels on an axis at one of the voxel sizes, or with a coordinate that is not finite, fails the
+ * call; so does an L out of range, a radius <= 0, a negative its or a NULL list, before anything is launched.  The
+ * point-to-point levels search as "icp_search" says.  Workspace: the handle's, grown on demand ("icp_multiscale_ws_bytes"
+ * reads what the last call carved): 24 bytes per raw point and downsampled level plus the tables. */
+int alignnet_icp_multiscale_register(alignnet_handle* h, const float* points1, const float* points2, const int64_t* offsets,
+                                     int32_t B, const double* init, int32_t L, const double* voxel_sizes, const double* radii,
+                                     const int32_t* its, const double* normal_radii, int32_t estimate, int32_t flags,
+                                     double* out, double* fitness, double* rmse, int32_t* iterations, int32_t* level_sizes);
+int alignnet_icp_multiscale_register_dataset(alignnet_handle* h, const int32_t* rows, int32_t B, const double* init, int32_t L,
+                                             const double* voxel_sizes, const double* radii, const int32_t* its,
+                                             const double* normal_radii, int32_t estimate, int32_t flags, double* out,
+                                             double* fitness, double* rmse, int32_t* iterations, int32_t* level_sizes);
+/* Test hook: the level clouds of ONE cloud of n points through the shipped pyramid kernels.  Every output holds L slots of n
+ * entries; level l fills the first sizes[l] of its slot: cloud [L][n][3] the float32 points the ICP reads, means [L][n][3]
+ * the fp64 means before the rounding, voxels [L][n][3] the voxel indices, counts [L][n] the points per voxel.  A level with
+ * voxel <= 0 is the caller's own cloud: sizes[l] = n and its slots are left as they are. */
+int alignnet_debug_voxel_pyramid(alignnet_handle* h, const float* points, int64_t n, int32_t L, const double* voxel_sizes,
+                                 float* cloud, double* means, int32_t* voxels, int32_t* counts, int64_t* sizes);
+
 /* ---- one-call registration: two raw clouds per pair in, a 4x4 transform per pair out ------------
  * The chain the evaluation loop joins in host Python (train.py:447-481), queued as one piece on the device: the
  * sampler (alignnet_dataset_sample's draw, no jitter), the eval forward, the decode of the three yaws in fp64
@@ -843,6 +874,8 @@ int alignnet_tracklet_extract_frustum(alignnet_handle* h, const int32_t* frames,
  *   which is the faster staging there once the bands have cut the intersections.  Off by default.
  *   "icp_grid_ws_bytes" (read-only): the workspace the last call with grid pairs carved (per chunk of pairs, at most 1 GiB unless one pair
  *   needs more; freed with the handle).
+ *   "icp_multiscale_ws_bytes" (read-only): the workspace the last alignnet_icp_multiscale_register* / alignnet_debug_voxel_pyramid call
+ *   carved (sort records, level clouds, tables, chained results; freed with the handle).
  * "icp_plane_ws_budget" (bytes, default 0 = 1 GiB): the workspace one chunk of pairs of alignnet_icp_plane_register* may take (two grids,
  *   ordered records, normals and counts per pair; a pair that needs more forms a chunk alone).  Results do not depend on it: a smaller value
  *   only cuts a call into more chunks (a test hook for the chunking, and a way to bound the allocation).
